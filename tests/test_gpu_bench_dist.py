@@ -34,7 +34,7 @@ def test_bench_two_ranks_gloo(tmp_path):
     env = dict(os.environ, BPP_DIST_BACKEND="gloo", TMPDIR=os.environ.get("TMPDIR", "/tmp"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
-           "--gpus", "2", "--steps", "4", "--warmup", "1", "--log2n", "20", "--no-cpu",
+           "--gpus", "2", "--steps", "4", "--warmup", "1", "--log2n", "20", "--full", "--no-cpu",
            "--proofs-per-gpu", "64", "--proof-streams", "2", "--proof-steps", "2",
            "--verify-proofs", "512", "--verify-steps", "1", "--job-proofs", "256", "--job-reps", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)

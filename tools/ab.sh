@@ -62,7 +62,7 @@ for cfg in "$@"; do
     done
     case $LEG in
       msm|msmv|full)
-        args="--no-cpu --steps ${STEPS:-20} --warmup ${WARMUP:-2} --inflight ${INFLIGHT:-3}"
+        args="--full --no-cpu --steps ${STEPS:-20} --warmup ${WARMUP:-2} --inflight ${INFLIGHT:-3}"
         [ $LEG = full ] || args="$args --proofs-per-gpu 0"
         [ $LEG = msm ] && args="$args --verify-proofs 0"
         args="$args --no-extra ${BENCH_ARGS//,/ }"

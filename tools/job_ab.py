@@ -11,7 +11,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 for spec in sys.argv[1].split(","):
     tot, jb = spec.split(":")
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--no-cpu", "--steps", "2", "--warmup", "1", "--proof-steps", "1",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--no-cpu", "--steps", "2", "--warmup", "1", "--proof-steps", "1",
            "--proofs-per-gpu", "64", "--proof-streams", "32", "--verify-proofs", "0", "--no-extra",
            "--job-proofs", tot, "--job-batch", jb, "--job-reps", "5"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
