@@ -557,6 +557,44 @@ class PermProver:
         return ([praw[i * self.proof_len:(i + 1) * self.proof_len] for i in range(count)],
                 [vraw[i * 32 * self.m:(i + 1) * 32 * self.m] for i in range(count)])
 
+    def prove_shuffle_batch(self, cards, perms, seeds32: bytes | None = None, gammas=None, raw: bool = False):
+        """Proves caller-supplied shuffles (bpp_perm_prove_shuffle_batch):
+        cards[p] = the k canonical 32-byte scalars of proof p's deck (or their
+        32 k bytes joined), perms[p] = k indices, output slot i holding
+        cards[p][perms[p][i]]; gammas[p] = the 2k blindings of V_0..V_2k-1
+        (None: drawn); seeds32 = 32 bytes per proof (None: the OS CSPRNG).
+        Returns what prove_batch returns; the batch's secrets are wiped."""
+        count = len(cards)
+        if len(perms) != count or (gammas is not None and len(gammas) != count):
+            raise ValueError("cards, perms and gammas must have one entry per proof")
+        if seeds32 is not None and len(seeds32) != 32 * count:
+            raise ValueError("seeds32 must hold 32 bytes per proof")
+
+        def rows(items, n, what):
+            out = b"".join(x if isinstance(x, (bytes, bytearray)) else _join(x, 32, what) for x in items)
+            if len(out) != 32 * n * count:
+                raise ValueError(f"{what}: expected {n} scalars of 32 bytes per proof")
+            return out
+
+        cb = rows(cards, self.k, "cards")
+        gb = rows(gammas, 2 * self.k, "gammas") if gammas is not None else None
+        flat = [int(i) for p in perms for i in p]
+        if len(flat) != self.k * count:
+            raise ValueError("perms: expected k indices per proof")
+        pm = (C.c_uint32 * len(flat))(*flat)
+        pf = C.create_string_buffer(self.proof_len * count)
+        V = C.create_string_buffer(32 * self.m * count)
+        check(self.ctx.lib.bpp_perm_prove_shuffle_batch(self.ctx.h, self.gens.h, self.k, count, _buf(cb), pm,
+                                                        _buf(gb) if gb is not None else None,
+                                                        _buf(seeds32) if seeds32 is not None else None,
+                                                        _buf(self.label), len(self.label), pf, V),
+              "bpp_perm_prove_shuffle_batch", self.ctx.h)
+        praw, vraw = pf.raw, V.raw
+        if raw:
+            return praw, vraw
+        return ([praw[i * self.proof_len:(i + 1) * self.proof_len] for i in range(count)],
+                [vraw[i * 32 * self.m:(i + 1) * 32 * self.m] for i in range(count)])
+
     def verify(self, proof: bytes, V) -> bool:
         vb = _join(V, 32, "V")
         rc = self.ctx.lib.bpp_perm_verify(self.ctx.h, self.gens.h, self.k, _buf(self.label), len(self.label),

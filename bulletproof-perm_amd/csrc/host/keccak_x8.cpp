@@ -211,8 +211,8 @@ void draw_prover_randomness_x8(const Circuit& C, const Seed seeds[8], RandomDraw
   vec(&RandomDraws::taus, 5);
 }
 
-void draw_prover_host_x8(const Circuit& C, const Seed seeds[8], RandomDraws* const out[8]) {
-  draw_pi_x8(C, seeds, out);
+void draw_prover_host_x8(const Circuit& C, const Seed seeds[8], RandomDraws* const out[8], bool with_pi) {
+  if (with_pi) draw_pi_x8(C, seeds, out);
   hsc::Sc* o[8];
   hsc::Sc RandomDraws::*abr[3] = {&RandomDraws::alpha, &RandomDraws::beta, &RandomDraws::rho};
   for (uint32_t i = 0; i < 3; ++i) {

@@ -34,6 +34,11 @@ Circuit build(uint32_t k);
 // v = [1..k, pi(1..k), x]; gate values (sound create_a)
 void witness(const Circuit& C, const std::vector<uint32_t>& pi, const hsc::Sc& x, std::vector<hsc::Sc>& v,
              std::vector<hsc::Sc>& aL, std::vector<hsc::Sc>& aR, std::vector<hsc::Sc>& aO);
+// The same over a caller's deck (bpp_perm_prove_shuffle_batch): v = [cards,
+// cards[pi], x], cards = k canonical scalars (the explicit v of the
+// reference's create_a, weights.rs:63-113)
+void witness(const Circuit& C, const hsc::Sc* cards, const std::vector<uint32_t>& pi, const hsc::Sc& x,
+             std::vector<hsc::Sc>& v, std::vector<hsc::Sc>& aL, std::vector<hsc::Sc>& aR, std::vector<hsc::Sc>& aO);
 
 // (z^Q)^T W as a dense vector of length ncols
 std::vector<hsc::Sc> zW(const std::vector<Entry>& W, const std::vector<hsc::Sc>& zq, uint32_t ncols);
@@ -114,7 +119,9 @@ void draw_prover_randomness_x8(const Circuit& C, const Seed seeds[8], RandomDraw
 // As above, but only the host's share -- pi, alpha, beta, rho and tau: the
 // GPU draws gamma, s_L and s_R (and alpha, beta, rho again, into its scalar
 // arrays; poly.h draws_dev), and out[j]'s vectors for them are left empty.
-void draw_prover_host_x8(const Circuit& C, const Seed seeds[8], RandomDraws* const out[8]);
+// with_pi = false (a caller-supplied shuffle): no pi stream is read and
+// out[j]->pi is left as it is.
+void draw_prover_host_x8(const Circuit& C, const Seed seeds[8], RandomDraws* const out[8], bool with_pi = true);
 
 size_t proof_len(uint32_t k);
 

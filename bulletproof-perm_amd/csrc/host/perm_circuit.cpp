@@ -67,15 +67,38 @@ Circuit build(uint32_t k) {
   return C;
 }
 
+// gate values from v = [chain A's k values, chain B's k values, x]
+static void witness_gates(const Circuit& C, const std::vector<Sc>& v, std::vector<Sc>& aL, std::vector<Sc>& aR,
+                          std::vector<Sc>& aO);
+
 void witness(const Circuit& C, const std::vector<uint32_t>& pi, const Sc& x, std::vector<Sc>& v, std::vector<Sc>& aL,
              std::vector<Sc>& aR, std::vector<Sc>& aO) {
-  const uint32_t k = C.k, n = C.n;
+  const uint32_t k = C.k;
   v.assign(C.m, hsc::zero());
   for (uint32_t i = 0; i < k; ++i) {
     v[i] = hsc::from_u64(i + 1);
     v[k + i] = hsc::from_u64(pi[i] + 1);
   }
   v[2 * k] = x;
+  witness_gates(C, v, aL, aR, aO);
+}
+
+void witness(const Circuit& C, const Sc* cards, const std::vector<uint32_t>& pi, const Sc& x, std::vector<Sc>& v,
+             std::vector<Sc>& aL, std::vector<Sc>& aR, std::vector<Sc>& aO) {
+  const uint32_t k = C.k;
+  v.assign(C.m, hsc::zero());
+  for (uint32_t i = 0; i < k; ++i) {
+    v[i] = cards[i];
+    v[k + i] = cards[pi[i]];
+  }
+  v[2 * k] = x;
+  witness_gates(C, v, aL, aR, aO);
+}
+
+static void witness_gates(const Circuit& C, const std::vector<Sc>& v, std::vector<Sc>& aL, std::vector<Sc>& aR,
+                          std::vector<Sc>& aO) {
+  const uint32_t k = C.k, n = C.n;
+  const Sc x = v[2 * k];
   aL.assign(C.n_p, hsc::zero());
   aR.assign(C.n_p, hsc::zero());
   aO.assign(C.n_p, hsc::zero());

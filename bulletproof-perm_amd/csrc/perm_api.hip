@@ -223,8 +223,17 @@ struct ProverState {
   merlin::Transcript tr;
   perm::RandomDraws d;  // pi, gamma, alpha, beta, rho, s_L, s_R, tau
   std::vector<Sc> vals, aL, aR, aO;
+  std::vector<Sc> cards;  // a caller-supplied deck, kept for the host witness (k > 768) only
   Sc x_perm, w;
   Sc t[7];
+};
+
+// A caller-supplied shuffle (bpp_perm_prove_shuffle_batch): this batch's
+// slices of the caller's arrays, validated by the entry point.
+struct ShuffleIn {
+  const uint8_t* cards;   // [P][k] canonical scalars
+  const uint32_t* perms;  // [P][k], each a bijection on [0, k)
+  const uint8_t* gammas;  // nullptr (drawn), or [P][2k] canonical scalars
 };
 
 std::vector<std::unique_ptr<ProverState>>& prover_states_tl() {
@@ -287,7 +296,7 @@ int prove_wipe(bpp_ctx* ctx) {
   for (auto& S : prover_states_tl()) {
     perm::RandomDraws& d = S->d;
     std::fill(d.pi.begin(), d.pi.end(), 0u);
-    for (auto* v : {&d.gamma, &d.sL, &d.sR, &d.taus, &S->vals, &S->aL, &S->aR, &S->aO})
+    for (auto* v : {&d.gamma, &d.sL, &d.sR, &d.taus, &S->vals, &S->aL, &S->aR, &S->aO, &S->cards})
       std::fill(v->begin(), v->end(), hsc::zero());
     d.alpha = d.beta = d.rho = hsc::zero();
     for (Sc& t : S->t) t = hsc::zero();
@@ -326,8 +335,12 @@ static int secret_residue(bpp_ctx* ctx, uint64_t* nz) {
 // round) is ONE launch sequence for the whole batch, and the per-proof host
 // work between them (transcripts, challenges, polynomial coefficients) runs
 // on a thread pool.  Outputs are identical to proving one at a time.
+// With sh, the witness is the caller's (cards, perms, optionally the V
+// blindings) instead of the seed's: no pi stream is read, the uploaded cards
+// and perms feed k_shuffle_inputs and k_witness_cards, and the V commitments
+// take full-width values; every other step is the same launch sequence.
 int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
-                const uint8_t* label, size_t llen, std::vector<Proof>& Ps) {
+                const uint8_t* label, size_t llen, std::vector<Proof>& Ps, const ShuffleIn* sh = nullptr) {
   const uint32_t k = C.k, n_p = C.n_p, m = C.m;
   const size_t P = seeds.size();
   Ps.resize(P);
@@ -374,8 +387,14 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
       }
     BPP_TRY(ctx_ws(ctx, "pb_gamma", (size_t)P * m * 32, &dg));
     BPP_TRY(ctx_ws(ctx, "mt_s", (size_t)P * per * 32 + 32, &dsc));
-    // templates then pi, one device buffer filled by one copy
-    BPP_TRY(ctx_ws(ctx, "pb_rng_in", P * tlen + (size_t)P * k * 4, &dst));
+    // templates then pi, one device buffer filled by one copy; a caller's
+    // shuffle appends its cards and V blindings (32-byte aligned: the kernels
+    // read them with 16-byte loads) to the same buffer and the same copy
+    const size_t rng_bytes = P * tlen + (size_t)P * k * 4;
+    const size_t sh_off = (rng_bytes + 31) & ~(size_t)31, cards_bytes = (size_t)P * k * 32;
+    const size_t gam_bytes = sh && sh->gammas ? (size_t)P * 2 * k * 32 : 0;
+    const size_t in_bytes = sh ? sh_off + cards_bytes + gam_bytes : rng_bytes;
+    BPP_TRY(ctx_ws(ctx, "pb_rng_in", in_bytes, &dst));
     dpi = (uint8_t*)dst + P * tlen;
     d_gamma = (uint32_t*)dg;
     d_s = (uint32_t*)dsc;
@@ -383,8 +402,9 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
     // (one staging region: a second take could recycle the arena under the first;
     // read in place instead, by k_draws through LDS, measured within noise)
     uint8_t* stage = nullptr;
-    BPP_TRY(ctx_h2d_stage(ctx, P * tlen + (size_t)P * k * 4, &stage));
-    ctx_secret_span(ctx, stage, P * tlen + (size_t)P * k * 4);  // (prove_wipe)
+    BPP_TRY(ctx_h2d_stage(ctx, in_bytes, &stage));
+    ctx_secret_span(ctx, stage, in_bytes);  // (prove_wipe)
+    if (sh) memset(stage + rng_bytes, 0, sh_off - rng_bytes);
     uint8_t* pis = stage + P * tlen;
     par::for_each((P + 7) / 8, [&](size_t gi) {
       perm::Seed sd[8];
@@ -395,9 +415,19 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
         sd[j] = seeds[std::min(8 * gi + j, P - 1)];
         d[j] = real ? &S[8 * gi + j]->d : &spare;
       }
-      perm::draw_prover_host_x8(C, sd, d);
+      perm::draw_prover_host_x8(C, sd, d, !sh);
       for (size_t j = 0; j < 8 && 8 * gi + j < P; ++j) {
         const size_t i = 8 * gi + j;
+        if (sh) {
+          S[i]->d.pi.assign(sh->perms + i * k, sh->perms + (i + 1) * k);
+          memcpy(stage + sh_off + i * 32 * (size_t)k, sh->cards + i * 32 * (size_t)k, 32 * (size_t)k);
+          if (sh->gammas)
+            memcpy(stage + sh_off + cards_bytes + i * 64 * (size_t)k, sh->gammas + i * 64 * (size_t)k, 64 * (size_t)k);
+          if (!dev_witness) {  // (canonical Sc == its 32 bytes)
+            S[i]->cards.resize(k);
+            memcpy(S[i]->cards.data(), sh->cards + i * 32 * (size_t)k, 32 * (size_t)k);
+          }
+        }
         S[i]->tr.arithmetic_domain_sep(n_p);
         uint64_t tm[7];
         draw_template(sd[j], tm);
@@ -410,15 +440,25 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
       }
 #endif
     });
-    BPP_TRY(ctx_h2d_staged(ctx, dst, stage, P * tlen + (size_t)P * k * 4));  // (pis follows the templates)
+    BPP_TRY(ctx_h2d_staged(ctx, dst, stage, in_bytes));  // (pis follows the templates)
     // (the V commitments' inputs in the same launch: values 1..k and pi + 1,
     // gamma copies and gamma_2k / 2, into the V phase's workspaces)
     void *dv = nullptr, *dgv = nullptr, *dgx = nullptr;
     BPP_TRY(ctx_ws(ctx, "pv_v", (size_t)P * 2 * k * 32, &dv));
     BPP_TRY(ctx_ws(ctx, "pv_g", (size_t)P * 2 * k * 32, &dgv));
     BPP_TRY(ctx_ws(ctx, "pv_gx", (size_t)P * 32, &dgx));
-    BPP_TRY(draws_dev(ctx, C, (uint32_t)P, (const uint64_t*)dst, P ? seeds[0].len : 0, per, d_gamma, d_s, d_pi,
-                      (uint32_t*)dv, (uint32_t*)dgv, (uint32_t*)dgx));
+    if (sh) {
+      // the draws alone, then the V inputs from the uploaded cards and perms
+      // (and the caller's blindings over the drawn gamma_0..2k-1)
+      const uint8_t* dsh = (const uint8_t*)dst + sh_off;
+      BPP_TRY(draws_dev(ctx, C, (uint32_t)P, (const uint64_t*)dst, seeds[0].len, per, d_gamma, d_s));
+      BPP_TRY(shuffle_inputs_dev(ctx, C, (uint32_t)P, (const uint32_t*)dsh, d_pi,
+                                 gam_bytes ? (const uint32_t*)(dsh + cards_bytes) : nullptr, d_gamma, (uint32_t*)dv,
+                                 (uint32_t*)dgv, (uint32_t*)dgx));
+    } else {
+      BPP_TRY(draws_dev(ctx, C, (uint32_t)P, (const uint64_t*)dst, P ? seeds[0].len : 0, per, d_gamma, d_s, d_pi,
+                        (uint32_t*)dv, (uint32_t*)dgv, (uint32_t*)dgx));
+    }
   }
   // V_0..V_2k-1 of every proof: one fixed-base launch over device inputs
   // (values 1..k, pi + 1 and gamma, written by k_draws), encodings back to the host
@@ -447,9 +487,11 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
       HostScope hk(ctx, "ped_kernels");
       void* dvenc = nullptr;
       if (dev_v) BPP_TRY(ctx_ws(ctx, "pv_enc_d", nv * 32, &dvenc));
-      // (values 1..k and pi + 1 <= k: the public bound k + 1)
+      // (values 1..k and pi + 1 <= k: the public bound k + 1; a caller's
+      // cards are secret full-width scalars: no bound, every digit position
+      // walked whatever the value, as for gamma)
       BPP_TRY(pedersen_dev(ctx, G, (const uint32_t*)dv, (const uint32_t*)dg, nv,
-                           dev_v ? (uint32_t*)dvenc : (uint32_t*)denc, nullptr, (uint64_t)k + 1));
+                           dev_v ? (uint32_t*)dvenc : (uint32_t*)denc, nullptr, sh ? 0 : (uint64_t)k + 1));
       if (dev_v) {
         BPP_HIP(hipMemcpyAsync(denc, dvenc, nv * 32, hipMemcpyDeviceToHost, ctx->stream));
         uint32_t init[52], *h_init = nullptr;
@@ -509,7 +551,11 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
     }
     uint32_t* d_vh = nullptr;
     BPP_TRY(upload_sc(ctx, vh, "pv_vx", &d_vh));
-    if (dev_witness) BPP_TRY(witness_dev(ctx, C, (uint32_t)P, d_pi, d_vh + 8 * P, per, d_s));
+    if (dev_witness) {
+      void* dvals = nullptr;  // (a caller's shuffle: both chains' values, as committed)
+      if (sh) BPP_TRY(ctx_ws(ctx, "pv_v", (size_t)P * 2 * k * 32, &dvals));
+      BPP_TRY(witness_dev(ctx, C, (uint32_t)P, d_pi, d_vh + 8 * P, per, d_s, (const uint32_t*)dvals));
+    }
     uint32_t* h_p3 = nullptr;  // written in place by the kernel (ctx_zc_out)
     BPP_TRY(ctx_zc_out(ctx, "pv_p3_h", P * P3_BYTES, &h_p3));
     BPP_TRY(pedersen_dev(ctx, G, d_vh, d_gx_half, P, nullptr, h_p3));
@@ -519,7 +565,13 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
     par::for_each(P, [&](size_t p) {
       Ps[p].V.push_back(Vx[p]);
       S[p]->tr.append_point("V", Vx[p].data());
-      if (!dev_witness) perm::witness(C, S[p]->d.pi, S[p]->x_perm, S[p]->vals, S[p]->aL, S[p]->aR, S[p]->aO);
+      if (!dev_witness) {
+        ProverState& st = *S[p];
+        if (sh)
+          perm::witness(C, st.cards.data(), st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
+        else
+          perm::witness(C, st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
+      }
     });
   }
   MsmPoints pts;
@@ -1607,7 +1659,7 @@ std::vector<Proof>& proofs_tl() {
 // context inside its sub-batch thread (whose prover states are its own)
 static int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, const std::vector<perm::Seed>& seeds,
                            const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out,
-                           bool wipe = false) {
+                           bool wipe = false, const ShuffleIn* sh = nullptr) {
   const size_t count = seeds.size();
   if (!count) return BPP_OK;
   const perm::Circuit C = perm::build(k);
@@ -1631,7 +1683,7 @@ static int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, const st
     BPP_TRY(gens_points(ctx, G, &warm));
   }
   if (S <= 1) {
-    BPP_TRY(prove_batch(ctx, G, C, seeds, label, llen, Ps));
+    BPP_TRY(prove_batch(ctx, G, C, seeds, label, llen, Ps, sh));
   } else {
     std::vector<bpp_ctx*> kids(S);
     for (size_t s = 0; s < S; ++s) BPP_TRY(ctx_child(ctx, s, &kids[s]));
@@ -1648,7 +1700,11 @@ static int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, const st
         }
         std::vector<Proof> sub;
         std::vector<perm::Seed> part(seeds.begin() + b, seeds.begin() + e);
-        rcs[s] = prove_batch(kc, G, C, part, label, llen, sub);
+        ShuffleIn shs;  // this sub-batch's slices of the caller's witness
+        if (sh)
+          shs = {sh->cards + b * 32 * (size_t)k, sh->perms + b * (size_t)k,
+                 sh->gammas ? sh->gammas + b * 64 * (size_t)k : nullptr};
+        rcs[s] = prove_batch(kc, G, C, part, label, llen, sub, sh ? &shs : nullptr);
         if (rcs[s] == BPP_OK)
           for (size_t i = b; i < e; ++i) Ps[i] = std::move(sub[i - b]);
         if (wipe) {
@@ -1708,6 +1764,70 @@ int bpp_perm_prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, si
     std::vector<perm::Seed> sd(count);
     for (size_t i = 0; i < count; ++i) sd[i] = perm::Seed::bytes32(seeds32 + 32 * i);
     int rc = prove_batch_api(ctx, G, k, sd, label, llen, proofs_out, V_out, true);
+    if (!ent.empty()) memset(ent.data(), 0, ent.size());
+    for (perm::Seed& x : sd) memset(x.b, 0, sizeof x.b);
+    const int wrc = prove_wipe(ctx);
+    return rc ? rc : wrc;
+  });
+}
+
+int bpp_perm_prove_shuffle_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* cards,
+                                 const uint32_t* perms, const uint8_t* gammas, const uint8_t* seeds32,
+                                 const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out) {
+  return bpp_guard(ctx, [&]() -> int {
+    if (((!cards || !perms || !proofs_out || !V_out) && count) || (!label && llen) || k < 2 || k > (1u << 20))
+      return BPP_ERR_ARG;
+    // the whole witness is checked before any device work and before any
+    // output byte is written (it needs neither the context nor the
+    // generators, whose null checks follow): every perm a bijection on
+    // [0, k), every card and supplied blinding a canonical scalar
+    std::vector<int> bad(count, BPP_OK);
+    par::for_each(count, [&](size_t p) {
+      std::vector<uint8_t> seen(k, 0);
+      const uint32_t* pm = perms + p * (size_t)k;
+      for (uint32_t i = 0; i < k; ++i) {
+        if (pm[i] >= k || seen[pm[i]]) {
+          bad[p] = BPP_ERR_ARG;
+          return;
+        }
+        seen[pm[i]] = 1;
+      }
+      Sc t;
+      for (uint32_t i = 0; i < k; ++i)
+        if (!hsc::from_canonical(t, cards + (p * (size_t)k + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
+      if (gammas)
+        for (uint32_t i = 0; i < 2 * k; ++i)
+          if (!hsc::from_canonical(t, gammas + (p * 2 * (size_t)k + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
+      t = hsc::zero();
+    });
+    for (size_t p = 0; p < count; ++p)
+      if (bad[p] != BPP_OK) {
+        if (ctx)
+          ctx->err = bad[p] == BPP_ERR_ARG ? "shuffle " + std::to_string(p) + ": perm is not a bijection on [0, k)"
+                                           : "shuffle " + std::to_string(p) + ": non-canonical card or blinding";
+        return bad[p];
+      }
+    if (!ctx || !G) return BPP_ERR_ARG;
+    if (!count) return BPP_OK;
+    std::vector<uint8_t> ent;
+    if (!seeds32) {  // the OS CSPRNG, as bpp_perm_prove_batch_entropy
+      ent.resize(32 * count);
+      size_t got = 0;
+      while (got < ent.size()) {
+        const ssize_t r = getrandom(ent.data() + got, ent.size() - got, 0);
+        if (r < 0) {
+          if (errno == EINTR) continue;
+          ctx->err = "getrandom failed";
+          return BPP_ERR_DEVICE;
+        }
+        got += (size_t)r;
+      }
+      seeds32 = ent.data();
+    }
+    std::vector<perm::Seed> sd(count);
+    for (size_t i = 0; i < count; ++i) sd[i] = perm::Seed::bytes32(seeds32 + 32 * i);
+    const ShuffleIn sh = {cards, perms, gammas};
+    int rc = prove_batch_api(ctx, G, k, sd, label, llen, proofs_out, V_out, true, &sh);
     if (!ent.empty()) memset(ent.data(), 0, ent.size());
     for (perm::Seed& x : sd) memset(x.b, 0, sizeof x.b);
     const int wrc = prove_wipe(ctx);

@@ -43,7 +43,18 @@ int draws_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint64_t* 
 void draw_template(const perm::Seed& seed, uint64_t tmpl[7]);
 
 
+// The V commitment inputs of a caller-supplied shuffle (k_shuffle_inputs),
+// after draws_dev without d_v on the same stream: d_v [P][2k] = cards then
+// cards[perm] (d_cards [P][k] canonical scalars, d_perm [P][k] u32 < k), d_g
+// [P][2k] = the drawn gamma_0..2k-1 or, when d_gammas ([P][2k]) is non-null,
+// the caller's, which then replace d_gamma's too; d_gx_half [P] = gamma_2k / 2.
+int shuffle_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_cards,
+                       const uint32_t* d_perm, const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v,
+                       uint32_t* d_g, uint32_t* d_gx_half);
+
 // The witness a_L, a_R, a_O of every proof (x = x_perm [P] canonical, pi
-// [P][k]) into their slots of d_sc.
+// [P][k]) into their slots of d_sc.  With d_vals ([P][2k] canonical, d_v
+// above) both chains take their values from it instead of 1..k and pi + 1
+// (k_witness_cards; d_pi is not read).
 int witness_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_pi, const uint32_t* d_x,
-                uint32_t per, uint32_t* d_sc);
+                uint32_t per, uint32_t* d_sc, const uint32_t* d_vals = nullptr);

@@ -679,9 +679,15 @@ __global__ void __launch_bounds__(256) k_draws(uint32_t P, uint32_t m, uint32_t 
 // padding gates are zero.  a_L, a_R, a_O go straight into the A_I/A_O/S
 // scalar array.  Prefix products: per-lane chunks, then a Hillis-Steele scan
 // of the chunk products in LDS.  dynamic LDS = (2 k + 4 blockDim) x 32 B.
-__global__ void __launch_bounds__(256) k_witness(uint32_t k, uint32_t n_p, uint32_t per, const uint32_t* __restrict__ pi,
-                                                const uint32_t* __restrict__ xs, uint32_t* __restrict__ sc_out) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+//
+// CARDS (bpp_perm_prove_shuffle_batch): both chains' values are the caller's
+// cards, read from vals ([P][2k] canonical, the V commitments' inputs that
+// k_shuffle_inputs wrote: cards then cards[perm]) instead of synthesised from
+// pi; the values stay in global memory, the LDS budget is the same.
+template <bool CARDS>
+FE_INLINE void witness_body(uint32_t* lds, uint32_t k, uint32_t n_p, uint32_t per, const uint32_t* __restrict__ pi,
+                            const uint32_t* __restrict__ vals, const uint32_t* __restrict__ xs,
+                            uint32_t* __restrict__ sc_out) {
   uint32_t* pref = lds;           // [2][k] prefix products (A then B): Montgomery, then canonical
   uint32_t* scan = lds + 16 * k;  // [2 buffers][2][blockDim] chunk products
   const uint32_t p = blockIdx.x, nt = blockDim.x, t = threadIdx.x;
@@ -691,9 +697,12 @@ __global__ void __launch_bounds__(256) k_witness(uint32_t k, uint32_t n_p, uint3
   const sc oneR = sc_to_mont(one);
   // lane t owns elements [i0, i1) of both chains; nch lanes own any
   const uint32_t C = (k + nt - 1) / nt, nch = (k + C - 1) / C, i0 = t * C, i1 = min(i0 + C, k);
-  auto dd = [&](uint32_t c, uint32_t i) {  // v_i - x: v = i + 1 (A) or pi(i) + 1 (B)
+  auto dd = [&](uint32_t c, uint32_t i) {  // v_i - x: v = i + 1 (A) or pi(i) + 1 (B); or the cards
     sc v = sc_zero();
-    v.v[0] = c == 0 ? i + 1 : pi[(size_t)p * k + i] + 1;
+    if constexpr (CARDS)
+      v = sc_load(vals + 8 * ((size_t)p * 2 * k + c * k + i));
+    else
+      v.v[0] = c == 0 ? i + 1 : pi[(size_t)p * k + i] + 1;
     return sc_sub(v, x);
   };
   sc run[2] = {oneR, oneR};
@@ -754,13 +763,75 @@ __global__ void __launch_bounds__(256) k_witness(uint32_t k, uint32_t n_p, uint3
   }
 }
 
+__global__ void __launch_bounds__(256) k_witness(uint32_t k, uint32_t n_p, uint32_t per, const uint32_t* __restrict__ pi,
+                                                const uint32_t* __restrict__ xs, uint32_t* __restrict__ sc_out) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  witness_body<false>(lds, k, n_p, per, pi, nullptr, xs, sc_out);
+}
+
+__global__ void __launch_bounds__(256) k_witness_cards(uint32_t k, uint32_t n_p, uint32_t per,
+                                                      const uint32_t* __restrict__ vals,
+                                                      const uint32_t* __restrict__ xs, uint32_t* __restrict__ sc_out) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  witness_body<true>(lds, k, n_p, per, nullptr, vals, xs, sc_out);
+}
+
+// The V phase's inputs of a caller-supplied shuffle, one lane per commitment
+// input (P x m lanes, after k_draws with v = nullptr on the same stream):
+// v[p][i] = cards[p][i], v[p][k + i] = cards[p][perm[p][i]] (i < k; perm is a
+// bijection on [0, k), checked by the entry point before any device work --
+// the index is clamped all the same), g[p][j] = the blinding of V_j: the
+// drawn gamma[p][j], or the caller's gammas[p][j], which then also replaces
+// gamma[p][j] (k_poly_coef reads it for tau_x); gx_half[p] = gamma_2k / 2
+// (always drawn).  cards [P][k], gammas [P][2k], gamma [P][m]: canonical.
+__global__ void __launch_bounds__(256) k_shuffle_inputs(uint32_t P, uint32_t k, uint32_t m,
+                                                       const uint32_t* __restrict__ cards,
+                                                       const uint32_t* __restrict__ perm,
+                                                       const uint32_t* __restrict__ gammas,
+                                                       uint32_t* __restrict__ gamma, uint32_t* __restrict__ v,
+                                                       uint32_t* __restrict__ g, uint32_t* __restrict__ gx_half) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)P * m) return;
+  const uint32_t p = (uint32_t)(t / m), j = (uint32_t)(t % m);
+  uint32_t* gm = gamma + 8 * ((size_t)p * m + j);
+  if (j == 2 * k) {
+    sc_store(gx_half + 8 * (size_t)p, sc_half(sc_load(gm)));
+    return;
+  }
+  const uint32_t src = j < k ? j : min(perm[(size_t)p * k + (j - k)], k - 1);
+  const size_t o = 8 * ((size_t)p * 2 * k + j);
+  sc_store(v + o, sc_load(cards + 8 * ((size_t)p * k + src)));
+  sc x;
+  if (gammas) {
+    x = sc_load(gammas + o);
+    sc_store(gm, x);
+  } else {
+    x = sc_load(gm);
+  }
+  sc_store(g + o, x);
+}
+
+int shuffle_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_cards,
+                       const uint32_t* d_perm, const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v,
+                       uint32_t* d_g, uint32_t* d_gx_half) {
+  if (!P) return BPP_OK;
+  const size_t nt = (size_t)P * C.m;
+  hipLaunchKernelGGL(k_shuffle_inputs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, P, C.k, C.m,
+                     d_cards, d_perm, d_gammas, d_gamma, d_v, d_g, d_gx_half);
+  return ctx_check_launch(ctx, "k_shuffle_inputs");
+}
+
 int witness_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_pi, const uint32_t* d_x,
-                uint32_t per, uint32_t* d_sc) {
+                uint32_t per, uint32_t* d_sc, const uint32_t* d_vals) {
   if (!P) return BPP_OK;
   // (256 lanes while the prefixes and both scan buffers fit 64 KB, else 128:
   // perm_api's dev_witness bound (2 k + 512) x 32 B)
   const unsigned nt = (2 * (size_t)C.k + 4 * 256) * 32 <= 64 * 1024 ? 256 : 128;
   const size_t lds = (2 * (size_t)C.k + 4 * nt) * 32;
+  if (d_vals) {
+    hipLaunchKernelGGL(k_witness_cards, dim3(P), dim3(nt), lds, ctx->stream, C.k, C.n_p, per, d_vals, d_x, d_sc);
+    return ctx_check_launch(ctx, "k_witness_cards");
+  }
   hipLaunchKernelGGL(k_witness, dim3(P), dim3(nt), lds, ctx->stream, C.k, C.n_p, per, d_pi, d_x, d_sc);
   return ctx_check_launch(ctx, "k_witness");
 }

@@ -324,6 +324,38 @@ int bpp_perm_prove_batch(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t cou
  * the caller's to wipe). */
 int bpp_perm_prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* seeds32,
                                  const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out);
+/* Proves a CALLER-SUPPLIED shuffle: the caller's deck, permutation and
+ * (optionally) the blindings of commitments it has already published -- the
+ * direction of the reference, whose deck is an explicit vector handed to
+ * commit_variables and create_a (weights.rs:58-113).  Per proof p:
+ *   cards   count x k x 32 B: the deck, canonical scalars (proof-major);
+ *   perms   count x k u32: output slot i holds cards[perm[i]];
+ *   gammas  NULL, or count x 2k x 32 B: the blindings of V_0..V_2k-1.
+ * V_0..V_{k-1} commit to cards[i], V_k..V_{2k-1} to cards[perm[i]] and V_2k
+ * to the transcript challenge x_perm, as above.  The circuit proves
+ * prod (v_i - x) = prod (v'_i - x), i.e. that the two halves are equal as
+ * MULTISETS: cards may be any canonical scalars, 0 and l - 1 and repeated
+ * values included, and with repeated values the proof says nothing about
+ * which of the equal cards went where.
+ * Proof format, transcript order, bpp_perm_proof_len and the V_out layout are
+ * those of the other provers; the proofs verify with bpp_perm_verify /
+ * bpp_perm_verify_batch unchanged.
+ * Randomness: seeds32 as bpp_perm_prove_batch_entropy (count x 32 B, or NULL
+ * for the OS CSPRNG); blinding scalar j is the same indexed draw in the same
+ * order; supplied gammas replace draws 0..2k-1, while gamma_2k, alpha, beta,
+ * rho, s_L, s_R and tau stay drawn; no pi stream is read.  With cards = 1..k,
+ * perms = the permutation bpp_perm_prove_batch_entropy derives from the same
+ * seeds and gammas = NULL, proofs and V equal that call's bytes.
+ * Checked before any device work and before any output byte is written:
+ * a perm that is not a bijection on [0, k) -> BPP_ERR_ARG; a card or gamma
+ * >= l -> BPP_ERR_NONCANONICAL (the witness is checked first: it needs
+ * neither ctx nor g); then the k / g / null checks of the other provers.
+ * Secret lifetime: always that of bpp_perm_prove_batch_entropy; the staged
+ * and uploaded cards, perms and gammas are part of what is zeroed (the
+ * caller's own arrays are the caller's to wipe). */
+int bpp_perm_prove_shuffle_batch(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* cards,
+                                 const uint32_t* perms, const uint8_t* gammas, const uint8_t* seeds32,
+                                 const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out);
 /* Test hook for the secret lifetime above: the number of nonzero bytes left
  * in what the last bpp_perm_prove_batch_entropy zeroed on ctx and its child
  * contexts (device workspaces, pinned buffers and staging spans, including
