@@ -86,18 +86,14 @@ struct bpp_ctx {
   // job is valid while its generation is the context's latest
   uint64_t vjob_gen = 0;
   // the device job's proof-point decompression runs on child context
-  // VJ_CHILD beside the replay: vj_ev_in (inputs uploaded, ctx stream) ->
-  // decompress -> vj_ev_dec (child stream), waited for before the MSM and
-  // before the next upload overwrites the inputs
-  hipEvent_t vj_ev_in = nullptr, vj_ev_dec = nullptr;
+  // VJ_CHILD beside the replay: vj_ev_chunk (a chunk's inputs uploaded, ctx
+  // stream) -> decompress -> vj_ev_dec (child stream), waited for before the
+  // MSM and before the next upload overwrites the inputs
+  hipEvent_t vj_ev_dec = nullptr;
   bool vj_dec_pending = false;
   // one event per upload chunk (verify_begin_dev: each chunk's points are
   // decompressed as soon as its copy lands)
   std::vector<hipEvent_t> vj_ev_chunk;
-  // the split replay (BPP_VERIFY_SPLIT): the proof-byte chunks' events, and
-  // the end of the V-part replays on their child stream
-  std::vector<hipEvent_t> vj_ev_chunk2;
-  hipEvent_t vj_ev_vrep = nullptr;
   // bpp_msm_submit_host: the uploaded scalars of this (child) context's MSM,
   // copied on the parent's upload streams (up_stream, created on first use;
   // one per chunk of the copy) and signalled to this context's stream by
@@ -188,8 +184,6 @@ void ctx_stage_copy(void* dst, const void* src, size_t bytes);
 void host_pinned_add(const void* p, size_t n);
 void host_pinned_remove(const void* p);
 bool host_is_pinned(const void* p, size_t n);
-// Two host buffers copied back to back into d (one staging copy).
-int ctx_h2d2(bpp_ctx* ctx, void* d, const void* h0, size_t n0, const void* h1, size_t n1);
 // Two-step form for data produced straight into the pinned arena:
 // ctx_h2d_stage hands out `bytes` of staging (valid until the next
 // ctx_sync), ctx_h2d_staged enqueues its copy to d.

@@ -23,8 +23,8 @@
 // Pinned host buffers handed out by bpp_host_alloc (start -> bytes), so that
 // an entry point can tell them from pageable memory without a runtime
 // query; other pointers are then looked up with hipPointerGetAttributes
-// (memory a caller pinned itself with hipHostRegister; BPP_PIN_QUERY=0
-// skips it -- config 5 single batches measured the same either way, r05)
+// (memory a caller pinned itself with hipHostRegister; config 5 single
+// batches measured the same with and without the lookup, r05)
 static std::mutex g_pin_mu;
 static std::map<uintptr_t, size_t> g_pinned;
 void host_pinned_add(const void* p, size_t n) {
@@ -44,13 +44,9 @@ bool host_is_pinned(const void* p, size_t n) {
       if ((uintptr_t)p >= it->first && (uintptr_t)p + n <= it->first + it->second) return true;
     }
   }
-  static const bool query = [] {  // (BPP_PIN_QUERY=0: the registry alone; measured the same, r05)
-    const char* e = getenv("BPP_PIN_QUERY");
-    return !e || atoi(e) != 0;
-  }();
-  if (!query) return false;
-  // both ends of [p, p + n) must be page-locked (a buffer the caller
-  // registered only in part is staged as pageable)
+  // not in the registry: ask the runtime (the registry alone measured the
+  // same, r05).  Both ends of [p, p + n) must be page-locked (a buffer the
+  // caller registered only in part is staged as pageable)
   auto pinned_at = [](const void* q) {
     hipPointerAttribute_t at;
     const bool pin = hipPointerGetAttributes(&at, q) == hipSuccess && at.type == hipMemoryTypeHost;
@@ -63,7 +59,7 @@ bool host_is_pinned(const void* p, size_t n) {
 // Non-temporal copy into the pinned arena: the arena is only read back by
 // the copy engine, so streaming stores skip the read-for-ownership of every
 // destination line (a plain memcpy moves each byte three times over the
-// memory bus, this one twice).  BPP_STAGE_NT=0 falls back to memcpy (A/B).
+// memory bus, this one twice).
 static void copy_nt(uint8_t* d, const uint8_t* s, size_t n) {
   while (n && ((uintptr_t)d & 31)) {
     *d++ = *s++;
@@ -85,12 +81,8 @@ static void copy_nt(uint8_t* d, const uint8_t* s, size_t n) {
 }
 
 void ctx_stage_copy(void* dst, const void* src, size_t bytes) {
-  static const bool nt = [] {
-    const char* e = getenv("BPP_STAGE_NT");
-    return !e || atoi(e) != 0;
-  }();
   auto cp = [&](uint8_t* d, const uint8_t* s, size_t n) {
-    if (nt && n >= 4096)
+    if (n >= 4096)
       copy_nt(d, s, n);
     else
       memcpy(d, s, n);
@@ -194,11 +186,6 @@ int ctx_sync(bpp_ctx* ctx) {
 }
 
 int ctx_sync_latency(bpp_ctx* ctx, unsigned spin_us) {
-  static const int spin_env = [] {  // (BPP_SYNC_SPIN_US overrides, for A/B; 0 = ctx_sync)
-    const char* e = getenv("BPP_SYNC_SPIN_US");
-    return e ? atoi(e) : -1;
-  }();
-  if (spin_env >= 0) spin_us = (unsigned)spin_env;
   if (!ctx->sync_ev) BPP_HIP(hipEventCreateWithFlags(&ctx->sync_ev, hipEventDisableTiming));
   BPP_HIP(hipEventRecord(ctx->sync_ev, ctx->stream));
   const auto t0 = std::chrono::steady_clock::now();
@@ -322,27 +309,6 @@ int ctx_h2d(bpp_ctx* ctx, void* d, const void* h, size_t bytes) {
   BPP_TRY(stage_take(ctx, bytes, &p));
   ctx_stage_copy(p, h, bytes);
   BPP_HIP(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return BPP_OK;
-}
-
-// In pieces of 2 MB: the DMA of piece i runs while the host stages piece
-// i + 1 (a batch verification's 17 MB of proofs and V: the copy engine's
-// ~0.35 ms then hides under the staging instead of following it).
-int ctx_h2d2(bpp_ctx* ctx, void* d, const void* h0, size_t n0, const void* h1, size_t n1) {
-  if (!n0 && !n1) return BPP_OK;
-  uint8_t* p = nullptr;
-  const size_t total = n0 + n1, piece = (size_t)2 << 20;
-  BPP_TRY(stage_take(ctx, total, &p));
-  for (size_t off = 0; off < total;) {
-    const size_t e = std::min(total, off + piece);
-    if (off < n0) ctx_stage_copy(p + off, (const uint8_t*)h0 + off, std::min(e, n0) - off);
-    if (e > n0) {
-      const size_t s = std::max(off, n0);
-      ctx_stage_copy(p + s, (const uint8_t*)h1 + (s - n0), e - s);
-    }
-    BPP_HIP(hipMemcpyAsync((uint8_t*)d + off, p + off, e - off, hipMemcpyHostToDevice, ctx->stream));
-    off = e;
-  }
   return BPP_OK;
 }
 
@@ -549,11 +515,8 @@ void bpp_ctx_destroy(bpp_ctx* ctx) {
       hipStreamSynchronize(s);
       hipStreamDestroy(s);
     }
-  if (ctx->vj_ev_in) hipEventDestroy(ctx->vj_ev_in);
   if (ctx->vj_ev_dec) hipEventDestroy(ctx->vj_ev_dec);
   for (auto e : ctx->vj_ev_chunk) hipEventDestroy(e);
-  for (auto e : ctx->vj_ev_chunk2) hipEventDestroy(e);
-  if (ctx->vj_ev_vrep) hipEventDestroy(ctx->vj_ev_vrep);
   for (auto& sl : ctx->msm_slot)
     if (sl.done) hipEventDestroy(sl.done);
   hipStreamDestroy(ctx->stream);

@@ -26,8 +26,8 @@ struct DtGeom {
 // Term groups per block (TG, lanes = TG * W) for a launch of `nmsm` MSMs:
 // at most DT_TG_DEFAULT (8: 128 lanes at c = 16) when the launch has blocks
 // enough to fill the device (>= 256 MSMs; a few long MSMs keep 16 groups for
-// latency), fewer for short MSMs; BPP_DT_TG_MAX overrides the cap (an A/B
-// switch).  Fewer lanes per MSM mean a shallower block tree and
+// latency), fewer for short MSMs.  Fewer lanes per MSM mean a shallower
+// block tree and
 // less issue per MSM but a longer walk per lane.  256-proof batches, 52-card
 // proofs (tools/prove_inflight_exp.py): at 12 in flight with the host the
 // bottleneck, 16 / 8 / 4 / 2 groups measured 263-265 / 265 / 244 / 168-171 K
@@ -38,10 +38,6 @@ struct DtGeom {
 static inline uint32_t dt_term_groups(uint32_t W, double terms_per_msm, uint32_t nmsm) {
   uint32_t TG = DT_NT_MAX / W;
   if (nmsm >= 256 && TG > DT_TG_DEFAULT) TG = DT_TG_DEFAULT;
-  if (const char* e = getenv("BPP_DT_TG_MAX")) {
-    const int v = atoi(e);
-    if (v >= 1 && (uint32_t)v <= DT_NT_MAX / W) TG = (uint32_t)v;
-  }
   while (TG > 1 && terms_per_msm < 2.0 * TG) TG >>= 1;
   return TG;
 }
@@ -235,7 +231,7 @@ FE_INLINE void lds_store_coord(uint32_t* tl, uint32_t nslots, uint32_t j, uint32
 // lane per addition while 4 segs s exceeds the block, then four lanes per
 // addition (ge_add_quad): a narrow level's latency is one wave's instruction
 // stream, which the quads cut by ~3x (the 8-level tree was ~29 us of each
-// 80-us IPA round at 256 lanes, measured with EXP_IPA_NOTREE).  Segments
+// 80-us IPA round at 256 lanes, measured with the tree compiled out).  Segments
 // side by side share the narrow levels' waves (the two-sided IPA round).
 FE_INLINE void dt_block_tree_segs(uint32_t* tl, const ge_p3& acc, uint32_t nt, uint32_t segs,
                                   uint32_t* __restrict__ out_p3, uint32_t m0, uint32_t mstride,

@@ -145,14 +145,6 @@ FE_INLINE ge_p3 ge_madd_h2(const ge_madd_mid& m) {
   return r;
 }
 
-FE_INLINE ge_niels ge_niels_neg(const ge_niels& q) {
-  ge_niels r;
-  r.ypx = q.ymx;
-  r.ymx = q.ypx;
-  r.xy2d = fe_neg(q.xy2d);
-  return r;
-}
-
 // YpX / YmX only ever feed multipliers: left uncarried.
 FE_INLINE ge_cached ge_to_cached(const ge_p3& p) {
   ge_cached c;

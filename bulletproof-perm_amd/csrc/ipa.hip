@@ -16,12 +16,6 @@
 // challenge on the host, and the scalar fold (k_ipa_fold).  L, R, a, b are
 // identical group elements / scalars to the folding form (same transcript).
 #include <cstdlib>
-#include <chrono>
-#include <thread>
-#include <condition_variable>
-#include <mutex>
-#include <memory>
-#include <map>
 #include <functional>
 #include <cstring>
 
@@ -189,17 +183,6 @@ __global__ void __launch_bounds__(256) k_ipa_fold(uint32_t n, uint32_t lg_n, uin
   }
 }
 
-// The J partials of a split round's L / R (block b = MSM b, lane j = partial
-// b J + j, J a power of two <= 64) summed by dt_block_tree_segs' tree and
-// written to out[b] (pinned host memory) -- the host then encodes 2P points
-// instead of adding 2P (J - 1) first.
-__global__ void __launch_bounds__(64) k_ipa_jsum(const uint32_t* __restrict__ part, uint32_t J,
-                                                uint32_t* __restrict__ out) {
-  extern __shared__ uint32_t lds[];
-  const ge_p3 p = load_p3(part, (size_t)blockIdx.x * J + threadIdx.x);
-  dt_block_tree_segs(lds, p, J, 1, out, blockIdx.x, 0);
-}
-
 // The last fold of the fused path, for element 0 only (the proof's a, b):
 // out[p] = (a_0 u + a_1 u^-1, b_0 u^-1 + b_1 u), Montgomery words, written
 // in place into pinned host memory -- one launch where k_ipa_fold over all n
@@ -233,8 +216,7 @@ __global__ void __launch_bounds__(64) k_ipa_final(uint32_t P, uint32_t n, const 
 // and their passes over the [P][n] arrays leave every round of a batch.
 // (512-lane blocks, half the walk per lane: 73.9 vs 70.8 us per round -- a
 // lone wave per SIMD already issues the walk at its rate)
-// One batch's round as the fused kernel sees it (k_ipa_round_dt's
-// arguments; k_ipa_round_dt_multi runs several batches' rounds in one launch).
+// One batch's round as the fused kernel sees it (k_ipa_round_dt's arguments).
 struct IpaRoundArgs {
   const uint32_t *am_in, *bm_in, *fG_in, *fH_in;
   uint32_t *am_out, *bm_out, *fG_out, *fH_out;
@@ -242,7 +224,6 @@ struct IpaRoundArgs {
   uint32_t* out_p3;
   const uint32_t *a0, *b0, *gf0, *hf0;
   uint32_t m, lg_h, fold, init, halve, gbase, hbase, qidx;
-  uint32_t blocks;  // 2 P J (k_ipa_round_dt_multi)
   uint32_t split;   // J: blocks per L / R MSM, each walking a slice of its n + 1 terms
   const uint32_t* qpow;  // IpaGens::qpow (null: Q's term walked from its table rows)
   uint32_t qrow0;        // qpow's first row as a row of dt (the virtual terms' rows)
@@ -333,15 +314,13 @@ FE_INLINE void ipa_round_body(const uint32_t* __restrict__ dt, const DtGeom& dg,
     um = A.u1 ? A.u1m : sc_load(u + 16 * inst);
     uim = A.u1 ? A.u1im : sc_load(u + 16 * inst + 8);
   }
-#ifndef IPA_SPLIT_PROLOGUE
-#define IPA_SPLIT_PROLOGUE 1
-#endif
-  if (IPA_SPLIT_PROLOGUE && J > 1) {
+  if (J > 1) {
     // A split round (J blocks per MSM: small batches, config 2): each block
     // computes only what its slice needs -- the term scalars of its n / J
     // slots per side, its J-th of the next state's writes and of the cross
     // product -- instead of every block folding the whole state and forming
-    // all 2n term scalars (28 of a config-2 round's 64 us, EXP_IPA_NOWALK).
+    // all 2n term scalars (28 of a config-2 round's 64 us, measured with the
+    // walk compiled out).
     // The Q term rides in every block with that block's share of
     // c = <a_lo, b_hi> (resp. <a_hi, b_lo>): the host adds the J partials,
     // and sum_jp c^(jp) Q = c Q.
@@ -420,10 +399,6 @@ FE_INLINE void ipa_round_body(const uint32_t* __restrict__ dt, const DtGeom& dg,
     const DtLane ln = DtLane::make(dg, lt % dg.W);
     const uint32_t* __restrict__ tscs = tsl + 8 * ls * CS;
     const uint32_t* __restrict__ tgens = tgl + ls * CS;
-#ifdef EXP_IPA_NOWALK  // timing experiment only (wrong results): no walk, no tree
-    if (tid < S) store_p3(out_p3, (S == 2 ? 2 * inst * J + jp : bidx) + tid * J, ge_identity());
-    return;
-#endif
     // (QP: every slice walks its own share of c Q as the V virtual terms)
     const ge_p3 acc = tg < TG ? dt_walk<QP>(dt, dg, ln, tg, CS, TG,
                                             [&](uint32_t t, uint32_t sv[8], uint32_t& gen) {
@@ -434,10 +409,6 @@ FE_INLINE void ipa_round_body(const uint32_t* __restrict__ dt, const DtGeom& dg,
                                             ge_identity(), A.qrow0)
                               : ge_identity();
     __syncthreads();
-#ifdef EXP_IPA_NOTREE  // timing experiment only (wrong results): no block tree
-    if (lt == 0) store_p3(out_p3, (S == 2 ? 2 * inst * J + jp : bidx) + ls * J, acc);
-    return;
-#endif
     dt_block_tree_segs(lds, acc, nt, S, out_p3, S == 2 ? 2 * inst * J + jp : bidx, J);
     if (A.done_word) done_signal(A.done_ticket, A.done_word, A.done_tag);
     // (i) this block's share of the next state (the side-0 blocks of S = 1),
@@ -544,10 +515,6 @@ FE_INLINE void ipa_round_body(const uint32_t* __restrict__ dt, const DtGeom& dg,
   const DtLane ln = DtLane::make(dg, lt % dg.W);
   const uint32_t* __restrict__ tscs = tsc + 8 * ls * NS;
   const uint32_t* __restrict__ tgens = tgen + ls * NS;
-#ifdef EXP_IPA_NOWALK  // timing experiment only (wrong results): no walk, no tree
-  if (tid < S) store_p3(out_p3, S == 2 ? (2 * inst + tid) * J + jp : bidx, ge_identity());
-  return;
-#endif
   const uint32_t t0 = (uint32_t)((uint64_t)jp * NS / J), t1 = (uint32_t)((uint64_t)(jp + 1) * NS / J);
   const ge_p3 acc = tg < TG ? dt_walk<QP>(dt, dg, ln, t0 + tg, t1, TG,
                                           [&](uint32_t t, uint32_t s[8], uint32_t& gen) {
@@ -558,10 +525,6 @@ FE_INLINE void ipa_round_body(const uint32_t* __restrict__ dt, const DtGeom& dg,
                                           ge_identity(), A.qrow0)
                             : ge_identity();
   __syncthreads();
-#ifdef EXP_IPA_NOTREE  // timing experiment only (wrong results): no block tree
-  if (lt == 0) store_p3(out_p3, S == 2 ? (2 * inst + ls) * J + jp : bidx, acc);
-  return;
-#endif
   // result of side s: out_p3[(2 inst + s) J + jp] (= bidx for S = 1)
   dt_block_tree_segs(lds, acc, nt, S, out_p3, S == 2 ? 2 * inst * J + jp : bidx, J);
   if (A.done_word) done_signal(A.done_ticket, A.done_word, A.done_tag);
@@ -599,140 +562,6 @@ __global__ void __launch_bounds__(DT_NT_MAX) k_ipa_round_dt(
   }
   ipa_round_body<QP>(dt, dg, n, TG, A, blockIdx.x, lds, S);
 }
-
-// Several batches' rounds in one launch (BPP_IPA_MERGE, the shared-launch
-// round scheduler below): block b runs block b - prefix of batch j.  args:
-// nargs structs in pinned host memory, read once per block into LDS.
-#define IPA_MERGE_MAX 16
-__global__ void __launch_bounds__(DT_NT_MAX) k_ipa_round_dt_multi(const uint32_t* __restrict__ dt, DtGeom dg,
-                                                                 uint32_t n, uint32_t TG,
-                                                                 const IpaRoundArgs* __restrict__ args,
-                                                                 uint32_t nargs) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  __shared__ IpaRoundArgs sA;
-  __shared__ uint32_t sb;
-  if (threadIdx.x == 0) {
-    uint32_t b = blockIdx.x, j = 0;
-    while (j + 1 < nargs && b >= args[j].blocks) b -= args[j++].blocks;
-    sA = args[j];
-    sb = b;
-  }
-  __syncthreads();
-  ipa_round_body<false>(dt, dg, n, TG, sA, sb, lds, 1);  // (the merged launches never carry qpow)
-}
-
-// The shared-launch round scheduler (BPP_IPA_MERGE=1; an
-// A/B switch): the batches in flight on one device hand their fused IPA
-// rounds to one merger, which issues ONE k_ipa_round_dt_multi over every
-// round pending at the time on its own stream, after each batch's stream has
-// reached the round (an event per request).  Combining: the first thread to
-// arrive leads -- it waits BPP_IPA_MERGE_US (default 0) for others, takes
-// every pending request with the same shape (n, TG, tables), launches, and
-// wakes them; each then waits for the launch's event.  A batch's round thus
-// runs as part of a larger grid (more waves per SIMD for the latency-bound
-// walk and tree) instead of on its own queue beside the others.
-namespace {
-struct IpaMergeReq {
-  IpaRoundArgs a;
-  hipEvent_t ready = nullptr;  // recorded on the batch's stream
-  const uint32_t* dt = nullptr;
-  DtGeom dg;
-  uint32_t n = 0, TG = 0, nt = 0;
-  size_t lds = 0;
-  uint64_t gen = 0;            // set when launched
-  hipEvent_t done = nullptr;   // the launch's completion
-  int err = BPP_OK;
-};
-struct IpaMerger {
-  std::mutex mu;
-  std::condition_variable cv;
-  bool leading = false;
-  uint64_t gen = 0;
-  std::vector<IpaMergeReq*> pending;
-  hipStream_t stream = nullptr;
-  static constexpr int RING = 64;
-  IpaRoundArgs* ring = nullptr;  // pinned: RING x IPA_MERGE_MAX argument blocks
-  hipEvent_t ring_ev[RING] = {};
-  bool ring_used[RING] = {};
-  int ring_pos = 0;
-  uint64_t launches = 0, rounds = 0;
-};
-IpaMerger& ipa_merger(int dev) {
-  static std::mutex mu;
-  static std::map<int, std::unique_ptr<IpaMerger>> all;
-  std::lock_guard<std::mutex> g(mu);
-  auto& p = all[dev];
-  if (!p) p.reset(new IpaMerger);
-  return *p;
-}
-bool same_shape(const IpaMergeReq& a, const IpaMergeReq& b) {
-  return a.dt == b.dt && a.n == b.n && a.TG == b.TG && a.nt == b.nt && a.dg.c == b.dg.c;
-}
-// the leader's launch of `reqs` (same shape); sets their gen / done
-int merger_launch(bpp_ctx* ctx, IpaMerger& M, std::vector<IpaMergeReq*>& reqs) {
-  if (!M.stream) BPP_HIP(hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking));
-  if (!M.ring) BPP_HIP(hipHostMalloc((void**)&M.ring, sizeof(IpaRoundArgs) * IPA_MERGE_MAX * IpaMerger::RING));
-  const int slot = M.ring_pos;
-  M.ring_pos = (M.ring_pos + 1) % IpaMerger::RING;
-  if (!M.ring_ev[slot]) BPP_HIP(hipEventCreateWithFlags(&M.ring_ev[slot], hipEventDisableTiming));
-  if (M.ring_used[slot]) BPP_HIP(hipEventSynchronize(M.ring_ev[slot]));  // (its last launch has read the slot)
-  IpaRoundArgs* args = M.ring + (size_t)slot * IPA_MERGE_MAX;
-  uint32_t blocks = 0;
-  for (size_t i = 0; i < reqs.size(); ++i) {
-    args[i] = reqs[i]->a;
-    blocks += reqs[i]->a.blocks;
-    BPP_HIP(hipStreamWaitEvent(M.stream, reqs[i]->ready, 0));
-  }
-  const IpaMergeReq& r0 = *reqs[0];
-  hipLaunchKernelGGL(k_ipa_round_dt_multi, dim3(blocks), dim3(r0.nt), r0.lds, M.stream, r0.dt, r0.dg, r0.n, r0.TG,
-                     (const IpaRoundArgs*)args, (uint32_t)reqs.size());
-  BPP_HIP(hipGetLastError());
-  BPP_HIP(hipEventRecord(M.ring_ev[slot], M.stream));
-  M.ring_used[slot] = true;
-  ++M.launches;
-  M.rounds += reqs.size();
-  for (IpaMergeReq* r : reqs) r->done = M.ring_ev[slot];
-  return BPP_OK;
-}
-// Blocks until the request's round has been launched; returns the event to
-// wait for (or an error).
-int merger_submit(bpp_ctx* ctx, IpaMergeReq& req) {
-  IpaMerger& M = ipa_merger(ctx->device);
-  static const int wait_us = [] {
-    const char* e = getenv("BPP_IPA_MERGE_US");
-    return e ? std::max(0, atoi(e)) : 0;
-  }();
-  std::unique_lock<std::mutex> lk(M.mu);
-  M.pending.push_back(&req);
-  for (;;) {
-    if (req.gen) return req.err;
-    if (!M.leading) break;
-    M.cv.wait(lk);
-  }
-  // lead: gather, launch every pending request of this shape, wake them
-  M.leading = true;
-  if (wait_us > 0) {
-    lk.unlock();
-    std::this_thread::sleep_for(std::chrono::microseconds(wait_us));
-    lk.lock();
-  }
-  std::vector<IpaMergeReq*> take{&req}, keep;  // (the leader's own request first)
-  for (IpaMergeReq* r : M.pending)
-    if (r != &req) (same_shape(*r, req) && take.size() < IPA_MERGE_MAX ? take : keep).push_back(r);
-  M.pending.swap(keep);
-  lk.unlock();
-  const int rc = merger_launch(ctx, M, take);
-  lk.lock();
-  const uint64_t g = ++M.gen;
-  for (IpaMergeReq* r : take) {
-    r->gen = g;
-    r->err = rc;
-  }
-  M.leading = false;
-  M.cv.notify_all();
-  return req.err;
-}
-}  // namespace
 
 // LDS words of k_ipa_round_dt: terms + indices + a, b + wave partials, or
 // the block tree, whichever is larger
@@ -849,22 +678,12 @@ int ipa_prove_batch_dev(bpp_ctx* ctx, const std::vector<merlin::Transcript*>& tr
     BPP_TRY(ctx_ws(ctx, "ipa_res", (size_t)2 * P * P3_BYTES, &d_res));
     dg = dt_geom(g.pts.dt_c);
     TG = dt_term_groups(dg.W, (double)(n + 1), 2 * P);  // as msm_multi_dt_dev for (n + 1)-term MSMs
-    static const int tg_env = [] {  // term groups per side (A/B switch)
-      const char* e = getenv("BPP_IPA_TG");
-      return e ? atoi(e) : 0;
-    }();
-    if (tg_env >= 1 && (uint32_t)tg_env * dg.W <= DT_NT_MAX) TG = (uint32_t)tg_env;
     nt = TG * dg.W;
   }
   // Both sides of an instance in one block (ipa_round_body S = 2) for batches
-  // that fill the device with blocks anyway; BPP_IPA_LR=0 keeps one side per
-  // block (A/B switch)
-  static const bool lr_env = [] {
-    const char* e = getenv("BPP_IPA_LR");
-    return !e || atoi(e) != 0;
-  }();
+  // that fill the device with blocks anyway
   uint32_t sides = 1;
-  if (fused && lr_env && P >= 128 && 2 * nt <= DT_NT_MAX && ipa_round_lds_words(n, 2 * nt, 2) * 4 <= 65536) sides = 2;
+  if (fused && P >= 128 && 2 * nt <= DT_NT_MAX && ipa_round_lds_words(n, 2 * nt, 2) * 4 <= 65536) sides = 2;
   // Device transcript path (an A/B experiment: see
   // DESIGN.md): the rounds run back to back on the stream -- fused MSM,
   // k_compress_p3 of L and R, k_ipa_transcript_step (Merlin + u^-1) --
@@ -875,75 +694,40 @@ int ipa_prove_batch_dev(bpp_ctx* ctx, const std::vector<merlin::Transcript*>& tr
   // kernel writes L/2, R/2 straight into pinned host memory and reads the
   // challenges u, u^-1 from it (ctx_host_buf), where a device result buffer
   // and a staged upload cost a copy launch each way per round.
-#ifdef EXP_IPA_NOZC
-  const bool zc = false;
-#else
   const bool zc = fused && !dev_merlin;
-#endif
-  // the shared-launch round scheduler (A/B switch, off by default)
-  static const bool merge_env = [] {
-    const char* e = getenv("BPP_IPA_MERGE");
-    return e && atoi(e) != 0;
-  }();
-  const bool merge = merge_env && zc && !g.qpow;
   // J blocks per L / R MSM when the batch is small (config 2: P = 1, two
   // blocks of one wave per SIMD walking ~64 of the 1025 terms per lane in a
   // row): each block walks a slice of the terms and the host adds the J
-  // partials before it encodes (zero-copy path only; BPP_IPA_SPLIT overrides).
-  // Since each block folds only its own slice (IPA_SPLIT_PROLOGUE) a slice
-  // may be as short as one term per lane group: config 2 J = 16 1.10-1.13 ms,
+  // partials before it encodes (zero-copy path only).
+  // Since each block folds only its own slice a slice may be as short as one
+  // term per lane group: config 2 J = 16 1.10-1.13 ms,
   // 32 1.06, 64 1.10 (profiles/r06_ipa_jsweep.txt)
   uint32_t J = 1;
   if (zc && nt) {
-    static const int split_env = [] {
-      const char* e = getenv("BPP_IPA_SPLIT");
-      return e ? atoi(e) : -1;
-    }();
-    if (split_env >= 1) {
-      J = (uint32_t)split_env;
-    } else if (split_env < 0) {
-#ifndef IPA_J_MAX
-#define IPA_J_MAX 32
-#endif
-#ifndef IPA_J_SLICE_TG
-#define IPA_J_SLICE_TG (IPA_SPLIT_PROLOGUE ? 1 : 2)
-#endif
-      const uint32_t per_slice = IPA_J_SLICE_TG * TG;
-      while (J < IPA_J_MAX && 2 * P * (2 * J) <= 512 && (n + 1) / (2 * J) >= per_slice) J *= 2;
-    }
+    constexpr uint32_t J_MAX = 32, J_SLICE_TG = 1;  // slices at most; terms per lane group of a slice at least
+    while (J < J_MAX && 2 * P * (2 * J) <= 512 && (n + 1) / (2 * J) >= J_SLICE_TG * TG) J *= 2;
   }
-  // the J partials of each L / R summed on the device (k_ipa_jsum, one
-  // block per MSM, a 5-level tree for J = 32) rather than by 2 (J - 1) host
-  // additions between the rounds: an A/B switch, off (BPP_IPA_JSUM=1 on).
-  // Config 2 measured 1.10-1.11 ms with it against 1.03-1.04 without: the
-  // host's 62 additions take ~6.5 us a round, the extra launch and its tree
-  // ~13 us of the round's wait (profiles/r06_ipa_jsum_ab.txt)
-  static const bool jsum_env = [] {
-    const char* e = getenv("BPP_IPA_JSUM");
-    return e && atoi(e) != 0;
-  }();
-  const bool dev_jsum = zc && !merge && J > 1 && J <= 64 && (J & (J - 1)) == 0 && jsum_env;
-  void* d_part = nullptr;  // dev_jsum: the round kernel's J partials per MSM
+  // (The J partials of each L / R summed on the device, one block per MSM and
+  // a 5-level tree for J = 32, rather than by 2 (J - 1) host additions between
+  // the rounds, was measured behind a switch since removed: config 2 1.10-1.11
+  // ms with it against 1.03-1.04 without: the host's 62 additions take ~6.5 us
+  // a round, the extra launch and its tree ~13 us of the round's wait,
+  // profiles/r06_ipa_jsum_ab.txt)
   // one IPA alone (bpp_ipa_prove: P = 1 on a spinning context) waits for
   // each round through the kernel's completion flag instead of an event
-  // (ctx_wait_flag; BPP_IPA_FLAG=0 off): config 2 0.92-0.95 vs 0.96-0.99 ms.
+  // (ctx_wait_flag): config 2 0.92-0.95 vs 0.96-0.99 ms.
   // Not for prover batches: with 8 sub-batches in flight the busy flag
   // waits cost the config-4 job 7.5-9.1 vs 7.0-7.2 ms (r06_ipa_flag_ab.txt)
-  static const bool flag_env = [] {
-    const char* e = getenv("BPP_IPA_FLAG");
-    return !e || atoi(e) != 0;
-  }();
-  const bool use_flag = zc && !merge && !dev_jsum && P == 1 && ctx->sync_spin_us > 0 && flag_env;
+  const bool use_flag = zc && P == 1 && ctx->sync_spin_us > 0;
   uint32_t *done_ticket = nullptr, *done_word = nullptr, done_tag = 0;
   uint32_t* h_uw = nullptr;  // zc: the challenges' device words, in place
   if (zc) {
     void *hr = nullptr, *hu = nullptr;
-    BPP_TRY(ctx_host_buf(ctx, "ipa_res_h", (size_t)2 * P * (dev_jsum ? 1 : J) * P3_BYTES, &hr));
+    BPP_TRY(ctx_host_buf(ctx, "ipa_res_h", (size_t)2 * P * J * P3_BYTES, &hr));
     BPP_TRY(ctx_host_buf(ctx, "ipa_u_h", (size_t)P * 64, &hu));
     d_res = hr;
     d_u = hu;
     h_uw = (uint32_t*)hu;
-    if (dev_jsum) BPP_TRY(ctx_ws(ctx, "ipa_part", (size_t)2 * P * J * P3_BYTES, &d_part));
   }
   void *d_states = nullptr, *d_lr = nullptr;
   if (dev_merlin) {
@@ -961,47 +745,14 @@ int ipa_prove_batch_dev(bpp_ctx* ctx, const std::vector<merlin::Transcript*>& tr
     const uint32_t h = m >> 1;
     if (fused) {
       const int in = cur, outs = cur ^ 1;
-      if (merge) {  // one launch with the other batches' pending rounds (the merger's stream)
-        static thread_local hipEvent_t ready = nullptr;
-        if (!ready) BPP_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-        IpaMergeReq req;
-        IpaRoundArgs& A = req.a;
-        A.am_in = S[in][0]; A.bm_in = S[in][1]; A.fG_in = S[in][2]; A.fH_in = S[in][3];
-        A.am_out = S[round ? outs : in][0]; A.bm_out = S[round ? outs : in][1];
-        A.fG_out = S[round ? outs : in][2]; A.fH_out = S[round ? outs : in][3];
-        A.u = (const uint32_t*)d_u; A.qmul = (const uint32_t*)d_q; A.out_p3 = (uint32_t*)d_res;
-        A.a0 = d_a; A.b0 = d_b; A.gf0 = d_Gf; A.hf0 = d_Hf;
-        A.m = m; A.lg_h = lg_h; A.fold = round ? 1u : 0u; A.init = round ? 0u : 1u; A.halve = 1u;
-        A.gbase = g.gbase; A.hbase = g.hbase; A.qidx = g.qidx;
-        A.blocks = 2 * P * J;
-        A.split = J;
-        A.qpow = g.qpow;
-        A.qrow0 = 0;  // (merged launches never carry qpow: merge is off with it)
-        A.done_ticket = A.done_word = nullptr;
-        A.done_tag = 0;
-        A.u1 = 0;
-        req.dt = g.pts.dt;
-        req.dg = dg;
-        req.n = n;
-        req.TG = TG;
-        req.nt = nt;
-        req.lds = ipa_round_lds_words(n, nt) * 4;
-        BPP_HIP(hipEventRecord(ready, ctx->stream));
-        req.ready = ready;
-        BPP_TRY(merger_submit(ctx, req));
-        BPP_HIP(hipStreamWaitEvent(ctx->stream, req.done, 0));  // (ctx_sync below then covers the round)
-      } else {
+      {
         ProfScope ps(ctx, "ipa_round_dt");  // (bench.py: this kernel's own roofline)
         if (use_flag) BPP_TRY(ctx_done_flag(ctx, &done_ticket, &done_word, &done_tag));
         // one instance: its u words as kernel arguments (the host wrote them
-        // after the last round; BPP_IPA_U_ARG=0: read in place).  Config 2
+        // after the last round) instead of a read in place.  Config 2
         // best of four 0.795 vs 0.804 ms, within the run-to-run noise
         // (r06_ipa_uarg_ab.txt)
-        static const bool u1_env = [] {
-          const char* e = getenv("BPP_IPA_U_ARG");
-          return !e || atoi(e) != 0;
-        }();
-        const bool u1 = P == 1 && zc && round > 0 && u1_env;
+        const bool u1 = P == 1 && zc && round > 0;
         IpaU1 u1w{};
         if (u1) memcpy(u1w.w, h_uw, sizeof u1w.w);
         hipLaunchKernelGGL(g.qpow ? k_ipa_round_dt<true> : k_ipa_round_dt<false>, dim3(2 / sides * P * J),
@@ -1011,12 +762,9 @@ int ipa_prove_batch_dev(bpp_ctx* ctx, const std::vector<merlin::Transcript*>& tr
                            g.pts.dt, dg, n, m, lg_h, round ? 1u : 0u, S[in][0], S[in][1], S[in][2], S[in][3],
                            S[round ? outs : in][0], S[round ? outs : in][1], S[round ? outs : in][2],
                            S[round ? outs : in][3], (const uint32_t*)d_u, (const uint32_t*)d_q, g.gbase, g.hbase,
-                           g.qidx, TG, dev_merlin ? 0u : 1u, (uint32_t*)(dev_jsum ? d_part : d_res), d_a, d_b,
+                           g.qidx, TG, dev_merlin ? 0u : 1u, (uint32_t*)d_res, d_a, d_b,
                            d_Gf, d_Hf, round ? 0u : 1u, J, sides, g.qpow, done_ticket,
                            use_flag ? done_word : nullptr, done_tag, u1 ? 1u : 0u, u1w);
-        if (dev_jsum)
-          hipLaunchKernelGGL(k_ipa_jsum, dim3(2 * P), dim3(J), (size_t)J * P3_BYTES, ctx->stream,
-                             (const uint32_t*)d_part, J, (uint32_t*)d_res);
       }
       BPP_TRY(ctx_check_launch(ctx, "k_ipa_round_dt"));
       if (round) cur = outs;
@@ -1040,12 +788,12 @@ int ipa_prove_batch_dev(bpp_ctx* ctx, const std::vector<merlin::Transcript*>& tr
         {
           HostScope hw(ctx, "ipa_wait");
           // the kernel's L/2, R/2 are in host memory now
-          if (use_flag && !merge)
+          if (use_flag)
             BPP_TRY(ctx_wait_flag(ctx, done_word, done_tag));
           else
             BPP_TRY(ctx_sync(ctx));
         }
-        BPP_TRY(points_double_encode_host(ctx, (const uint32_t*)d_res, 2 * (size_t)P, enc.data(), dev_jsum ? 1 : J));
+        BPP_TRY(points_double_encode_host(ctx, (const uint32_t*)d_res, 2 * (size_t)P, enc.data(), J));
       } else {
         HostScope hs(ctx, "ipa_msm");
         BPP_TRY(points_double_encode_p3(ctx, (const uint32_t*)d_res, 2 * (size_t)P, enc.data()));

@@ -192,13 +192,9 @@ int bpp_vec_commit(bpp_ctx* ctx, const bpp_gens* g, const uint8_t blind[32], con
     // one long MSM alone runs as one block (one wave per SIMD walking ~T/16
     // terms per lane in a row): cut it into J slices of >= 32 terms, J blocks
     // side by side, and add the J results here (ge_sum_auto) -- config 2's
-    // 2049 terms: BPP_VC_SPLIT caps J (default 64; config 2 at 16 / 32 / 64
-    // slices 1.016-1.024 / 0.996-1.004 / 0.979-0.996 ms, r06_vc_split_ab.txt)
-    static const size_t vc_split = [] {
-      const char* e = getenv("BPP_VC_SPLIT");
-      return (size_t)std::max(1, e ? atoi(e) : 64);
-    }();
-    const uint32_t J = (uint32_t)std::max<size_t>(1, std::min<size_t>(vc_split, T / 32));
+    // 2049 terms: at most 64 slices (config 2 at 16 / 32 / 64 slices
+    // 1.016-1.024 / 0.996-1.004 / 0.979-0.996 ms, r06_vc_split_ab.txt)
+    const uint32_t J = (uint32_t)std::max<size_t>(1, std::min<size_t>(64, T / 32));
     std::vector<uint32_t> off(J + 1);
     for (uint32_t j = 0; j <= J; ++j) off[j] = (uint32_t)((uint64_t)T * j / J);
     BPP_TRY(msm_multi(ctx, d_s, (const uint32_t*)d_i, off, pts, res));
@@ -230,54 +226,12 @@ void niels_row_host(const h25519::ge& p, const h25519::fe& zi, uint32_t w[MSM_NI
   w[30] = w[31] = 0;
 }
 
-// Q into the generators' Q slot (gens.h): its window points 2^(8u) Q, u <
-// 32, on the host (248 doublings: ~35 us, where one GPU lane's chain took
-// ~0.5 ms), their Niels rows uploaded as a window table, then Q's direct-table
-// rows built on the device into slot 2n + 2 and its Niels row into d_tbl.
-// The caller holds g->q_mu until the IPA using the slot has completed.
-int ipa_q_slot(bpp_ctx* ctx, const bpp_gens* g, const uint8_t Q[32], uint32_t dt_c) {
-  h25519::ge P;
-  if (!h25519::decode(P, Q)) {
-    ctx->err = "Q does not decode";
-    return BPP_ERR_DECOMPRESS;
-  }
-  std::vector<uint32_t> wt((size_t)FBW_W * MSM_NIELS_WORDS);
-  std::vector<h25519::ge> pts(FBW_W);
-  h25519::ge cur = P;
-  for (uint32_t u = 0; u < FBW_W; ++u) {
-    pts[u] = cur;
-    for (uint32_t i = 0; i < FBW_C; ++i) cur = h25519::ge_dbl(cur);
-  }
-  // the FBW_W inverses of Z by one field inversion (Montgomery's trick): the
-  // latency of bpp_ipa_prove on a fresh Q (config 2: ~75 -> ~15 us of host time)
-  std::vector<h25519::fe> pre(FBW_W);
-  h25519::fe run = h25519::fe_one();
-  for (uint32_t u = 0; u < FBW_W; ++u) {
-    pre[u] = run;
-    run = h25519::fe_mul(run, pts[u].Z);  // (Z is never zero for a decoded point)
-  }
-  h25519::fe inv = h25519::fe_invert(run);
-  for (uint32_t u = FBW_W; u-- > 0;) {
-    const h25519::fe zi = h25519::fe_mul(inv, pre[u]);
-    inv = h25519::fe_mul(inv, pts[u].Z);
-    niels_row_host(pts[u], zi, &wt[(size_t)u * MSM_NIELS_WORDS]);
-  }
-  void* d_wt = nullptr;
-  BPP_TRY(ctx_ws(ctx, "ipa_q_wt", wt.size() * 4, &d_wt));
-  BPP_TRY(ctx_h2d(ctx, d_wt, wt.data(), wt.size() * 4));
-  // (slot rows start after the 2n + 2 generators' rows: dt_bytes per point)
-  uint32_t* slot = g->d_dt + dt_bytes(g->qslot(), dt_c) / 4;
-  BPP_TRY(dt_build(ctx, (const uint32_t*)d_wt, 1, dt_c, slot));
-  BPP_HIP(hipMemcpyAsync(g->d_tbl + (size_t)g->qslot() * MSM_NIELS_WORDS, d_wt, MSM_NIELS_WORDS * 4,
-                         hipMemcpyDeviceToDevice, ctx->stream));
-  return BPP_OK;
-}
 // Q as its doublings 2^j Q, j < 253 (IpaGens::qpow): 253 doublings on the
-// host (the window points of a Q-slot table took 248), their Z inverses by
-// one field inversion, and the 253 Niels rows written over the start of g's
-// Q slot (the caller holds g->q_mu until the IPA has completed).  The fused
-// rounds then add c Q bit by bit (ipa.hip q_bits_*, DtLane::row_of_q): no
-// direct table is built for Q, where its build was 152 us of config 2.
+// host, their Z inverses by one field inversion, and the 253 Niels rows
+// written over the start of g's Q slot (the caller holds g->q_mu until the
+// IPA has completed).  The fused rounds then add c Q bit by bit
+// (DtLane::row_of_q): no direct table is built for Q, where its build was
+// 152 us of config 2.
 int ipa_q_powers(bpp_ctx* ctx, const bpp_gens* g, const uint8_t Q[32], uint32_t dt_c, const uint32_t** d_out) {
   h25519::ge P;
   if (!h25519::decode(P, Q)) {
@@ -330,43 +284,26 @@ static int ipa_prove_api(bpp_ctx* ctx, const bpp_gens* g, IpaTranscript* tr, con
     ig.gbase = 0;
     ig.hbase = (uint32_t)g->n;
     // Q in the generators' slot when they have direct tables and the rounds
-    // can run fused (BPP_IPA_QSLOT=0: Q as an extra point, the four-kernel
-    // rounds over the generic engine)
-    static const bool qslot_env = [] {
-      const char* e = getenv("BPP_IPA_QSLOT");
-      return !e || atoi(e) != 0;
-    }();
+    // can run fused; otherwise Q as an extra point, the four-kernel rounds
+    // over the generic engine
     std::unique_lock<std::mutex> qlock;
     // (exactly the fused rounds' condition, ipa.hip: the slot has direct-table
     // rows and a Niels row only, no window-table rows for the other engines)
-    const bool qslot =
-        qslot_env && n >= 2 && n <= IPA_FUSED_NMAX && msm_use_dt(ig.pts, 2, (uint32_t)(2 * n + 2));
-    // the fused path: Q's table build is queued first, and a, b and the
+    const bool qslot = n >= 2 && n <= IPA_FUSED_NMAX && msm_use_dt(ig.pts, 2, (uint32_t)(2 * n + 2));
+    // the fused path: Q's rows are queued first, and a, b and the
     // factors are read in place by round 0 from pinned host memory (each
     // element once) -- the inputs' staging copies and H2D enqueues, ~40 us
-    // of host time, run beside the build instead of before it
+    // of host time, run beside that upload instead of before it
     bool zc_in = false;
     IpaZcWipe wipe(ctx);  // (destroyed before qlock: the drain below runs first)
     IpaProofHost pf;
-    // Q in the fused rounds: by its doublings (IpaGens::qpow, default) or in
-    // g's Q slot with a per-call direct table (BPP_IPA_QPOW=0)
-    static const bool qpow_env = [] {
-      const char* e = getenv("BPP_IPA_QPOW");
-      return !e || atoi(e) != 0;
-    }();
     auto body = [&]() -> int {
       if (qslot) {
         qlock = std::unique_lock<std::mutex>(g->q_mu);
-        if (qpow_env)
-          BPP_TRY(ipa_q_powers(ctx, g, Q, ig.pts.dt_c, &ig.qpow));
-        else
-          BPP_TRY(ipa_q_slot(ctx, g, Q, ig.pts.dt_c));
+        // Q in the fused rounds: by its doublings (IpaGens::qpow)
+        BPP_TRY(ipa_q_powers(ctx, g, Q, ig.pts.dt_c, &ig.qpow));
         ig.qidx = g->qslot();
-        static const bool zc_env = [] {
-          const char* e = getenv("BPP_IPA_ZC_IN");
-          return !e || atoi(e) != 0;
-        }();
-        zc_in = zc_env;
+        zc_in = true;
       } else {
         BPP_TRY(decompress_ws(ctx, Q, 1, "ipa_q", &d_q));
         BPP_TRY(msm_points_extra(ctx, &ig.pts, d_q, 1, (uint32_t)(2 * g->n + 2), "ipa_q_wt", (double)(n + 1)));

@@ -28,11 +28,6 @@ bool scalar_is_canonical(const uint8_t* s) {
 }
 
 uint32_t msm_choose_c(double n_per_msm) {
-  static const int c_env = [] {  // (A/B runs: one window size for every MSM)
-    const char* e = getenv("BPP_MSM_C");
-    return e ? atoi(e) : 0;
-  }();
-  if (c_env >= 2 && c_env <= 16) return (uint32_t)c_env;
   uint32_t best = 4;
   double bestc = 1e300;
   // c <= 16: a window's bucket histogram (2^(c-1) x 4 B) fits in LDS
@@ -266,7 +261,6 @@ int msm_engine(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx, con
       BPP_TRY(ctx_ws(ctx, "msm_rpart", nseg * nw * 2 * P3_BYTES, &part));
       BPP_TRY(ctx_ws(ctx, "msm_wsum_terms", nseg * (1 + J) * P3_BYTES, &wsum));
       ProfScope ps(ctx, "msm_reduce");
-#ifndef EXP_NO_REDUCE  // (timing experiment only: results are wrong without it)
       if (rlog == RWAVE_LOG) {
         hipLaunchKernelGGL(k_msm_reduce_wave<RWAVE_LOG>, dim3((unsigned)(nseg * nw)), dim3(64), 0, ctx->stream,
                            (const uint32_t*)boff, K, (const uint32_t*)head, (const uint32_t*)tail,
@@ -288,7 +282,6 @@ int msm_engine(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx, con
           default: launch(k_msm_reduce_wave<3>, k_msm_reduce_bits<3>); break;
         }
       }
-#endif
       BPP_TRY(ctx_check_launch(ctx, "k_msm_reduce_wave/bits"));
       *terms_out = 1 + J;
       if (rshift_out) *rshift_out = rshift;
@@ -347,12 +340,8 @@ int msm_single_dev(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx,
   // (window groups pipelined over two child streams measured slower: G = 2
   // 1.38 ms, G = 4 1.70 ms vs 1.26 ms at 2^20 -- the reduce and fixup are
   // latency-bound and would run G times)
-  // alone on the device: the latency-shaped bucket reduction (RWAVE_LOG_LONE;
-  // BPP_MSM_LONE_RLOG=4 selects the stream shape, for A/B runs)
-  static const uint32_t rlog = [] {
-    const char* e = getenv("BPP_MSM_LONE_RLOG");
-    return (e && atoi(e) == RWAVE_LOG) ? (uint32_t)RWAVE_LOG : (uint32_t)RWAVE_LOG_LONE;
-  }();
+  // alone on the device: the latency-shaped bucket reduction
+  const uint32_t rlog = RWAVE_LOG_LONE;
   uint32_t* d_ws = nullptr;
   uint32_t nterms = 1, rshift = rlog + 6;
   BPP_TRY(msm_engine(ctx, d_scal, d_pidx, nullptr, 1, (uint32_t)n, c, wb, Wn, d_tbl, &d_ws, d_tbl1, n0, false,
@@ -366,18 +355,14 @@ int msm_single_dev(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx,
 }
 
 // Host scalars -> device d on ctx's stream: staged into ctx's pinned arena by
-// the pool in pieces of 2^17 scalars (4 MB; BPP_UP_PIECE_SC overrides, for
-// A/B), each piece checked for canonical scalars while it is in cache (when
+// the pool in pieces of 2^17 scalars (4 MB), each piece checked for
+// canonical scalars while it is in cache (when
 // `check`) and its DMA queued as soon as it is staged, so the copy engine
 // moves piece k while the pool stages piece k + 1.  Returns the index of the
 // first non-canonical scalar, or n.  (2^20 one at a time: one serial check
 // pass, a parallel copy and then the whole DMA took ~1.7 ms before the MSM.)
 static int upload_pieces(bpp_ctx* ctx, void* d, const uint8_t* scalars, size_t n, bool check, size_t* bad_out) {
-  static const size_t PIECE = [] {
-    const char* e = getenv("BPP_UP_PIECE_SC");
-    const long v = e ? atol(e) : 0;
-    return v > 0 ? ((size_t)v + 4095) & ~(size_t)4095 : (size_t)1 << 17;
-  }();
+  constexpr size_t PIECE = (size_t)1 << 17;
   constexpr size_t SUB = 4096;  // scalars per pool task
   *bad_out = n;
   if (!n) return BPP_OK;
@@ -526,14 +511,10 @@ static int msm_submit(bpp_ctx* ctx, const void* d_scalars, const void* h_scalars
   // Another MSM in flight: hold this accumulation to 3 workgroups per CU
   // (LDS 40 + 13 KB each) so the other MSM's sort runs beside it rather than
   // after it -- 2^20, two in flight: 0.97 -> 0.945 ms per MSM; alone it
-  // would cost the accumulation ~8 % (BPP_ACC_LDS_PAD overrides the pad).
+  // would cost the accumulation ~8 %.
   bool others = false;
   for (size_t i = 0; i < BPP_MSM_INFLIGHT; ++i) others |= ctx->msm_slot[i].busy;
-  static const long pad_env = [] {
-    const char* e = getenv("BPP_ACC_LDS_PAD");
-    return e ? atol(e) : -1L;
-  }();
-  ch->acc_lds_pad = others ? (pad_env >= 0 ? (size_t)pad_env : (size_t)13000) : 0;
+  ch->acc_lds_pad = others ? 13000 : 0;
   if (!sl.done) BPP_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
   // inputs written on ctx's stream before this call are visible to the child
   BPP_HIP(hipEventRecord(sl.done, ctx->stream));
@@ -548,16 +529,10 @@ static int msm_submit(bpp_ctx* ctx, const void* d_scalars, const void* h_scalars
       if (ch->up_sc) BPP_HIP(hipFree(ch->up_sc));
       ch->up_sc = nullptr;
       ch->up_sc_bytes = 0;
-      // (BPP_MSM_UP_CACHED=1: an ordinary allocation; by default uncached,
-      // so that the upload's 32 B x n writes do not evict the point table
-      // the other MSMs' accumulations gather from the caches; the digit
-      // kernel reads each scalar once)
-      const bool cached = getenv("BPP_MSM_UP_CACHED") && atoi(getenv("BPP_MSM_UP_CACHED"));
-      if (cached) {
-        BPP_HIP(hipMalloc(&ch->up_sc, n * 32));
-      } else {
-        BPP_HIP(hipExtMallocWithFlags(&ch->up_sc, n * 32, hipDeviceMallocUncached));
-      }
+      // uncached, so that the upload's 32 B x n writes do not evict the
+      // point table the other MSMs' accumulations gather from the caches;
+      // the digit kernel reads each scalar once
+      BPP_HIP(hipExtMallocWithFlags(&ch->up_sc, n * 32, hipDeviceMallocUncached));
       ch->up_sc_bytes = n * 32;
     }
     void* d = ch->up_sc;
@@ -880,17 +855,11 @@ int dt_build(bpp_ctx* ctx, const uint32_t* d_wt, uint32_t npts, uint32_t c, uint
     return BPP_ERR_LEN;
   }
   // 4 rows a lane (k_dt_build_n: one double-and-add and one inversion per 4
-  // rows; BPP_DT_BUILD_RPL=1 keeps one row a lane, an A/B switch)
-  static const int rpl = [] {
-    const char* e = getenv("BPP_DT_BUILD_RPL");
-    return e ? atoi(e) : 4;
-  }();
+  // rows)
   {
     ProfScope ps(ctx, "dt_tables");
-    if (rpl == 4 && g.H % 4 == 0)
+    if (g.H % 4 == 0)
       hipLaunchKernelGGL(k_dt_build_n<4>, dim3(grid_for(rows / 4, 64)), dim3(64), 0, ctx->stream, d_wt, npts, g, d_dt);
-    else if (rpl == 2)
-      hipLaunchKernelGGL(k_dt_build_n<2>, dim3(grid_for(rows / 2, 64)), dim3(64), 0, ctx->stream, d_wt, npts, g, d_dt);
     else
       hipLaunchKernelGGL(k_dt_build, dim3(grid_for(rows, 64)), dim3(64), 0, ctx->stream, d_wt, npts, g, d_dt);
   }
@@ -924,17 +893,13 @@ static int msm_multi_dt_dev(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t
   const double t_avg = (double)T / (double)M;
   const uint32_t TG = dt_term_groups(dg.W, t_avg, M);
   const uint32_t nt = TG * dg.W;
-  // two MSMs per block (k_dt_msm segs = 2, BPP_DT_PAIR=1) for launches with
-  // blocks to spare, an A/B switch, off: round 6 re-ran the A/B at the bench's
-  // prover shape (384 x 32 in flight, 8 queues): proofs/s equal (363-365 K
-  // vs 364-366 K), but one MSM per block issues more (k_dt_msm VALU issue
-  // 0.359 vs 0.314, wait_any 0.368 vs 0.456) and misses the UTCL1 less (5.2 %
-  // vs 8.3 % of requests); profiles/r06_dt_pair_ab.txt, r06_tlb_prover.json
-  static const bool pair_env = [] {
-    const char* e = getenv("BPP_DT_PAIR");
-    return e && atoi(e) != 0;
-  }();
-  const uint32_t segs = pair_env && M >= 512 && 2 * nt <= DT_NT_MAX ? 2u : 1u;
+  // One MSM per block.  (Two per block, for launches with blocks to spare,
+  // was measured behind a switch since removed: round 6 re-ran the A/B at the
+  // bench's prover shape (384 x 32 in flight, 8 queues): proofs/s equal
+  // (363-365 K vs 364-366 K), but one MSM per block issues more (k_dt_msm VALU
+  // issue 0.359 vs 0.314, wait_any 0.368 vs 0.456) and misses the UTCL1 less
+  // (5.2 % vs 8.3 % of requests); profiles/r06_dt_pair_ab.txt,
+  // r06_tlb_prover.json)
   ctx_work(ctx, "msm_terms", T);
   ctx_work(ctx, "madds", (uint64_t)T * dg.W);
   ctx_work(ctx, "padds", (uint64_t)M * (nt - 1));
@@ -944,9 +909,8 @@ static int msm_multi_dt_dev(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t
   ctx_work(ctx, "dt_launches", 1);
   {
     ProfScope ps(ctx, "msm_direct");
-    hipLaunchKernelGGL(k_dt_msm, dim3((M + segs - 1) / segs), dim3(segs * nt), (size_t)segs * nt * P3_BYTES,
-                       ctx->stream, pts.dt, dg, d_scal, d_pidx, (const uint32_t*)d_off, (uint32_t*)res, d_smap, segs,
-                       M);
+    hipLaunchKernelGGL(k_dt_msm, dim3(M), dim3(nt), (size_t)nt * P3_BYTES, ctx->stream, pts.dt, dg, d_scal, d_pidx,
+                       (const uint32_t*)d_off, (uint32_t*)res, d_smap, 1u, M);
   }
   BPP_TRY(ctx_check_launch(ctx, "k_dt_msm"));
   *d_res = (uint32_t*)res;

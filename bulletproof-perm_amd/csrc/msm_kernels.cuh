@@ -155,19 +155,15 @@ FE_INLINE uint32_t bucket_of(const uint32_t* __restrict__ boff, uint32_t nb, uin
   return lo;
 }
 
-#ifndef ACC_ADDR_SWAP
-#define ACC_ADDR_SWAP 1
-#endif
-#ifndef ACC_RESET_Z
-#define ACC_RESET_Z 1
-#endif
 // Table row of entry e for ge_madd_fg: for a negative digit (-Q = (y-x,
 // y+x, -2dxy)) the (y+x, y-x) fields are read swapped -- the swap is in the
 // per-lane load addresses, so it costs no instruction -- and the sign of
 // 2dxy is left to ge_madd_fg (F and G exchanged).  The two swapped fields sit
-// at 40-byte offsets, so they are read as 8-byte loads.  This replaces the
-// divergent negation branch below (a register swap and a carried fe_neg that
-// the wave ran in almost every iteration).
+// at 40-byte offsets, so they are read as 8-byte loads.  This replaced a
+// divergent negation branch (a register swap and a carried fe_neg that the
+// wave ran in almost every iteration; an uncarried -2dxy in that branch was
+// slower still: the 2^20 stream ran 1.09 vs 0.85 ms per MSM,
+// profiles/r04_acc_ab.txt).
 FE_INLINE ge_niels fetch_entry_sw(const uint32_t* __restrict__ tbl, const uint32_t* __restrict__ tbl1, uint32_t n0,
                                   uint32_t e) {
   const uint32_t pi = e & 0x7fffffffu;
@@ -217,33 +213,6 @@ FE_INLINE ge_p3 ge_madd_fg(const ge_p3& p, const ge_niels& q, bool neg) {
   return r;
 }
 
-// Table point of entry e, negated for a negative digit (in this kernel the
-// branch measured 1.5 % faster than ge_madd_signed's operand selects).
-FE_INLINE ge_niels fetch_entry(const uint32_t* __restrict__ tbl, const uint32_t* __restrict__ tbl1, uint32_t n0,
-                               uint32_t e) {
-#ifdef EXP_ACC_L2ROWS  // timing experiment only (wrong results): every gather from 1024 L2-resident rows
-  const uint32_t pi = e & 0x3ffu;
-#else
-  const uint32_t pi = e & 0x7fffffffu;
-#endif
-  ge_niels q = pi < n0 ? load_niels(tbl, pi) : load_niels(tbl1, pi - n0);
-#ifdef ACC_NEG_NC
-  // (A/B only) -2dxy uncarried (2p - limb < 2^27.6, a valid multiplier
-  // operand): 10 subtractions instead of a carried fe_neg, but the 2^20
-  // stream ran 1.09 vs 0.85 ms per MSM (accumulate 0.85 vs 0.67 ms; more
-  // spills around the branch), profiles/r04_acc_ab.txt
-  if (e & 0x80000000u) {
-    const fe t = q.ypx;
-    q.ypx = q.ymx;
-    q.ymx = t;
-    q.xy2d = fe_sub_nc(fe_zero(), q.xy2d);
-  }
-#else
-  if (e & 0x80000000u) q = ge_niels_neg(q);
-#endif
-  return q;
-}
-
 // A bucket spanning more than FIX_MAX chunks (bucket skew: the few buckets
 // of a narrow top window, equal scalars) is listed in heavy[1..] (count in
 // heavy[0]) by the lane where it starts and summed by a whole wave
@@ -251,12 +220,6 @@ FE_INLINE ge_niels fetch_entry(const uint32_t* __restrict__ tbl, const uint32_t*
 #define FIX_MAX 8
 #ifndef ACC_T
 #define ACC_T 256
-#endif
-#ifndef ACC_PARK_SPLIT
-#define ACC_PARK_SPLIT 1
-#endif
-#ifndef ACC_PARK_PRE
-#define ACC_PARK_PRE 1
 #endif
 
 // Balanced bucket accumulation: lane l owns entries [l*K, (l+1)*K) of the
@@ -285,120 +248,67 @@ __global__ void __launch_bounds__(ACC_T) ACC_ATTR k_msm_accumulate(const uint32_
   const uint32_t E = boff[nbuckets];
   const uint32_t i0 = l * K;
   const uint32_t i1 = min(i0 + K, E);
-#if ACC_PIECE_GLOBAL
-  // (A/B) every later piece to head[l], the owner folding this workgroup's
-  // from there after the barrier (a workgroup's waves share the CU's L1, so
-  // the barrier's release / acquire makes them visible): no LDS, so the
-  // occupancy is the VGPRs' (8 waves per SIMD at 64) instead of 4 workgroups
-  // of 40 KB per CU
-  auto park = [&](const ge_p3& v, uint32_t, uint32_t) { store_p3(head, l, v); };
-  const uint32_t* piece = head + (size_t)lane_first * P3_WORDS;
-#else
   __shared__ __attribute__((aligned(16))) uint32_t piece[ACC_T * P3_WORDS];
   // a later piece of a bucket that started in an earlier chunk: to LDS when
-  // its owner is in this workgroup and will fold it, else to head[l]
-#if ACC_PARK_SPLIT && ACC_PARK_PRE
+  // its owner is in this workgroup and will fold it, else to head[l].
   // Only a lane's FIRST run can park (its bucket started in an earlier
   // chunk), so where it parks is decided once before the loop (park_lds0)
   // instead of by two divisions by the runtime K inside the divergent close
   // path, which the whole wave executed whenever any lane closed its first
-  // run.  Two destinations as two stores (ds_write / global_store), as below.
+  // run.  The two destinations are two stores (ds_write / global_store)
+  // instead of one through a selected generic pointer, which compiled to 10
+  // flat_store_dwordx4 on every close: accumulate 0.715-0.735 vs 0.743-0.749
+  // ms at 2^20, three interleaved passes (profiles/r05_acc_park_ab.txt).
+  // (Every later piece to head[l] and no LDS, for the VGPRs' occupancy
+  // instead of 4 workgroups of 40 KB per CU, measured slower: DESIGN.md §4)
   bool park_lds0 = false;
-  auto park = [&](const ge_p3& v, uint32_t, uint32_t) {
+  auto park = [&](const ge_p3& v) {
     if (park_lds0)
       store_p3(piece, threadIdx.x, v);
     else
       store_p3(head, l, v);
   };
-#elif ACC_PARK_SPLIT
-  // the two destinations as two stores (ds_write / global_store) instead of
-  // one through a selected generic pointer, which compiled to 10
-  // flat_store_dwordx4 on every close: accumulate 0.715-0.735 vs 0.743-0.749
-  // ms at 2^20, three interleaved passes (profiles/r05_acc_park_ab.txt)
-  auto park = [&](const ge_p3& v, uint32_t s, uint32_t e) {
-    const uint32_t l0 = s / K;
-    if ((((e - 1) / K) - l0) < FIX_MAX && l0 >= lane_first)
-      store_p3(piece, threadIdx.x, v);
-    else
-      store_p3(head, l, v);
-  };
-#else
-  auto park = [&](const ge_p3& v, uint32_t s, uint32_t e) {
-    const uint32_t l0 = s / K;
-    uint32_t* dst = ((((e - 1) / K) - l0) < FIX_MAX && l0 >= lane_first) ? piece + threadIdx.x * P3_WORDS
-                                                                           : head + (size_t)l * P3_WORDS;
-    store_p3(dst, 0, v);
-  };
-#endif
-#endif
   bool owner = false;
   uint32_t b = 0, bstart = 0, bend = 0;
   // a bucket is heavy when it ends FIX_MAX or more lanes past this one:
   // ((bend - 1) / K) - l >= FIX_MAX  <=>  bend - 1 >= (l + FIX_MAX) K (no
   // division by the runtime K in the loop's bucket-close path: accumulate
   // 0.668-0.671 vs 0.682-0.693 ms at 2^20, three interleaved passes,
-  // profiles/r04_acc_ab.txt; ACC_HEAVY_DIV = the division, A/B)
+  // profiles/r04_acc_ab.txt)
   const uint32_t heavy_lim = (l + FIX_MAX) * K;
   ge_p3 acc = ge_identity();
   if (i0 < E) {
     b = bucket_of(boff, nbuckets, i0);
     bstart = boff[b];
     bend = boff[b + 1];
-#if ACC_PARK_SPLIT && ACC_PARK_PRE && !ACC_PIECE_GLOBAL
     if (bstart < i0) {
       const uint32_t l0 = bstart / K;
       park_lds0 = (((bend - 1) / K) - l0) < FIX_MAX && l0 >= lane_first;
     }
-#endif
     // the lane where a bucket starts lists it if it is heavy
-#ifndef ACC_HEAVY_DIV
     if (bstart == i0 && bend - 1 >= heavy_lim) heavy[1 + atomicAdd(&heavy[0], 1u)] = b;
-#else
-    if (bstart == i0 && ((bend - 1) / K) - l >= FIX_MAX) heavy[1 + atomicAdd(&heavy[0], 1u)] = b;
-#endif
     // entries are read 4 at a time (one 16-B load; K is a multiple of 4 and
     // the array is padded): a lane's chunk is contiguous, so per-entry 4-B
     // loads touch the same 128-B line K times across a long loop and
     // re-fetch it once the table gathers have evicted it
     uint4 e4 = make_uint4(0, 0, 0, 0);
-#ifndef EXP_ACC_BOFF_CHAIN
     // end of bucket b + 1, loaded one bucket ahead: when b closes, the next
     // bucket (almost always non-empty: ~32 entries each at 2^20) starts at
     // bend and ends at nbend, so the wave does not wait on dependent boff
     // loads in the iteration that closes a run
     uint32_t nbend = boff[min(b + 2, nbuckets)];
-#endif
-#if ACC_PREFETCH
-    // (A/B) one entry ahead: the next entry's table row is requested before
-    // this entry's mixed addition, so its load latency hides behind ~5 K
-    // cycles of arithmetic instead of stalling the next iteration
-    e4 = *reinterpret_cast<const uint4*>(entries + i0);
-    uint32_t e_next = e4.x;
-    ge_niels q_next = fetch_entry_sw(tbl, tbl1, n0, e_next);
-#endif
+    // (requesting the next entry's table row one entry ahead measured slower:
+    // DESIGN.md §4)
     for (uint32_t i = i0; i < i1; ++i) {
-#if ACC_PREFETCH
-      const uint32_t e = e_next;
-      const ge_niels q_cur = q_next;
-      if (i + 1 < i1) {
-        const uint32_t j = i + 1 - i0;
-        if ((j & 3u) == 0) e4 = *reinterpret_cast<const uint4*>(entries + i + 1);
-        const uint32_t jq = j & 3u;
-        e_next = jq == 0 ? e4.x : jq == 1 ? e4.y : jq == 2 ? e4.z : e4.w;
-        q_next = fetch_entry_sw(tbl, tbl1, n0, e_next);
-      }
-#else
       if (((i - i0) & 3u) == 0) e4 = *reinterpret_cast<const uint4*>(entries + i);
       const uint32_t q = (i - i0) & 3u;
       const uint32_t e = q == 0 ? e4.x : q == 1 ? e4.y : q == 2 ? e4.z : e4.w;
-#endif
       if (i == bend) {  // close the run of bucket b
         if (bstart >= i0) {
           store_p3(bsum, b, acc);  // whole bucket inside the chunk
         } else {
-          park(acc, bstart, bend);  // first run, bucket started earlier
+          park(acc);  // first run, bucket started earlier
         }
-#ifndef EXP_ACC_BOFF_CHAIN
         if (nbend > i) {  // bucket b + 1 is non-empty
           ++b;
           bstart = i;
@@ -409,39 +319,20 @@ __global__ void __launch_bounds__(ACC_T) ACC_ATTR k_msm_accumulate(const uint32_
           bend = boff[b + 1];
         }
         nbend = boff[min(b + 2, nbuckets)];
-#else
-        do { ++b; } while (boff[b + 1] <= i);
-        bstart = boff[b];
-        bend = boff[b + 1];
-#endif
-#ifndef ACC_HEAVY_DIV
         if (bend - 1 >= heavy_lim) heavy[1 + atomicAdd(&heavy[0], 1u)] = b;
-#else
-        if (((bend - 1) / K) - l >= FIX_MAX) heavy[1 + atomicAdd(&heavy[0], 1u)] = b;
-#endif
-#if ACC_RESET_Z
         // the identity as (0 : Z : Z : 0) with the accumulator's own Z (never
         // zero): 30 moves instead of materialising (0 : 1 : 1 : 0)'s 40 words
         acc.Y = acc.Z;
         acc.X = fe_zero();
         acc.T = fe_zero();
-#else
-        acc = ge_identity();
-#endif
       }
-#if ACC_PREFETCH
-      acc = ge_madd_fg(acc, q_cur, (e >> 31) != 0);
-#elif ACC_ADDR_SWAP
       acc = ge_madd_fg(acc, fetch_entry_sw(tbl, tbl1, n0, e), (e >> 31) != 0);
-#else
-      acc = ge_madd(acc, fetch_entry(tbl, tbl1, n0, e));
-#endif
     }
     // last run [max(bstart, i0), i1)
     if (bstart >= i0 && bend <= i1) {
       store_p3(bsum, b, acc);
     } else if (bstart < i0) {  // single run crossing both borders
-      park(acc, bstart, bend);
+      park(acc);
     } else {  // bucket starts here and continues: its partial waits in
       owner = true;  // tail[l] (holding it in registers across the barrier
       store_p3(tail, l, acc);  // costs ~20 VGPRs in the main loop)
@@ -1073,9 +964,14 @@ __global__ void __launch_bounds__(RS_FT) k_rsort_fine(const uint32_t* __restrict
 
 // smap (optional): term t's scalar is scalars[smap[t]] / 2 mod l (the
 // prover's halved, compacted A_I/A_O/S terms without a gather pass).
-// segs MSMs per block (1 or 2; M = the launch's MSM count): lanes
+// segs MSMs per block (M = the launch's MSM count): lanes
 // [j nt / segs, (j + 1) nt / segs) walk MSM blockIdx.x * segs + j, and the
 // segments' block trees run side by side (their narrow levels share waves).
+// The host always passes 1: two per block measured equal in proofs/s and
+// worse in issue and UTCL1 misses (msm.hip msm_multi_dt_dev).  The parameter
+// stays: the kernel without it measured 363.4 K against 364.8 K proofs/s
+// (medians of three interleaved passes at 384 x 32 in flight), outside the
+// passes' own spread, so the shipped kernel is kept as it was.
 __global__ void __launch_bounds__(DT_NT_MAX) k_dt_msm(const uint32_t* __restrict__ dt, DtGeom dg,
                                                     const uint32_t* __restrict__ scalars,
                                                     const uint32_t* __restrict__ pidx, const uint32_t* __restrict__ off,
@@ -1087,10 +983,6 @@ __global__ void __launch_bounds__(DT_NT_MAX) k_dt_msm(const uint32_t* __restrict
   const uint32_t m0 = blockIdx.x * segs, m = m0 + sg;
   const DtLane ln = DtLane::make(dg, lt % dg.W);
   const uint32_t tg = lt / dg.W;
-#ifdef EXP_DT_NOWALK  // timing experiment only (wrong results): no walk, no tree
-  if (lt == 0 && m < M) store_p3(out_p3, m, ge_identity());
-  return;
-#endif
   const ge_p3 acc = tg < TG && m < M ? dt_walk(dt, dg, ln, off[m] + tg, off[m + 1], TG,
                                                [&](uint32_t t, uint32_t s[8], uint32_t& gen) {
                                                  if (smap) {

@@ -348,11 +348,7 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
   // A small batch is a latency chain (a config-4 job's sub-batches): its
   // syncs spin before sleeping; the throughput shape (384 proofs, 32 in
   // flight) keeps the sleeping wait that frees the host cores
-  // (BPP_SPIN_BATCH = the largest batch that spins, 0 = none)
-  static const size_t spin_batch = [] {
-    const char* e = getenv("BPP_SPIN_BATCH");
-    return e ? (size_t)std::max(0, atoi(e)) : (size_t)128;
-  }();
+  constexpr size_t spin_batch = 128;  // the largest batch that spins
   SyncSpin spin(ctx, P <= spin_batch ? 300u : ctx->sync_spin_us);
   // (a plain reference: pool workers must reach THIS thread's states, a
   // thread_local named inside their lambdas would be their own)
@@ -434,11 +430,6 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
         memcpy(stage + i * tlen, tm, tlen);
         memcpy(pis + i * 4 * (size_t)k, S[i]->d.pi.data(), 4 * (size_t)k);
       }
-#ifdef EXP_HOST_BURN_US  // timing experiment only: extra host CPU per proof
-      const auto t0 = std::chrono::steady_clock::now();
-      while (std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(8 * EXP_HOST_BURN_US)) {
-      }
-#endif
     });
     BPP_TRY(ctx_h2d_staged(ctx, dst, stage, in_bytes));  // (pis follows the templates)
     // (the V commitments' inputs in the same launch: values 1..k and pi + 1,
@@ -939,9 +930,10 @@ struct bpp_verify_job {
   bool dev = false;
   bpp_ctx* dctx = nullptr;
   uint64_t dgen = 0;
-  // sliced device job (bpp_perm_verify_begin_dev_slice): all `count` proofs
-  // uploaded and their points decompressed, only [rfirst, rfirst + rcount)
-  // replayed (records and rs of that slice); a whole job has rcount = count
+  // sliced device job: all `count` proofs uploaded and their points
+  // decompressed, only [rfirst, rfirst + rcount) replayed (records and rs of
+  // that slice); a whole job has rcount = count.  (The sharded path,
+  // bpp_perm_verify_partial_sharded, takes one whole job per slice.)
   size_t rfirst = 0, rcount = 0;
 };
 
@@ -1150,7 +1142,6 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
   const size_t plen = perm::proof_len(C.k), vbytes = (size_t)C.m * 32, npts = count * J.npt;
   bpp_ctx* kid = nullptr;
   BPP_TRY(ctx_child(ctx, VJ_CHILD, &kid));
-  if (!ctx->vj_ev_in) BPP_HIP(hipEventCreateWithFlags(&ctx->vj_ev_in, hipEventDisableTiming));
   if (!ctx->vj_ev_dec) BPP_HIP(hipEventCreateWithFlags(&ctx->vj_ev_dec, hipEventDisableTiming));
   // (the previous job's decompression may still read "vj_in")
   if (ctx->vj_dec_pending) BPP_HIP(hipStreamWaitEvent(ctx->stream, ctx->vj_ev_dec, 0));
@@ -1163,157 +1154,38 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
   BPP_TRY(ctx_ws(ctx, "vj_x", npts * MSM_NIELS_WORDS * 4, &d_x));
   BPP_TRY(ctx_ws(ctx, "vj_dbad", 8, &d_dbad));
   BPP_HIP(hipMemsetAsync(d_dbad, 0xff, 8, ctx->stream));
-  // decompression order (BPP_VERIFY_DEC, A/B): 0 = per upload chunk, beside
-  // the upload and then the replay, 1 = launched after the replay's launch
-  // (beside it), 2 = after the replay completes (it then overlaps the host
-  // weights and k_verify_scalars instead)
-  static const int dec_order = [] {
-    const char* e = getenv("BPP_VERIFY_DEC");
-    return e ? atoi(e) : 0;
-  }();
-  auto launch_dec = [&]() -> int {
-    BPP_HIP(hipEventRecord(ctx->vj_ev_in, ctx->stream));
-    BPP_HIP(hipStreamWaitEvent(kid->stream, ctx->vj_ev_in, 0));
-    BPP_TRY(verify_decompress_dev(kid, C, (uint32_t)count, d_pf, d_V, (uint32_t*)d_x, (unsigned long long*)d_dbad));
-    BPP_HIP(hipEventRecord(ctx->vj_ev_dec, kid->stream));
-    ctx->vj_dec_pending = true;
-    return BPP_OK;
-  };
-  // BPP_VERIFY_SPLIT=1 (whole jobs): the V bytes of every chunk go up first
-  // and the transcripts run their V part (2k V appends, x_perm, V_2k: ~60 %
-  // of a transcript's permutations) on a second child stream as soon as the
-  // last V byte lands, while the proof bytes are still being copied; the
-  // proof part follows the last copy.  Each chunk's V points and then its
-  // proof points are decompressed as they land.
-  static const bool split_env = [] {
-    const char* e = getenv("BPP_VERIFY_SPLIT");
-    return e && atoi(e) != 0;
-  }();
-  const bool split = split_env && dec_order == 0 && rfirst == 0 && rcount == count && count >= 256;
-  uint32_t* d_stt = nullptr;
-  uint32_t* h_init = nullptr;  // the shared transcript prefix, read in place (zero copy)
-  ReplayEarly early{};
-  bool use_early = false;
-  if (split) {
-    void* d = nullptr;
-    BPP_TRY(ctx_ws(ctx, "vj_stt", count * 52 * 4, &d));
-    d_stt = (uint32_t*)d;
-  }
   {
     HostScope hs(ctx, "verify_upload");
-    if (split) {
-      bpp_ctx* kv = nullptr;
-      BPP_TRY(ctx_child(ctx, VJ_CHILD + 1, &kv));
-      {
-        uint32_t init[52];
-        verify_init_state(C, label, llen, init);
-        BPP_TRY(ctx_zc_in(ctx, "vj_init", init, sizeof init, &h_init));
-      }
-      static const size_t nchunk_env = [] {
-        const char* e = getenv("BPP_VERIFY_CHUNKS");
-        return (size_t)std::max(1, e ? atoi(e) : 4);
-      }();
-      const size_t nchunk = std::min(nchunk_env, std::max<size_t>(1, count / 256));
-      for (auto* evs : {&ctx->vj_ev_chunk, &ctx->vj_ev_chunk2})
-        while (evs->size() < nchunk) {
-          hipEvent_t e = nullptr;
-          BPP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          evs->push_back(e);
-        }
-      if (!ctx->vj_ev_vrep) BPP_HIP(hipEventCreateWithFlags(&ctx->vj_ev_vrep, hipEventDisableTiming));
-      const bool direct = host_is_pinned(proofs, count * plen) && host_is_pinned(V, count * vbytes);
-      uint8_t* stg = nullptr;
-      if (!direct) BPP_TRY(ctx_h2d_stage(ctx, count * (plen + vbytes), &stg));
-      auto up = [&](size_t off, const uint8_t* src, size_t n) -> int {
-        if (direct) {
-          BPP_HIP(hipMemcpyAsync((uint8_t*)d_in + off, src, n, hipMemcpyHostToDevice, ctx->stream));
-        } else {
-          ctx_stage_copy(stg + off, src, n);
-          BPP_TRY(ctx_h2d_staged(ctx, (uint8_t*)d_in + off, stg + off, n));
-        }
-        return BPP_OK;
-      };
-      const uint32_t m = C.m, npt = (uint32_t)J.npt;
-      // (the V parts as ONE launch once every V byte is up: a transcript is a
-      // latency chain, so per-chunk launches in a row on one stream cost a
-      // chain each -- 4 x 185 us, measured)
-      for (size_t q = 0; q < nchunk; ++q) {  // V bytes, V points
-        const size_t p0 = count * q / nchunk, p1 = count * (q + 1) / nchunk;
-        BPP_TRY(up(count * plen + p0 * vbytes, V + p0 * vbytes, (p1 - p0) * vbytes));
-        BPP_HIP(hipEventRecord(ctx->vj_ev_chunk[q], ctx->stream));
-        BPP_HIP(hipStreamWaitEvent(kid->stream, ctx->vj_ev_chunk[q], 0));
-        BPP_TRY(verify_decompress_dev(kid, C, (uint32_t)count, d_pf, d_V, (uint32_t*)d_x, (unsigned long long*)d_dbad,
-                                      (uint32_t)p0, (uint32_t)p1, 0, m));
-      }
-      BPP_HIP(hipStreamWaitEvent(kv->stream, ctx->vj_ev_chunk[nchunk - 1], 0));
-      BPP_TRY(verify_replay_v_dev(ctx, kv->stream, C, 0, (uint32_t)count, (uint32_t)count, h_init, d_V, d_stt));
-      BPP_HIP(hipEventRecord(ctx->vj_ev_vrep, kv->stream));
-      for (size_t q = 0; q < nchunk; ++q) {  // proof bytes, proof points
-        const size_t p0 = count * q / nchunk, p1 = count * (q + 1) / nchunk;
-        BPP_TRY(up(p0 * plen, proofs + p0 * plen, (p1 - p0) * plen));
-        BPP_HIP(hipEventRecord(ctx->vj_ev_chunk2[q], ctx->stream));
-        BPP_HIP(hipStreamWaitEvent(kid->stream, ctx->vj_ev_chunk2[q], 0));
-        BPP_TRY(verify_decompress_dev(kid, C, (uint32_t)count, d_pf, d_V, (uint32_t*)d_x, (unsigned long long*)d_dbad,
-                                      (uint32_t)p0, (uint32_t)p1, m, npt - m));
-      }
-      BPP_HIP(hipEventRecord(ctx->vj_ev_dec, kid->stream));
-      ctx->vj_dec_pending = true;
-      BPP_HIP(hipStreamWaitEvent(ctx->stream, ctx->vj_ev_vrep, 0));
-    } else if (dec_order == 0) {
+    {
       // The proofs and V go up in chunks of proofs (each chunk's proof bytes
       // and V bytes to their places in the [proofs][V] layout), and each
       // chunk's points are decompressed on the child stream as soon as its
       // copies land, so the decompression -- the longest stage beside the
       // replay -- starts while later chunks are still being staged and copied
-      // (BPP_VERIFY_CHUNKS, default 4; 1 = one decompression after the whole
-      // upload).
-      static const size_t nchunk_env = [] {
-        const char* e = getenv("BPP_VERIFY_CHUNKS");
-        return (size_t)std::max(1, e ? atoi(e) : 4);
-      }();
+      // (at most 4 chunks).
       // (chunks of >= 1024 proofs: a decompression launch is a per-lane
       // latency chain of ~50-80 us however few points it has, and the
       // launches of one stream run in turn -- a 512-proof slice in two
       // chunks waited 0.32 ms for its points, tools/shard_model.py)
-      const size_t nchunk = std::min(nchunk_env, std::max<size_t>(1, count / 1024));
+      const size_t nchunk = std::min<size_t>(4, std::max<size_t>(1, count / 1024));
       while (ctx->vj_ev_chunk.size() < nchunk) {
         hipEvent_t e = nullptr;
         BPP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         ctx->vj_ev_chunk.push_back(e);
       }
-      // proofs and V already in pinned host memory (bpp_host_alloc; memory
-      // the caller registered itself with BPP_PIN_QUERY=1) go up by DMA from
-      // where they are; pageable buffers are staged through the pinned arena
-      // first (the host copy then paces the upload)
+      // proofs and V already in pinned host memory (bpp_host_alloc, or memory
+      // the caller registered itself) go up by DMA from where they are;
+      // pageable buffers are staged through the pinned arena first (the host
+      // copy then paces the upload)
       const bool direct = host_is_pinned(proofs, count * plen) && host_is_pinned(V, count * vbytes);
       uint8_t* stg = nullptr;
       if (!direct) BPP_TRY(ctx_h2d_stage(ctx, count * (plen + vbytes), &stg));
-      static const size_t stage_piece = [] {  // (BPP_VERIFY_PIECE_KB, A/B; 0 = whole parts, the default)
-        const char* e = getenv("BPP_VERIFY_PIECE_KB");
-        const long kb = e ? atol(e) : 0;
-        return kb > 0 ? (size_t)kb << 10 : SIZE_MAX;
-      }();
-      // BPP_VERIFY_EARLY=1 (A/B, off): the first nchunk - 1 chunks'
-      // transcripts start on a side stream once their bytes are up, beside
-      // the last chunk's upload.  It does not pay: a replay launch is a
+      // (The first nchunk - 1 chunks' transcripts started on a side stream
+      // once their bytes were up, beside the last chunk's upload, did not pay
+      // when measured behind a switch since removed: a replay launch is a
       // latency chain of ~0.26-0.28 ms however few transcripts it holds, so
-      // the last chunk's replay ends when the whole one did (1.84-1.89 vs
+      // the last chunk's replay ends when the whole one did: 1.84-1.89 vs
       // 1.80-1.86 ms per batch, profiles/r05_verify_ab.txt)
-      static const bool early_env = [] {
-        const char* e = getenv("BPP_VERIFY_EARLY");
-        return e && atoi(e) != 0;
-      }();
-      if (early_env && nchunk >= 2 && rfirst == 0 && rcount == count) {
-        bpp_ctx* kv = nullptr;
-        BPP_TRY(ctx_child(ctx, VJ_CHILD + 1, &kv));
-        if (!ctx->vj_ev_vrep) BPP_HIP(hipEventCreateWithFlags(&ctx->vj_ev_vrep, hipEventDisableTiming));
-        early = ReplayEarly{kv->stream, ctx->vj_ev_chunk[nchunk - 2], ctx->vj_ev_vrep,
-                            (uint32_t)(count * (nchunk - 1) / nchunk)};
-        use_early = true;
-        uint32_t init[52];
-        verify_init_state(C, label, llen, init);
-        BPP_TRY(ctx_zc_in(ctx, "vj_init", init, sizeof init, &h_init));
-      }
       for (size_t q = 0; q < nchunk; ++q) {
         const size_t p0 = count * q / nchunk, p1 = count * (q + 1) / nchunk;
         const size_t po = p0 * plen, pn = (p1 - p0) * plen, vo = count * plen + p0 * vbytes, vn = (p1 - p0) * vbytes;
@@ -1321,15 +1193,11 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
           BPP_HIP(hipMemcpyAsync((uint8_t*)d_in + po, proofs + po, pn, hipMemcpyHostToDevice, ctx->stream));
           BPP_HIP(hipMemcpyAsync((uint8_t*)d_in + vo, V + p0 * vbytes, vn, hipMemcpyHostToDevice, ctx->stream));
         } else {
-          // (in pieces, each piece's DMA behind its host copy, with
-          // BPP_VERIFY_PIECE_KB: measured slower, r05_verify_ab.txt)
+          // (whole parts: in pieces, each piece's DMA behind its host copy,
+          // measured slower, r05_verify_ab.txt)
           auto staged = [&](size_t o, const uint8_t* src, size_t n) -> int {
-            for (size_t a = 0; a < n; a += stage_piece) {
-              const size_t b = std::min(n, a + stage_piece);
-              ctx_stage_copy(stg + o + a, src + a, b - a);
-              BPP_TRY(ctx_h2d_staged(ctx, (uint8_t*)d_in + o + a, stg + o + a, b - a));
-            }
-            return BPP_OK;
+            ctx_stage_copy(stg + o, src, n);
+            return ctx_h2d_staged(ctx, (uint8_t*)d_in + o, stg + o, n);
           };
           BPP_TRY(staged(po, proofs + po, pn));
           BPP_TRY(staged(vo, V + p0 * vbytes, vn));
@@ -1338,19 +1206,15 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
         BPP_HIP(hipStreamWaitEvent(kid->stream, ctx->vj_ev_chunk[q], 0));
         BPP_TRY(verify_decompress_dev(kid, C, (uint32_t)count, d_pf, d_V, (uint32_t*)d_x,
                                       (unsigned long long*)d_dbad, (uint32_t)p0, (uint32_t)p1));
-        if (use_early && q + 2 == nchunk)
-          BPP_TRY(verify_replay_early_dev(ctx, C, (uint32_t)count, h_init, d_pf, d_V, early));
       }
       BPP_HIP(hipEventRecord(ctx->vj_ev_dec, kid->stream));
       ctx->vj_dec_pending = true;
-    } else {
-      BPP_TRY(ctx_h2d2(ctx, d_in, proofs, count * plen, V, count * vbytes));
     }
   }
   HostScope hs(ctx, "verify_replay");
-  if (dec_order != 0 && !rcount) BPP_TRY(launch_dec());
   uint32_t *h_r = nullptr, *h_bad = nullptr;
-  if (!h_init) {
+  uint32_t* h_init = nullptr;  // the shared transcript prefix, read in place (zero copy)
+  {
     uint32_t init[52];
     verify_init_state(C, label, llen, init);
     BPP_TRY(ctx_zc_in(ctx, "vj_init", init, sizeof init, &h_init));
@@ -1358,20 +1222,8 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
   if (!rcount) return ctx_sync(ctx);
   BPP_TRY(ctx_zc_out(ctx, "vj_r", rcount * 32, &h_r));
   BPP_TRY(ctx_zc_out(ctx, "vj_bad", rcount * 4, &h_bad));
-  if (dec_order == 1) {  // (the event is recorded before the replay: the decompression waits for the upload only)
-    BPP_HIP(hipEventRecord(ctx->vj_ev_in, ctx->stream));
-  }
   BPP_TRY(verify_replay_dev(ctx, C, (uint32_t)rcount, h_init, d_pf + rfirst * (plen / 4),
-                            d_V + rfirst * (vbytes / 4), (uint32_t*)d_rec, h_r, h_bad, d_stt,
-                            use_early ? &early : nullptr));
-  if (dec_order == 1) {
-    BPP_HIP(hipStreamWaitEvent(kid->stream, ctx->vj_ev_in, 0));
-    BPP_TRY(verify_decompress_dev(kid, C, (uint32_t)count, d_pf, d_V, (uint32_t*)d_x, (unsigned long long*)d_dbad));
-    BPP_HIP(hipEventRecord(ctx->vj_ev_dec, kid->stream));
-    ctx->vj_dec_pending = true;
-  } else if (dec_order == 2) {
-    BPP_TRY(launch_dec());
-  }
+                            d_V + rfirst * (vbytes / 4), (uint32_t*)d_rec, h_r, h_bad));
   if (!sync) {
     J.bad_h = h_bad;
     J.rs.clear();
@@ -1385,7 +1237,8 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
   return BPP_OK;
 }
 
-// A sliced job's scalars (bpp_perm_verify_slice_scalars): the slice's
+// A job's scalars as one slice of a sharded batch
+// (bpp_perm_verify_slice_scalars_at): the slice's
 // proofs weighted by perm::batch_weight(seed, rfirst + p, r_p), the generator
 // scalars summed over the slice and the slice's proof-point scalars ->
 // d_out = [NG | rcount x npt] x 32 B (device memory).
@@ -1861,15 +1714,9 @@ int bpp_perm_verify_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t co
   return bpp_guard(ctx, [&]() -> int {
     if (!ctx || !G || ((!proofs || !V) && count) || (!label && llen) || k < 2 || k > (1u << 20)) return BPP_ERR_ARG;
     if (!count) return BPP_OK;
-    // (BPP_VERIFY_SPIN_US > 0: its syncs spin before sleeping, an A/B
-    // switch, off: the verifier's waits already spin where they sit on the
-    // critical path (ctx_sync_latency), and 300 us measured within noise,
-    // profiles/r06_sync_spin_ab.txt)
-    static const unsigned vspin = [] {
-      const char* e = getenv("BPP_VERIFY_SPIN_US");
-      return e ? (unsigned)std::max(0, atoi(e)) : 0u;
-    }();
-    SyncSpin spin(ctx, vspin ? vspin : ctx->sync_spin_us);
+    // (the context's own spin: the verifier's waits already spin where they
+    // sit on the critical path (ctx_sync_latency), and syncs that spin 300 us
+    // before sleeping measured within noise, profiles/r06_sync_spin_ab.txt)
     BPP_HIP(hipSetDevice(ctx->device));
     const perm::Circuit C = perm::build(k);
     return verify_batch(ctx, G, C, label, llen, count, proofs, V);

@@ -182,24 +182,18 @@ __global__ void __launch_bounds__(POLY_T) k_poly_coef(uint32_t n_p, uint32_t m, 
       yhi = sc_mont(yhi, ystep);
       yihi = sc_mont(yihi, yistep);
     }
-#ifdef EXP_P_NOCS
-    const sc zWL = aL, zWR = aR, zWO = l2;
-#else
     const sc zWL = col_sum(cp, ce, i, zp), zWR = col_sum(cp + (n_p + 1), ce, i, zp),
              zWO = col_sum(cp + 2 * (n_p + 1), ce, i, zp);
-#endif
     const sc l1 = sc_add(aL, sc_mont(zWR, yip));
     const sc r0 = sc_sub(zWO, yp);
     const sc r1 = sc_add(sc_mont(aR, yp), zWL);
     const sc r3 = sc_mont(sR, yp);
-#ifndef EXP_P_NOT
     t[0] = sc_add(t[0], sc_mont(l1, r0));
     t[1] = sc_add(t[1], sc_add(sc_mont(l1, r1), sc_mont(l2, r0)));
     t[2] = sc_add(t[2], sc_add(sc_mont(l2, r1), sc_mont(l3, r0)));
     t[3] = sc_add(t[3], sc_add(sc_mont(l1, r3), sc_mont(l3, r1)));
     t[4] = sc_add(t[4], sc_mont(l2, r3));
     t[5] = sc_add(t[5], sc_mont(l3, r3));
-#endif
     uint32_t* v = vec + ((size_t)p * n_p + i) * POLY_SLOTS * 8;
     sc_store(v + 0, l1);
     sc_store(v + 8, r0);
@@ -214,7 +208,6 @@ __global__ void __launch_bounds__(POLY_T) k_poly_coef(uint32_t n_p, uint32_t m, 
   // the sum in the Montgomery domain of the other six
   const uint32_t* cpv = cp + 3 * (n_p + 1);
   const uint32_t* gam = gamma + 8 * (size_t)p * m;
-#ifndef EXP_P_NOV
   for (uint32_t j = threadIdx.x; j < m; j += blockDim.x)
     if (cpv[j + 1] - cpv[j] <= HEAVY_COL) t[6] = sc_add(t[6], sc_mont(col_sum(cpv, ce, j, zp), sc_to_mont(sc_load(gam + 8 * j))));
   const uint32_t* heavy = cpv + m + 1;  // [count, columns...] (build_csr)
@@ -223,7 +216,6 @@ __global__ void __launch_bounds__(POLY_T) k_poly_coef(uint32_t n_p, uint32_t m, 
     const sc cs = col_sum_block(cpv, ce, j, zp, red);
     if (threadIdx.x == 0) t[6] = sc_add(t[6], sc_mont(cs, sc_to_mont(sc_load(gam + 8 * j))));
   }
-#endif
   sc_block_sum<POLY_NT>(t, red);
   if (threadIdx.x == 0)
     _Pragma("unroll") for (int j = 0; j < POLY_NT; ++j) sc_store(t_out + (POLY_NT * p + j) * 8, sc_from_mont(t[j]));

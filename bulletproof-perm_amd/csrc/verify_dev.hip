@@ -59,18 +59,16 @@ FE_INLINE bool w8_zero(const uint32_t w[8]) {
 #define RG_GS GRP_BLOCK
 #define RG_SCR_OFF GRP_SCR_OFF
 #endif
-// PH: 0 = the whole transcript; 1 = its V part (the 2k V appends, x_perm,
-// V_2k), the sponge left in stt[p] (52 words: state, pos, pos_begin); 2 =
-// the rest, from stt[p].  The split lets the V part of a chunk of proofs run
-// as soon as that chunk's V bytes land (verify_begin_dev, BPP_VERIFY_SPLIT),
-// while the proof bytes are still on their way.  Proofs [p0, p1) of a batch
-// of `total` (ch and okw indexed by batch proof; ch[total] is the pad).
-template <bool STAGED, int PH>
+// Proofs [p0, p1) of a batch of `total` (ch and okw indexed by batch proof;
+// ch[total] is the pad).  (The transcript in two launches -- its V part as
+// soon as the V bytes landed, the rest from the saved sponges -- was measured
+// behind a switch since removed and lost: profiles/r05_verify_ab.txt.)
+template <bool STAGED>
 __global__ void __launch_bounds__(64) k_verify_replay_g(uint32_t p0, uint32_t p1, uint32_t total, uint32_t k,
                                                         uint32_t lg, uint32_t n_p, const uint32_t* __restrict__ init,
                                                         const uint32_t* __restrict__ proofs, uint32_t pw,
                                                         const uint32_t* __restrict__ V, uint32_t* __restrict__ ch,
-                                                        uint32_t* __restrict__ okw, uint32_t* __restrict__ stt) {
+                                                        uint32_t* __restrict__ okw) {
   __shared__ __attribute__((aligned(16))) uint8_t sp[RG_GROUPS * RG_GS];
   extern __shared__ __attribute__((aligned(16))) uint32_t stage[];  // STAGED: [8][pw + 8 m]
   // the replay is a latency chain and the proof-point decompression runs
@@ -87,23 +85,22 @@ __global__ void __launch_bounds__(64) k_verify_replay_g(uint32_t p0, uint32_t p1
   t.gl = gl;
   t.leader = gl == GRP_LEADER;
   {
-    const uint32_t* src = PH == 2 ? stt + (size_t)p * 52 : init;
     uint32_t* d = reinterpret_cast<uint32_t*>(t.st);
-    for (uint32_t i = gl; i < 50; i += GRP_LANES) d[i] = src[i];
-    t.pos = src[50];
-    t.pos_begin = src[51];
+    for (uint32_t i = gl; i < 50; i += GRP_LANES) d[i] = init[i];
+    t.pos = init[50];
+    t.pos_begin = init[51];
   }
   const uint32_t* PV = nullptr;
   const uint32_t* PP = nullptr;
   if (STAGED) {
-    const uint32_t pwh = PH == 1 ? 0u : pw, vw = PH == 2 ? 0u : 8 * m;  // the words this phase reads
-    uint32_t* sg = stage + (size_t)g * (pwh + vw);
+    const uint32_t vw = 8 * m;
+    uint32_t* sg = stage + (size_t)g * (pw + vw);
     const uint4* sp4 = reinterpret_cast<const uint4*>(proofs + (size_t)p * pw);
-    for (uint32_t i = gl; i < pwh / 4; i += GRP_LANES) reinterpret_cast<uint4*>(sg)[i] = sp4[i];
+    for (uint32_t i = gl; i < pw / 4; i += GRP_LANES) reinterpret_cast<uint4*>(sg)[i] = sp4[i];
     const uint4* sv4 = reinterpret_cast<const uint4*>(V + (size_t)p * m * 8);
-    for (uint32_t i = gl; i < vw / 4; i += GRP_LANES) reinterpret_cast<uint4*>(sg + pwh)[i] = sv4[i];
+    for (uint32_t i = gl; i < vw / 4; i += GRP_LANES) reinterpret_cast<uint4*>(sg + pw)[i] = sv4[i];
     PP = sg;
-    PV = sg + pwh;
+    PV = sg + pw;
   } else {
     PP = proofs + (size_t)p * pw;
     PV = V + (size_t)p * m * 8;
@@ -118,27 +115,13 @@ __global__ void __launch_bounds__(64) k_verify_replay_g(uint32_t p0, uint32_t p1
   uint32_t* CH = ch + (size_t)(live ? p : total) * nch * 16;
   uint32_t w[8];
   bool ok = true;
-  if (PH != 2) {
-    for (uint32_t j = 0; j < 2 * k; ++j) {
-      ld8(PV + 8 * j, w);
-      APPEND32("V", 1, w, PV + 8 * j);
-    }
-    t.challenge64_to("x_perm", 6, CH, true);
-    ld8(PV + 16 * k, w);
-    APPEND32("V", 1, w, PV + 16 * k);
+  for (uint32_t j = 0; j < 2 * k; ++j) {
+    ld8(PV + 8 * j, w);
+    APPEND32("V", 1, w, PV + 8 * j);
   }
-  if (PH == 1) {
-    if (live) {
-      const uint32_t* d = reinterpret_cast<const uint32_t*>(t.st);
-      uint32_t* o = stt + (size_t)p * 52;
-      for (uint32_t i = gl; i < 50; i += GRP_LANES) o[i] = d[i];
-      if (t.leader) {
-        o[50] = t.pos;
-        o[51] = t.pos_begin;
-      }
-    }
-    return;
-  }
+  t.challenge64_to("x_perm", 6, CH, true);
+  ld8(PV + 16 * k, w);
+  APPEND32("V", 1, w, PV + 16 * k);
   ld8(PP, w);
   ok &= !w8_zero(w);
   APPEND32("A_I", 3, w, PP);
@@ -268,9 +251,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VD_WPE)
 k_verify_decompress(size_t i0, size_t i1, uint32_t jlo, uint32_t jn, uint32_t m, uint32_t lg, uint32_t npt,
                     const uint32_t* __restrict__ proofs, uint32_t pw, const uint32_t* __restrict__ V,
                     uint32_t* __restrict__ tbl, unsigned long long* __restrict__ bad) {
-#ifdef VD_PRIO  // (A/B: issue priority against the expansion's s_setprio(2))
-  __builtin_amdgcn_s_setprio(VD_PRIO);
-#endif
   // lane -> (proof p, point j = jlo + j' with j' < jn): the V points (jlo =
   // 0, jn = m) or the proof's own points (jlo = m) can go separately
   const size_t t = i0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -306,51 +286,8 @@ void verify_init_state(const perm::Circuit& C, const uint8_t* label, size_t llen
   out[51] = tr.s.pos_begin;
 }
 
-template <int PH>
-static void launch_replay(hipStream_t st, const perm::Circuit& C, uint32_t p0, uint32_t p1, uint32_t total,
-                          const uint32_t* d_init, const uint32_t* d_proofs, const uint32_t* d_V, uint32_t* d_ch,
-                          uint32_t* d_ok, uint32_t* d_stt) {
-  const uint32_t pw = (uint32_t)(perm::proof_len(C.k) / 4);
-  // the bytes the phase reads, of the block's groups, staged in LDS while they fit
-  const size_t words = (PH == 1 ? 0 : pw) + (PH == 2 ? 0 : 8 * (size_t)C.m);
-  const size_t stage = (size_t)RG_GROUPS * words * 4;
-  if (stage <= 48 * 1024)
-    hipLaunchKernelGGL((k_verify_replay_g<true, PH>), dim3(grid_for(p1 - p0, RG_GROUPS)), dim3(64), stage, st,
-                       p0, p1, total, C.k, C.lg, C.n_p, d_init, d_proofs, pw, d_V, d_ch, d_ok, d_stt);
-  else
-    hipLaunchKernelGGL((k_verify_replay_g<false, PH>), dim3(grid_for(p1 - p0, RG_GROUPS)), dim3(64), 0, st,
-                       p0, p1, total, C.k, C.lg, C.n_p, d_init, d_proofs, pw, d_V, d_ch, d_ok, d_stt);
-}
-
-int verify_replay_v_dev(bpp_ctx* ctx, hipStream_t st, const perm::Circuit& C, uint32_t p0, uint32_t p1,
-                        uint32_t total, const uint32_t* d_init, const uint32_t* d_V, uint32_t* d_stt) {
-  if (p0 >= p1) return BPP_OK;
-  const uint32_t nch = 6 + C.lg;
-  void *d_ch = nullptr, *d_ok = nullptr;
-  BPP_TRY(ctx_ws(ctx, "vj_ch", ((size_t)total + 1) * nch * 64, &d_ch));
-  BPP_TRY(ctx_ws(ctx, "vj_ok", (size_t)total * 4, &d_ok));
-  launch_replay<1>(st, C, p0, p1, total, d_init, nullptr, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok, d_stt);
-  return ctx_check_launch(ctx, "k_verify_replay_g<V>");
-}
-
-int verify_replay_early_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_init,
-                            const uint32_t* d_proofs, const uint32_t* d_V, const ReplayEarly& e) {
-  if (!e.split || e.split >= count) return BPP_OK;
-  const uint32_t nch = 6 + C.lg;
-  void *d_ch = nullptr, *d_ok = nullptr;
-  BPP_TRY(ctx_ws(ctx, "vj_ch", ((size_t)count + 1) * nch * 64, &d_ch));
-  BPP_TRY(ctx_ws(ctx, "vj_ok", (size_t)count * 4, &d_ok));
-  // proofs [0, split) as soon as their bytes are up (e.ready): a latency
-  // chain of ~0.25-0.3 ms beside the last chunk's upload and the rest's replay
-  BPP_HIP(hipStreamWaitEvent(e.st, e.ready, 0));
-  launch_replay<0>(e.st, C, 0, e.split, count, d_init, d_proofs, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok, nullptr);
-  BPP_HIP(hipEventRecord(e.done, e.st));
-  return ctx_check_launch(ctx, "k_verify_replay_g<early>");
-}
-
 int verify_replay_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_init,
-                      const uint32_t* d_proofs, const uint32_t* d_V, uint32_t* d_rec, uint32_t* r_out, uint32_t* bad,
-                      const uint32_t* d_stt, const ReplayEarly* early) {
+                      const uint32_t* d_proofs, const uint32_t* d_V, uint32_t* d_rec, uint32_t* r_out, uint32_t* bad) {
   if (!count) return BPP_OK;
   const uint32_t pw = (uint32_t)(perm::proof_len(C.k) / 4);
   const uint32_t nch = 6 + C.lg;
@@ -359,19 +296,14 @@ int verify_replay_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, cons
   BPP_TRY(ctx_ws(ctx, "vj_ok", (size_t)count * 4, &d_ok));
   {
     ProfScope ps(ctx, "verify_replay_dev");
-    if (d_stt) {
-      launch_replay<2>(ctx->stream, C, 0, count, count, nullptr, d_proofs, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok,
-                       (uint32_t*)d_stt);
-    } else if (early && early->split > 0 && early->split < count) {
-      // proofs [0, split) went on early->st already (verify_replay_early_dev);
-      // the rest here after the last copy, then the join
-      launch_replay<0>(ctx->stream, C, early->split, count, count, d_init, d_proofs, d_V, (uint32_t*)d_ch,
-                       (uint32_t*)d_ok, nullptr);
-      BPP_HIP(hipStreamWaitEvent(ctx->stream, early->done, 0));
-    } else {
-      launch_replay<0>(ctx->stream, C, 0, count, count, d_init, d_proofs, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok,
-                       nullptr);
-    }
+    // the proof and V bytes of the block's groups, staged in LDS while they fit
+    const size_t stage = (size_t)RG_GROUPS * (pw + 8 * (size_t)C.m) * 4;
+    if (stage <= 48 * 1024)
+      hipLaunchKernelGGL(k_verify_replay_g<true>, dim3(grid_for(count, RG_GROUPS)), dim3(64), stage, ctx->stream, 0u,
+                         count, count, C.k, C.lg, C.n_p, d_init, d_proofs, pw, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok);
+    else
+      hipLaunchKernelGGL(k_verify_replay_g<false>, dim3(grid_for(count, RG_GROUPS)), dim3(64), 0, ctx->stream, 0u,
+                         count, count, C.k, C.lg, C.n_p, d_init, d_proofs, pw, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok);
   }
   BPP_TRY(ctx_check_launch(ctx, "k_verify_replay_g"));
   {

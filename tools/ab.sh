@@ -14,7 +14,7 @@
 # REPS (default 2; 3 for prove) interleaved passes over the CFGs.
 # Examples:
 #   bash tools/ab.sh msm "LIB=default" "LIB=w2"              (was ab_msm.sh)
-#   bash tools/ab.sh msmv "BPP_MSM_LONE_RLOG=2" "BPP_MSM_LONE_RLOG=4"
+#   bash tools/ab.sh msmv "BPP_MSM_ACC_K=48" "BPP_MSM_ACC_K=64"
 #   bash tools/ab.sh full "BPP_BENCH_HW_QUEUES=4" "BPP_BENCH_HW_QUEUES=8"   (bench.py sets GPU_MAX_HW_QUEUES from it)
 #   bash tools/ab.sh prove "B=256 T=16 BPP_HOST_THREADS=4" "B=384 T=11"
 #   bash tools/ab.sh prove "GPU_MAX_HW_QUEUES=8 T=12" "BPP_IPA_DEVICE_MERLIN=1"

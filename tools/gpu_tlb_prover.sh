@@ -1,7 +1,7 @@
 # Where does the prover's direct-table gather stall go?
 # Translation (UTCL1) and L2-latency counters of k_dt_msm / k_ipa_round_dt
 # under the prover's load shape, one rocprofv3 --pmc pass each, for the
-# configurations given (e.g. BPP_DT_PAIR=0 / =1).  Summarise with
+# configurations given (e.g. BPP_HOST_THREADS=8 / =16).  Summarise with
 # tools/tlb_summary.py.
 # Usage (on the box): bash tools/gpu_tlb_prover.sh TAG "CFG" ["CFG" ...]
 set -o pipefail

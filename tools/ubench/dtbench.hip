@@ -185,7 +185,8 @@ static float time_kernel(bool two, uint32_t M, uint32_t nt, const uint32_t* dt, 
     if (two)
       hipLaunchKernelGGL(k_dt_msm2, dim3(M), dim3(nt), nt * 160, 0, dt, g, sc, pidx, off, out);
     else
-      hipLaunchKernelGGL(k_dt_msm, dim3(M), dim3(nt), nt * 160, 0, dt, g, sc, pidx, off, out);
+      hipLaunchKernelGGL(k_dt_msm, dim3(M), dim3(nt), nt * 160, 0, dt, g, sc, pidx, off, out,
+                         (const uint32_t*)nullptr, 1u, (uint32_t)M);
     hipEventRecord(b);
     hipEventSynchronize(b);
     float ms;
@@ -226,7 +227,8 @@ static void run(uint32_t c, uint32_t M, uint32_t T, uint32_t nt_cap) {
   float best = 1e9;
   for (int rep = 0; rep < 5; ++rep) {
     hipEventRecord(a);
-    hipLaunchKernelGGL(k_dt_msm, dim3(M), dim3(nt), nt * 160, 0, dt, g, sc, pidx, off, out);
+    hipLaunchKernelGGL(k_dt_msm, dim3(M), dim3(nt), nt * 160, 0, dt, g, sc, pidx, off, out,
+                         (const uint32_t*)nullptr, 1u, (uint32_t)M);
     hipEventRecord(b);
     hipEventSynchronize(b);
     float ms;

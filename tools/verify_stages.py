@@ -1,7 +1,7 @@
 """Per-stage times of one batch verification (config 5 shape by default):
 the host phases and the device kernels (HIP events), averaged over --reps
 verifications after one warm run.  BPP_LIB selects an A/B build
-(build.py --variant ... -D EXP_...; timing-only variants verify False).
+(build.py --variant ...).
 
     python tools/verify_stages.py [--proofs 4096] [--reps 5]
 """
