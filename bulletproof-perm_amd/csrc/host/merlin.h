@@ -353,14 +353,17 @@ struct TranscriptX8 {
   }
 };
 
-// Runs transcript operations on P transcripts that are in lockstep, eight at
-// a time on the 8-way Keccak: fx8(X, idx, real) performs the group's ops on X
-// (instance j is transcript idx[j]; lanes j >= real pad a short last group
-// with copies of its last transcript, whose results the caller drops);
-// f1(p) performs the same ops on transcript p alone when a group is not in
-// lockstep.  `for_groups` runs the groups (the host pool's for_each).
-template <class ForGroups, class FX8, class F1>
-void lockstep_x8(const std::vector<Transcript*>& trs, ForGroups&& for_groups, FX8&& fx8, F1&& f1) {
+// One Fiat-Shamir phase of P transcripts, stated once: transcript p appends
+// n_msgs 32-byte messages (label_of(i), msg_of(p, i): points, or scalars as
+// their 32 canonical bytes, as append_point and append_scalar do), then draws
+// n_ch scalar challenges (ch_label_of(c)), each handed to out(p, c, challenge).
+// Transcripts in lockstep run eight at a time on the 8-way Keccak (lanes past
+// a short last group are copies of its last transcript, results dropped); a
+// group not in lockstep runs the same description on each transcript alone.
+// `for_groups` runs the groups (the host pool's for_each).
+template <class ForGroups, class LabelOf, class MsgOf, class ChLabelOf, class Out>
+void lockstep_phase(const std::vector<Transcript*>& trs, ForGroups&& for_groups, size_t n_msgs, LabelOf&& label_of,
+                    MsgOf&& msg_of, size_t n_ch, ChLabelOf&& ch_label_of, Out&& out) {
   const size_t P = trs.size();
   for_groups((P + 7) / 8, [&](size_t gi) {
     Transcript pad;  // (a short last group's padding lanes share one copy)
@@ -372,14 +375,24 @@ void lockstep_x8(const std::vector<Transcript*>& trs, ForGroups&& for_groups, FX
     for (size_t j = 0; j < 8; ++j) t[j] = j < real ? trs[idx[j]] : &pad;
     TranscriptX8 X;
     if (!X.load(t)) {
-      for (size_t j = 0; j < real; ++j) f1(idx[j]);
+      for (size_t j = 0; j < real; ++j) {
+        const size_t p = idx[j];
+        for (size_t i = 0; i < n_msgs; ++i) trs[p]->append(label_of(i), msg_of(p, i), 32);
+        for (size_t c = 0; c < n_ch; ++c) out(p, c, trs[p]->challenge_scalar(ch_label_of(c)));
+      }
       return;
     }
-    fx8(X, idx, real);
-    // padding lanes share `pad`: store only the real ones (pad's state is dropped)
-    Transcript* tr[8];
-    for (size_t j = 0; j < 8; ++j) tr[j] = j < real ? t[j] : &pad;
-    X.store(tr);
+    const uint8_t* msg[8];
+    for (size_t i = 0; i < n_msgs; ++i) {
+      for (size_t j = 0; j < 8; ++j) msg[j] = msg_of(idx[j], i);
+      X.append(label_of(i), msg, 32);
+    }
+    for (size_t c = 0; c < n_ch; ++c) {
+      hsc::Sc ch[8];
+      X.challenge_scalar(ch_label_of(c), ch);
+      for (size_t j = 0; j < real; ++j) out(idx[j], c, ch[j]);
+    }
+    X.store(t);  // (padding lanes all store into `pad`, which is dropped)
   });
 }
 

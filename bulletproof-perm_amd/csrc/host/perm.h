@@ -137,7 +137,10 @@ size_t proof_len(uint32_t k);
 // replay (DESIGN.md §5 "Batch weights").  A seed the provers can predict
 // voids the batch's soundness.
 hsc::Sc batch_weight(const uint8_t seed[32], uint64_t p, const hsc::Sc& r);
-// 32 bytes from the OS CSPRNG (getrandom); false if it fails
-bool verify_seed(uint8_t seed[32]);
+// len bytes from the OS CSPRNG (getrandom, restarted when a signal
+// interrupts it); false if it fails.  The verifier's batch seed and the
+// provers' entropy both come from here.
+__attribute__((visibility("hidden"))) bool os_entropy(uint8_t* out, size_t len);  // (not exported)
+bool verify_seed(uint8_t seed[32]);  // os_entropy(seed, 32)
 
 }  // namespace perm

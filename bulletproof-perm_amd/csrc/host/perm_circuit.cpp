@@ -189,10 +189,10 @@ hsc::Sc batch_weight(const uint8_t seed[32], uint64_t p, const hsc::Sc& r) {
   return hsc::from_wide(o);
 }
 
-bool verify_seed(uint8_t seed[32]) {
+bool os_entropy(uint8_t* out, size_t len) {
   size_t got = 0;
-  while (got < 32) {
-    const ssize_t n = getrandom(seed + got, 32 - got, 0);
+  while (got < len) {
+    const ssize_t n = getrandom(out + got, len - got, 0);
     if (n > 0)
       got += (size_t)n;
     else if (n < 0 && errno != EINTR)
@@ -200,5 +200,7 @@ bool verify_seed(uint8_t seed[32]) {
   }
   return true;
 }
+
+bool verify_seed(uint8_t seed[32]) { return os_entropy(seed, 32); }
 
 }  // namespace perm

@@ -820,53 +820,40 @@ int ipa_prove_batch_dev(bpp_ctx* ctx, const std::vector<merlin::Transcript*>& tr
       BPP_TRY(msm_multi_enc(ctx, (const uint32_t*)scal, (const uint32_t*)pidx, off, g.pts, enc.data(), true));
     }
     if (!dev_merlin) {
-    HostScope hs(ctx, "ipa_host");
-    if (one) {  // the caller's transcript (bpp_ipa_prove_cb), one instance
-      if (!one->append("L", enc.data(), 32) || !one->append("R", enc.data() + 32, 32) ||
-          !one->challenge_scalar("u", u[0]))
-        return ipa_hook_failed(ctx);
-    } else
-    // L, R appends and the u challenge of eight proofs at a time on the
-    // 8-way Keccak (their transcripts are in lockstep)
-    merlin::lockstep_x8(
-        trs, [](size_t n, const std::function<void(size_t)>& f) { par::for_each(n, f); },
-        [&](merlin::TranscriptX8& X, const size_t* idx, size_t real) {
-          const uint8_t *lm[8], *rm[8];
-          for (int j = 0; j < 8; ++j) {
-            lm[j] = enc.data() + 64 * idx[j];
-            rm[j] = lm[j] + 32;
-          }
-          X.append("L", lm, 32);
-          X.append("R", rm, 32);
-          hsc::Sc u8[8];
-          X.challenge_scalar("u", u8);
-          for (size_t j = 0; j < real; ++j) u[idx[j]] = u8[j];
-        },
-        [&](size_t p) {
-          trs[p]->append_point("L", enc.data() + 64 * p);
-          trs[p]->append_point("R", enc.data() + 64 * p + 32);
-          u[p] = trs[p]->challenge_scalar("u");
-        });
-    for (uint32_t p = 0; p < P; ++p) {
-      Enc32 Le, Re;
-      memcpy(Le.data(), enc.data() + 64 * p, 32);
-      memcpy(Re.data(), enc.data() + 64 * p + 32, 32);
-      out[p].L.push_back(Le);
-      out[p].R.push_back(Re);
-    }
-    ui = u;
-    {
-      HostScope hi(ctx, "ipa_uinv");
-      hsc::batch_invert(ui, false, true);  // (u: public challenges)
-    }
-    uint32_t* uwp = zc ? h_uw : uw.data();  // (zc: the device reads them in place)
-    for (uint32_t p = 0; p < P; ++p) {  // device Montgomery forms u R, u^-1 R
-      const sc um = to_dev_sc(hsc::to_mont(u[p]));
-      const sc uim = to_dev_sc(hsc::to_mont(ui[p]));
-      memcpy(&uwp[16 * (size_t)p], um.v, 32);
-      memcpy(&uwp[16 * (size_t)p + 8], uim.v, 32);
-    }
-    if (!zc) BPP_TRY(ctx_h2d(ctx, d_u, uw.data(), uw.size() * 4));
+      HostScope hs(ctx, "ipa_host");
+      if (one) {  // the caller's transcript (bpp_ipa_prove_cb), one instance
+        if (!one->append("L", enc.data(), 32) || !one->append("R", enc.data() + 32, 32) ||
+            !one->challenge_scalar("u", u[0]))
+          return ipa_hook_failed(ctx);
+      } else {
+        // L, R appends and the u challenge of eight proofs at a time on the
+        // 8-way Keccak (their transcripts are in lockstep)
+        merlin::lockstep_phase(
+            trs, [](size_t n, const std::function<void(size_t)>& f) { par::for_each(n, f); }, 2,
+            [](size_t i) { return i ? "R" : "L"; },
+            [&](size_t p, size_t i) { return (const uint8_t*)enc.data() + 64 * p + 32 * i; }, 1,
+            [](size_t) { return "u"; }, [&](size_t p, size_t, const hsc::Sc& c) { u[p] = c; });
+      }
+      for (uint32_t p = 0; p < P; ++p) {
+        Enc32 Le, Re;
+        memcpy(Le.data(), enc.data() + 64 * p, 32);
+        memcpy(Re.data(), enc.data() + 64 * p + 32, 32);
+        out[p].L.push_back(Le);
+        out[p].R.push_back(Re);
+      }
+      ui = u;
+      {
+        HostScope hi(ctx, "ipa_uinv");
+        hsc::batch_invert(ui, false, true);  // (u: public challenges)
+      }
+      uint32_t* uwp = zc ? h_uw : uw.data();  // (zc: the device reads them in place)
+      for (uint32_t p = 0; p < P; ++p) {  // device Montgomery forms u R, u^-1 R
+        const sc um = to_dev_sc(hsc::to_mont(u[p]));
+        const sc uim = to_dev_sc(hsc::to_mont(ui[p]));
+        memcpy(&uwp[16 * (size_t)p], um.v, 32);
+        memcpy(&uwp[16 * (size_t)p + 8], uim.v, 32);
+      }
+      if (!zc) BPP_TRY(ctx_h2d(ctx, d_u, uw.data(), uw.size() * 4));
     }
     // the fused rounds fold inside the next round's launch; the last
     // challenge (and every challenge of the unfused path) is folded here

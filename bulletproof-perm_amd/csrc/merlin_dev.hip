@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(64) k_ipa_transcript_step(uint32_t P, uint8_t*
 // The prover's V phase for P proofs, one lane each: from the shared state
 // after Transcript::new(label) + arithmetic_domain_sep(n_p) (init: 50 state
 // words + pos + pos_begin), append_point("V", V_i) for i < 2k and
-// x_perm = challenge_scalar("x_perm") (perm_api.hip prove_batch; the
+// x_perm = challenge_scalar("x_perm") (perm_prove.hip pedersen_V; the
 // reference's create, circuit_lib.rs:139-186, in sound form).  venc: [P][2k]
 // encodings on the device.  states_out: [P][MERLIN_DEV_STATE_BYTES],
 // xperm_out: [P][8] canonical words (both may be pinned host memory).

@@ -15,7 +15,7 @@
 //                proof's blindings) -> host for tau_x
 //   k_poly_x     l = l(x), r = r(x) straight into the IPA's input arrays,
 //                t_hat = <l, r> -> host
-// Identical values to the host formulas they replace (perm_api.hip history;
+// Identical values to the host formulas they replace (perm_prove.hip history;
 // oracle/bulletproofs.py prove()), hence identical proof bytes (tests).
 #include <algorithm>
 #include <cstring>
@@ -247,7 +247,7 @@ __global__ void __launch_bounds__(POLY_T) k_poly_x(uint32_t n_p, const uint32_t*
 // ---------------------------------------------------------------------------
 // Batch verifier's MSM scalars on the GPU (the verifier side of the same
 // circuit algebra, circuit_lib.rs:478-585 in sound form; host restatement
-// perm_api.hip verify_expand, which bpp_perm_verify_scalars still uses).
+// perm_verify.hip verify_expand, which bpp_perm_verify_scalars still uses).
 // One workgroup per proof; rec[p] = VREC_N canonical scalars:
 // (VREC_* slots: verify_dev.h)
 // Writes wt * (generator scalars) to gen[p][2 n_p + 2] (summed over proofs by
@@ -817,7 +817,7 @@ int witness_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t
                 uint32_t per, uint32_t* d_sc, const uint32_t* d_vals) {
   if (!P) return BPP_OK;
   // (256 lanes while the prefixes and both scan buffers fit 64 KB, else 128:
-  // perm_api's dev_witness bound (2 k + 512) x 32 B)
+  // perm_prove.hip's dev_witness bound (2 k + 512) x 32 B)
   const unsigned nt = (2 * (size_t)C.k + 4 * 256) * 32 <= 64 * 1024 ? 256 : 128;
   const size_t lds = (2 * (size_t)C.k + 4 * nt) * 32;
   if (d_vals) {

@@ -5,7 +5,7 @@
 // Restates the verifier's transcript of ACProof::verify
 // (bp-perm/src/circuit_lib.rs:478-585 in sound form; point validation as
 // TranscriptProtocol::validate_and_append_point, transcript_protocol.rs:48-60)
-// exactly as the host replay does (perm_api.hip verify_replay; byte-equal r
+// exactly as the host replay does (perm_verify.hip verify_replay; byte-equal r
 // challenges are tested, tests/test_gpu_verify_dev.py).  A batch's
 // transcripts perform the same operations with the same lengths, so one
 // wave-uniform schedule drives 64 sponges (merlin_lane.cuh).  The replay was
@@ -32,7 +32,7 @@ FE_INLINE bool w8_zero(const uint32_t w[8]) {
   return o == 0;
 }
 
-// Proof layout (perm_api.hip serialize, bpp_perm_proof_len): A_I A_O S T1 T3
+// Proof layout (perm_internal.h serialize, bpp_perm_proof_len): A_I A_O S T1 T3
 // T4 T5 T6 (points), tau_x mu t_hat, L_0 R_0 .. L_{lg-1} R_{lg-1}, a b;
 // 8 words each.
 // ---------------------------------------------------------------------------

@@ -414,7 +414,7 @@ static ge_ext commit2(const gens_t* g, sc_t v, sc_t gam) {
   return msm(s, P, 2);
 }
 
-/* proof layout (perm_api.hip serialize): A_I A_O S T1 T3 T4 T5 T6 | tau_x mu
+/* proof layout (perm_internal.h serialize): A_I A_O S T1 T3 T4 T5 T6 | tau_x mu
  * t_hat | L_j R_j ... | a b; V: m encodings */
 static int prove(const gens_t* G, const circuit_t* C, uint64_t seed, const uint8_t* label, size_t llen,
                  uint8_t* proof, uint8_t* Vout) {

@@ -4,6 +4,8 @@
 // leans on between launches:
 //   - merlin / STROBE transcripts (the KAT), the 8-way AVX-512 Keccak and
 //     TranscriptX8 against eight scalar transcripts, SHAKE256 x8;
+//   - merlin::lockstep_phase, its 8-wide path and its single-transcript
+//     fallback, against plain transcripts;
 //   - the prover's random draws (x8 vs scalar, u64 and 32-byte seeds);
 //   - scalar arithmetic mod l (invert, batch_invert, from_wide);
 //   - the host field / group (encode, decode, encode_double_batch);
@@ -12,6 +14,7 @@
 // Exit 0 and "ok" on success.
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <thread>
 #include <vector>
 
@@ -87,6 +90,61 @@ static int test_transcripts() {
     sh.read(out1, 500);
     CHECK(memcmp(out1, out8[j], 500) == 0);
   }
+  return 0;
+}
+
+// merlin::lockstep_phase (the prover's and the IPA's transcript phases): three
+// appends and two challenges on P transcripts against the same operations on
+// P plain Transcripts -- every challenge and every transcript's next 32
+// challenge bytes.  skew: one transcript of the first group takes an extra
+// short append beforehand (on both sides), so that group is not in lockstep
+// and runs the single-transcript fallback.
+static int lockstep_case(size_t P, bool skew) {
+  static const char* const lab[3] = {"A_I", "A_O", "S"};
+  static const char* const chl[2] = {"y", "z"};
+  std::vector<merlin::Transcript> a, b;
+  for (size_t p = 0; p < P; ++p) {
+    a.emplace_back((const uint8_t*)"phase", 5);
+    b.emplace_back((const uint8_t*)"phase", 5);
+  }
+  if (skew) {
+    const size_t q = P > 2 ? 2 : 0;
+    a[q].append("skew", (const uint8_t*)"x", 1);
+    b[q].append("skew", (const uint8_t*)"x", 1);
+  }
+  std::vector<uint8_t> msg(P * 3 * 32);
+  for (size_t i = 0; i < msg.size(); ++i) msg[i] = (uint8_t)(i * 89 + 5 * P + 3);
+  std::vector<merlin::Transcript*> trs(P);
+  for (size_t p = 0; p < P; ++p) trs[p] = &b[p];
+  std::vector<hsc::Sc> got(2 * P, hsc::zero());
+  std::vector<int> calls(2 * P, 0);
+  merlin::lockstep_phase(
+      trs, [](size_t n, const std::function<void(size_t)>& f) { par::for_each(n, f); }, 3,
+      [](size_t i) { return lab[i]; }, [&](size_t p, size_t i) { return msg.data() + (3 * p + i) * 32; }, 2,
+      [](size_t c) { return chl[c]; },
+      [&](size_t p, size_t c, const hsc::Sc& s) {
+        got[2 * p + c] = s;
+        ++calls[2 * p + c];
+      });
+  for (size_t p = 0; p < P; ++p) {
+    for (int i = 0; i < 3; ++i) a[p].append_point(lab[i], msg.data() + (3 * p + i) * 32);
+    for (int c = 0; c < 2; ++c) {
+      const hsc::Sc want = a[p].challenge_scalar(chl[c]);
+      CHECK(calls[2 * p + c] == 1);
+      CHECK(memcmp(&want, &got[2 * p + c], 32) == 0);
+    }
+    uint8_t n1[32], n2[32];
+    a[p].challenge_bytes("next", n1, 32);
+    b[p].challenge_bytes("next", n2, 32);
+    CHECK(memcmp(n1, n2, 32) == 0);
+  }
+  return 0;
+}
+
+static int test_lockstep_phase() {
+  for (size_t P : {1, 7, 8, 9, 17})
+    for (bool skew : {false, true})
+      if (lockstep_case(P, skew)) return 1;
   return 0;
 }
 
@@ -212,7 +270,7 @@ static int test_pool() {
 }
 
 int main() {
-  if (test_transcripts() || test_draws() || test_scalars() || test_group() || test_pool()) return 1;
+  if (test_transcripts() || test_lockstep_phase() || test_draws() || test_scalars() || test_group() || test_pool()) return 1;
   printf("ok\n");
   return 0;
 }
