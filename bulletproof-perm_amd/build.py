@@ -6,6 +6,9 @@ Every .hip under csrc/ is compiled with hipcc --offload-arch=gfx950 (host/*.cpp
 with the host C++ compiler, g++ by default)
 into build/ and linked into bpperm/libbpperm.so next to the ctypes wrapper,
 so the shared object travels with a gpurun snapshot.
+
+build_probe() builds the tests' device arithmetic probe
+(probe/arith_probe.hip) into its own bpperm/libbpperm_probe.so.
 """
 from __future__ import annotations
 
@@ -19,6 +22,8 @@ ROOT = Path(__file__).resolve().parent
 CSRC = ROOT / "csrc"
 BUILD = ROOT / "build"
 OUT = ROOT / "bpperm" / "libbpperm.so"
+PROBE = ROOT / "probe"
+PROBE_OUT = ROOT / "bpperm" / "libbpperm_probe.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HOSTCXX = os.environ.get("BPP_HOSTCXX", "g++")
 ARCH = os.environ.get("BPP_ARCH", "gfx950")
@@ -79,6 +84,28 @@ def build(debug: bool = False, jobs: int | None = None, variant: str = "", defin
     return out
 
 
+def build_probe(debug: bool = False) -> Path:
+    """The device arithmetic probe of the tests (probe/arith_probe.hip: the
+    csrc/ headers called one lane per case) -> bpperm/libbpperm_probe.so.
+    Same compiler, arch and flags as the library; its own shared object, so
+    it adds nothing to libbpperm.so or its ABI.  Rebuilt when the source or
+    any header of dep_headers() changes."""
+    src = PROBE / "arith_probe.hip"
+    deps = [src] + dep_headers()
+    if PROBE_OUT.exists() and PROBE_OUT.stat().st_mtime >= max(d.stat().st_mtime for d in deps):
+        return PROBE_OUT
+    flags = ["-O1", "-g"] if debug else ["-O3"]
+    flags += ["-Wno-unused-result", "-Wno-pass-failed", "-pthread", "-Xarch_host", "-march=x86-64-v3"]
+    # (-Bsymbolic: the probe's launches bind to its own copies of the kernels
+    # that libbpperm.so also defines, whatever else the process has loaded)
+    cmd = [HIPCC, f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", *flags, "-shared", "-Wl,-Bsymbolic", "-x", "hip",
+           str(src), "-o", str(PROBE_OUT)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"probe build failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
+    return PROBE_OUT
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
@@ -87,3 +114,5 @@ if __name__ == "__main__":
     ap.add_argument("-D", dest="defines", action="append", default=[])
     a = ap.parse_args()
     print(build(debug=a.debug, variant=a.variant, defines=a.defines))
+    if not a.variant:
+        print(build_probe(debug=a.debug))

@@ -18,6 +18,20 @@ struct DtGeom {
   uint32_t c, W, H;  // window bits, windows, rows per window (2^(c-1))
   uint32_t K[8];     // sum_{w < W-1} 2^(c w + c - 1), little-endian words
 };
+// The one construction of a DtGeom (host; msm.hip, ipa.hip and the
+// arithmetic probe).
+static inline DtGeom dt_geom(uint32_t c) {
+  DtGeom g;
+  g.c = c;
+  g.W = (254 + c - 1) / c;
+  g.H = 1u << (c - 1);
+  for (int i = 0; i < 8; ++i) g.K[i] = 0;
+  for (uint32_t w = 0; w + 1 < g.W; ++w) {  // bit c w + c - 1 (< 253)
+    const uint32_t pos = c * w + c - 1;
+    g.K[pos >> 5] |= 1u << (pos & 31);
+  }
+  return g;
+}
 #define DT_NT_MAX 256
 // (145 VGPRs, 3 waves per SIMD; capping the direct-table kernels at 128 for
 // a fourth spilled 124 B per lane and measured 104-120 K vs 147-151 K

@@ -17,6 +17,10 @@
 // value in flight is a valid multiplier operand.  The value is < 2^256 but
 // may exceed p; fe_canon gives the unique representative < p with exact
 // limb widths.
+//
+// Every bound stated in this file is executed at bound - 1 in every limb by
+// tests/test_gpu_arith_fe.py (through probe/arith_probe.hip); each comment
+// names its test.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,7 +50,11 @@ FE_INLINE fe fe_small(uint32_t x) {  // x < 2^26
   return r;
 }
 
-// One carry pass: limbs < 2^32 in, tight out (limb 0 < 2^26 + 19 * 2^7).
+// One carry pass: limbs < 2^32 - 2^7 in, tight out (limb 0 < 2^26 + 19 * 2^7,
+// the others exact width).  Not "< 2^32": a limb takes a carry of up to
+// 2^7 - 1 from the limb below, and limb + carry must not wrap 32 bits (the
+// largest input in the product is ~2^28.1).
+// [test_fe_carry_at_its_input_bound]
 FE_INLINE fe fe_carry(fe a) {
   uint32_t c;
   _Pragma("unroll") for (int i = 0; i < 9; ++i) {
@@ -67,7 +75,10 @@ FE_INLINE fe fe_add(const fe& a, const fe& b) {
   return fe_carry(r);
 }
 
-// a - b + 2p (each 2p limb exceeds a tight limb), carried
+// a - b + 2p, carried.  b's limbs must not exceed 2p's (0x7ffffda, then
+// 0x3fffffe odd / 0x7fffffe even): every tight limb qualifies, an fe_add_nc /
+// fe_sub_nc result does not.  a may be any multiplier operand (< 2^27.6).
+// [test_fe_add_sub_neg]
 FE_INLINE fe fe_sub(const fe& a, const fe& b) {
   fe r;
   r.v[0] = a.v[0] + 0x7ffffdau - b.v[0];
@@ -80,7 +91,10 @@ FE_INLINE fe fe_neg(const fe& a) { return fe_sub(fe_zero(), a); }
 // Non-carrying forms for the point formulas, where a result only feeds
 // multiplier operands (limit 2^27.6): a, b tight ->
 //   fe_add_nc < 2^27 + 2^19,  fe_sub_nc < 2^27 + 2^26 + 2^18 (= 2^27.59).
-// Neither result may be the subtrahend of a later fe_sub / fe_sub_nc.
+// Neither result may be the subtrahend of a later fe_sub / fe_sub_nc.  The
+// widest operand the point formulas build is G = fe_add_nc(fe_add_nc(Z, Z), C)
+// < 2^27 + 2^26 + 2^19 + 2^18 (= 2^27.593).
+// [test_fe_add_nc_sub_nc; as multiplier operands: test_fe_mul_sq_at_input_bound]
 FE_INLINE fe fe_add_nc(const fe& a, const fe& b) {
   fe r;
   _Pragma("unroll") for (int i = 0; i < FE_LIMBS; ++i) r.v[i] = a.v[i] + b.v[i];
@@ -100,7 +114,8 @@ FE_INLINE fe fe_sqn(fe a, int n) {
   return a;
 }
 
-// multiply by a small constant k < 2^31
+// multiply by a small constant k < 2^31: any limbs < 2^32 in, tight out
+// [test_fe_mul_small]
 FE_INLINE fe fe_mul_small(const fe& a, uint32_t k) {
   fe r;
   uint64_t acc = 0;
@@ -110,14 +125,17 @@ FE_INLINE fe fe_mul_small(const fe& a, uint32_t k) {
     r.v[i] = (uint32_t)acc & ((1u << w) - 1u);
     acc >>= w;
   }
-  // acc < 2^34: bits >= 255, worth 19
+  // acc < 2^38 (< 2^34 for tight limbs): bits >= 255, worth 19
   const uint64_t t = MAD64((uint32_t)acc, 19u, (uint64_t)r.v[0]) + ((uint64_t)((uint32_t)(acc >> 32) * 19u) << 32);
   r.v[0] = (uint32_t)t & FE_M26;
   r.v[1] += (uint32_t)(t >> 26);
   return r;
 }
 
-// Fully reduce: exact limb widths, value < p.
+// Fully reduce: exact limb widths, value < p.  Input: fe_carry's (tight
+// limbs, or exact limbs with the excess over 2^255 in limb 9).
+// [test_fe_canon_and_predicates: the values around p, 2p and 2^255, and limb
+// 0 stepping through 2^26 - 20 .. 2^26 + 19 * 2^7 over all-ones upper limbs]
 FE_INLINE fe fe_canon(fe a) {
   a = fe_carry(a);
   a = fe_carry(a);  // limb 0 < 2^26 + 19, others exact
@@ -205,7 +223,8 @@ FE_INLINE fe fe_pow22523(const fe& z) {
 }
 
 // ---------------------------------------------------------------- bytes
-// 8 little-endian 32-bit words (any value < 2^256; bit 255 is worth 19)
+// 8 little-endian 32-bit words (any value < 2^256; bit 255 is worth 19):
+// exact limbs out, limb 0 < 2^26 + 19.  [test_fe_words, bit 255 set included]
 FE_INLINE fe fe_load_words(const uint32_t* w) {
   fe r;
   const int OFF[10] = {0, 26, 51, 77, 102, 128, 153, 179, 204, 230};

@@ -7,6 +7,16 @@
 // Coordinates: extended (X:Y:Z:T), x = X/Z, y = Y/Z, XY = ZT, a = -1.
 // Addition is the unified HWCD'08 law, complete on this curve (a square,
 // d non-square), so bucket accumulation needs no identity/doubling branches.
+//
+// Limb contract: every point operation takes tight coordinates (fe25519.cuh)
+// and returns fe_mul outputs, which are tight.  tests/test_gpu_arith_ge.py
+// (through probe/arith_probe.hip) runs every operation on coordinates at the
+// tight maximum in every limb over the completeness cases (P + P, P - P,
+// identity, small-order points), checks the output limbs, feeds 64 outputs
+// back in (test_closure_of_accumulation_and_doubling), and holds the signed,
+// split, fetched-swapped and quad variants to ge_madd / ge_msub / ge_add limb
+// for limb.  ge_ristretto_encode gives one encoding per ristretto class
+// whatever the representative (test_ristretto_encode_is_constant_on_a_class).
 #pragma once
 #include "fe25519.cuh"
 

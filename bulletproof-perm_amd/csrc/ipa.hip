@@ -27,7 +27,6 @@
 #include "host/par.h"
 #include "sc25519.cuh"
 
-DtGeom dt_geom(uint32_t c);                                     // msm.hip
 bool msm_use_dt(const MsmPoints& pts, uint32_t M, uint32_t T);  // msm.hip
 
 static unsigned grid_for(size_t n, unsigned t) { return (unsigned)((n + t - 1) / t); }

@@ -64,27 +64,7 @@ int msm_engine(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx, con
                uint32_t* rshift_out) {
   if (terms_out) *terms_out = 1;
   if (rshift_out) *rshift_out = rlog + 6;
-  MsmGeom g;
-  g.M = M;
-  g.T = T;
-  g.c = c;
-  g.W = (254 + c - 1) / c;
-  g.wb = wb;
-  g.Wn = Wn;
-  g.B = 1u << (c - 1);
-  g.fb = fb ? 1u : 0u;
-  {
-    // radix sort: the top window holds 253 - c (W - 1) bits (canonical
-    // scalars < l < 2^253), i.e. buckets < 2^top; spread them over all
-    // NC = B / 2^RS_FINE_BITS coarse bins (rs_fbits)
-    const int top = 253 - (int)(c * (g.W - 1)), lognc = (int)c - 1 - RS_FINE_BITS;
-    g.tfb = (top >= (int)c - 1 || lognc < 0) ? RS_FINE_BITS : (uint32_t)std::max(0, top - lognc);
-    for (int i = 0; i < 8; ++i) g.K[i] = 0;
-    for (uint32_t w = 0; w + 1 < g.W; ++w) {  // bit c w + c - 1 (< 256)
-      const uint32_t pos = c * w + c - 1;
-      g.K[pos >> 5] |= 1u << (pos & 31);
-    }
-  }
+  const MsmGeom g = msm_geom(M, T, c, wb, Wn, fb);
   const size_t nseg = fb ? (size_t)M : (size_t)M * Wn;
   const size_t NB = nseg * g.B;
   ctx_work(ctx, "msm_terms", T);
@@ -738,15 +718,7 @@ int bpp_msm_batch(bpp_ctx* ctx, size_t count, const uint64_t* offsets, const uin
     BPP_HIP(hipMemcpyAsync(d_off, off32.data(), (count + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     const uint32_t c = msm_choose_c((double)T / (double)count);
     const uint32_t W = (254 + c - 1) / c;
-    MsmGeom g;
-    g.M = (uint32_t)count;
-    g.T = (uint32_t)T;
-    g.c = c;
-    g.W = W;
-    g.wb = 0;
-    g.Wn = W;
-    g.B = 1u << (c - 1);
-    g.fb = 0;
+    const MsmGeom g = msm_geom((uint32_t)count, (uint32_t)T, c, 0, W);
     uint32_t* d_ws = nullptr;
     BPP_TRY(msm_engine(ctx, d_s, (const uint32_t*)d_idx, (const uint32_t*)d_off, g.M, g.T, c, 0, W, tbl->d, &d_ws));
     {
@@ -820,19 +792,6 @@ static int fb_policy() {
 static bool fb_wins(double terms_per_msm) {
   const int pol = fb_policy();
   return pol == 1 || (pol == -1 && terms_per_msm <= 16384.0);
-}
-
-DtGeom dt_geom(uint32_t c) {
-  DtGeom g;
-  g.c = c;
-  g.W = (254 + c - 1) / c;
-  g.H = 1u << (c - 1);
-  for (int i = 0; i < 8; ++i) g.K[i] = 0;
-  for (uint32_t w = 0; w + 1 < g.W; ++w) {  // bit c w + c - 1 (< 253)
-    const uint32_t pos = c * w + c - 1;
-    g.K[pos >> 5] |= 1u << (pos & 31);
-  }
-  return g;
 }
 
 size_t dt_bytes(uint32_t npts, uint32_t c) {
@@ -1022,15 +981,7 @@ int msm_multi(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx, cons
       out[m] = horner_host_terms((const uint32_t*)h + (size_t)m * W * nterms * P3_WORDS, W, nterms, c, 0);
     return BPP_OK;
   }
-  MsmGeom g;
-  g.M = M;
-  g.T = T;
-  g.c = c;
-  g.W = W;
-  g.wb = 0;
-  g.Wn = W;
-  g.B = 1u << (c - 1);
-  g.fb = 0;
+  const MsmGeom g = msm_geom(M, T, c, 0, W);
   void* d_res = nullptr;
   BPP_TRY(ctx_ws(ctx, "multi_res", (size_t)M * P3_BYTES, &d_res));
   {

@@ -82,6 +82,9 @@ struct MsmGeom {
 // Signed digit loop: calls f(w - wb, digit) for every window in
 // [wb, wb + Wn) whose signed radix-2^c digit is non-zero.  Digits lie in
 // [-2^(c-1), 2^(c-1)]; scalars must be < 2^253 (canonical mod l).
+// (This recoding exists four times -- here, k_msm_digits, the closed form of
+// k_rsort_digits_count and DtLane::row_of; tests/test_gpu_arith_digits.py
+// holds all four to one reference for c = 2..16.)
 template <typename F>
 FE_INLINE void for_each_digit(const uint32_t s[8], const MsmGeom& g, F f) {
   uint32_t carry = 0;
@@ -683,6 +686,32 @@ FE_INLINE uint32_t rs_fbits(const MsmGeom& g, uint32_t ww) {
 // coarse bin of bucket b (clamped: a non-canonical device scalar gives a
 // wrong result, never an out-of-range bin)
 FE_INLINE uint32_t rs_bin(uint32_t b, uint32_t fbits, uint32_t NC) { return min(b >> fbits, NC - 1); }
+
+// The one construction of an MsmGeom (host): W, B, the radix sort's top-window
+// fine bits and the closed-form recoding constant K.  msm.hip's launches and
+// the arithmetic probe (probe/arith_probe.hip) build theirs here.
+static inline MsmGeom msm_geom(uint32_t M, uint32_t T, uint32_t c, uint32_t wb, uint32_t Wn, bool fb = false) {
+  MsmGeom g;
+  g.M = M;
+  g.T = T;
+  g.c = c;
+  g.W = (254 + c - 1) / c;
+  g.wb = wb;
+  g.Wn = Wn;
+  g.B = 1u << (c - 1);
+  g.fb = fb ? 1u : 0u;
+  // radix sort: the top window holds 253 - c (W - 1) bits (canonical
+  // scalars < l < 2^253), i.e. buckets < 2^top; spread them over all
+  // NC = B / 2^RS_FINE_BITS coarse bins (rs_fbits)
+  const int top = 253 - (int)(c * (g.W - 1)), lognc = (int)c - 1 - RS_FINE_BITS;
+  g.tfb = (top >= (int)c - 1 || lognc < 0) ? RS_FINE_BITS : (uint32_t)(top > lognc ? top - lognc : 0);
+  for (int i = 0; i < 8; ++i) g.K[i] = 0;
+  for (uint32_t w = 0; w + 1 < g.W; ++w) {  // bit c w + c - 1 (< 256)
+    const uint32_t pos = c * w + c - 1;
+    g.K[pos >> 5] |= 1u << (pos & 31);
+  }
+  return g;
+}
 
 // Digits of a chunk are loaded into registers in one batch of independent
 // coalesced loads (RS_PER per thread) before any LDS atomic: a load-then-

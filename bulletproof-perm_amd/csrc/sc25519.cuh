@@ -5,6 +5,12 @@
 // a/b folds a' = a_lo*u + u^-1*a_hi, b' = b_lo*u^-1 + u*b_hi and the cross
 // inner products c_L, c_R) and of the proof's vector polynomials.
 // Values in Montgomery form (x*R mod l) unless a name says otherwise.
+//
+// Operand contracts: sc_add / sc_sub / sc_neg / sc_half take canonical
+// (< l) operands; sc_mont and sc_mont_cios take a * b < l * R (one operand
+// < l, the other anything < 2^256); sc_reduce256 takes any w < 2^256.
+// tests/test_gpu_arith_sc.py runs each at those edges (through
+// probe/arith_probe.hip) against Python integers.
 #pragma once
 #include "fe25519.cuh"
 
@@ -69,6 +75,8 @@ FE_INLINE sc sc_neg(const sc& a) { return sc_sub(sc_zero(), a); }
 
 // a*b*R^-1 mod l (R = 2^256); requires a*b < l*R (true for a, b < 2^256
 // when one is < l); canonical result.
+// [test_sc_mont_matches_cios_and_integers: a = 2^256 - 1 with b = l - 1 and
+// b = R^2, both operand orders, equal to sc_mont_cios word for word]
 //
 // Radix 2^29 inside: 32 a and b as 9 limbs of 29 bits, the 17 product
 // columns as plain v_mad_u64_u32 sums (each < 18 * 2^58 with the reduction
@@ -138,7 +146,8 @@ FE_INLINE sc sc_mont(const sc& a, const sc& b) {
 }
 
 // The same product by CIOS over 8 x 32-bit words (the round-1 form, kept as
-// the reference of tests / tools/ubench/scbench.hip): every multiply-add of
+// the reference of tests/test_gpu_arith_sc.py and tools/ubench/scbench.hip;
+// same operand contract): every multiply-add of
 // a row waits for the previous one's carry, a ~130-deep chain.
 FE_INLINE sc sc_mont_cios(const sc& a, const sc& b) {
   uint32_t t[10];
@@ -217,7 +226,10 @@ FE_INLINE sc sc_one_mont() {
 }
 
 // canonical w mod l for w < 2^256: w = q 2^252 + rest (q < 16), w - q l =
-// rest - q delta is in (-l, 2^252), one conditional addition of l
+// rest - q delta is in (-l, 2^252), one conditional addition of l (taken
+// only when rest < q delta: probability ~2^-125 for random w).
+// [test_sc_reduce256_both_sides_of_the_add_back: rest = q delta - 1, q delta,
+// q delta + 1 for every q; test_sc_from_wide with those as the low half]
 FE_INLINE sc sc_reduce256(const uint32_t w[8]) {
   const uint32_t q = w[7] >> 28;
   sc r;

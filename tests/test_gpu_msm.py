@@ -63,6 +63,33 @@ def test_msm_edge_scalars(ctx):
     assert got == r255.encode(r255.msm(sc, pts))
 
 
+@pytest.mark.parametrize("n", [8, 64, 300])
+def test_msm_adversarial_window_scalars(ctx, n):
+    """The scalar families of test_gpu_arith_digits.py (every window at the
+    recoding threshold, carries arriving exactly at it, l - 1, 2^252 ...) for
+    the window width the engine picks at n, through bpp_msm and through the
+    window-split partials."""
+    import bpperm
+    import fe10_model as m
+    c, W = bpperm.msm_windows(n)
+    assert W == m.windows(c)
+    fams = m.digit_scalars(c, Rng(50 + n, b"test-scalars"), nrand=8)
+    # whole-scalar patterns first, then the longest carry chains, then the rest
+    order = fams[5:11] + fams[11:11 + W][::-1] + fams[:5] + fams[11 + W:]
+    sc = [order[i % len(order)] for i in range(n)]
+    raw, pts = _points(30 + n, n)
+    want = r255.encode(r255.msm(sc, pts))
+    sb = [r255.scalar_bytes(s) for s in sc]
+    assert ctx.msm(sb, [r255.encode(p) for p in pts]) == want
+    tbl = ctx.from_uniform(raw)
+    d = ctx.dev_alloc(32 * n)
+    ctx.htod(d, b"".join(sb))
+    cuts = [0, W // 3, W]
+    parts = [ctx.msm_table_dev_partial(d, tbl, n, cuts[i], cuts[i + 1]) for i in range(2)]
+    assert bpperm.partials_finish(parts) == want
+    ctx.dev_free(d)
+
+
 def test_msm_rejects_noncanonical(ctx):
     import bpperm
     _, pts = _points(6, 2)
