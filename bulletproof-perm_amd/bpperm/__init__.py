@@ -604,22 +604,39 @@ class PermProver:
         check(rc, "bpp_perm_verify", self.ctx.h)
         return True
 
-    def verify_batch(self, proofs, Vs) -> bool:
-        """proofs / Vs: sequences of per-proof bytes, or the two contiguous
-        buffers (prove_batch(..., raw=True))."""
+    def _batch_buffers(self, proofs, Vs):
+        """verify_batch's two input forms -> (proof bytes, V bytes, count)."""
         if isinstance(proofs, (bytes, bytearray)):
             pb, vb = bytes(proofs), bytes(Vs)
             count = len(pb) // self.proof_len
             if len(pb) != count * self.proof_len or len(vb) != count * 32 * self.m:
                 raise ValueError("contiguous proofs / V buffers of inconsistent length")
-        else:
-            pb, vb, count = b"".join(proofs), b"".join(Vs), len(proofs)
+            return pb, vb, count
+        return b"".join(proofs), b"".join(Vs), len(proofs)
+
+    def verify_batch(self, proofs, Vs) -> bool:
+        """proofs / Vs: sequences of per-proof bytes, or the two contiguous
+        buffers (prove_batch(..., raw=True))."""
+        pb, vb, count = self._batch_buffers(proofs, Vs)
         rc = self.ctx.lib.bpp_perm_verify_batch(self.ctx.h, self.gens.h, self.k, count, _buf(self.label),
                                                 len(self.label), _buf(pb), _buf(vb))
         if rc == 6:
             return False
         check(rc, "bpp_perm_verify_batch", self.ctx.h)
         return True
+
+    def verify_batch_each(self, proofs, Vs) -> "list[bool]":
+        """verify_batch that names the failing proofs: one verdict per proof,
+        what verify(proofs[i], Vs[i]) returns (bpp_perm_verify_batch_each; a
+        batch that passes costs what verify_batch costs).  Inputs as
+        verify_batch."""
+        pb, vb, count = self._batch_buffers(proofs, Vs)
+        ok = C.create_string_buffer(max(count, 1))
+        rc = self.ctx.lib.bpp_perm_verify_batch_each(self.ctx.h, self.gens.h, self.k, count, _buf(self.label),
+                                                     len(self.label), _buf(pb), _buf(vb), ok)
+        if rc != 6:
+            check(rc, "bpp_perm_verify_batch_each", self.ctx.h)
+        return [b != 0 for b in ok.raw[:count]]
 
     def verify_batch_ptr(self, proofs_ptr: int, V_ptr: int, count: int) -> bool:
         """verify_batch over `count` proofs and their V already in host

@@ -334,6 +334,23 @@ int msm_single_dev(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx,
   return BPP_OK;
 }
 
+// M MSMs over device term lists (offsets d_off, M + 1 entries) with the
+// bucket engine, every window: d_res[m] = MSM m's sum (extended point), one
+// lane per MSM running the Horner chain over its window sums.  Nothing waits.
+int msm_multi_dev(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx, const uint32_t* d_off, uint32_t M,
+                  uint32_t T, uint32_t c, const uint32_t* d_tbl, const uint32_t* d_tbl1, uint32_t n0,
+                  uint32_t* d_res) {
+  const uint32_t W = (254 + c - 1) / c;
+  const MsmGeom g = msm_geom(M, T, c, 0, W);
+  uint32_t* d_ws = nullptr;
+  BPP_TRY(msm_engine(ctx, d_scal, d_pidx, d_off, g.M, g.T, c, 0, W, d_tbl, &d_ws, d_tbl1, n0));
+  {
+    ProfScope ps(ctx, "msm_horner");
+    hipLaunchKernelGGL(k_msm_horner, dim3(grid_for(M, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)d_ws, g, d_res);
+  }
+  return ctx_check_launch(ctx, "k_msm_horner");
+}
+
 // Host scalars -> device d on ctx's stream: staged into ctx's pinned arena by
 // the pool in pieces of 2^17 scalars (4 MB), each piece checked for
 // canonical scalars while it is in cache (when
@@ -717,16 +734,8 @@ int bpp_msm_batch(bpp_ctx* ctx, size_t count, const uint64_t* offsets, const uin
     if (T) BPP_HIP(hipMemcpyAsync(d_idx, point_idx, T * 4, hipMemcpyHostToDevice, ctx->stream));
     BPP_HIP(hipMemcpyAsync(d_off, off32.data(), (count + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     const uint32_t c = msm_choose_c((double)T / (double)count);
-    const uint32_t W = (254 + c - 1) / c;
-    const MsmGeom g = msm_geom((uint32_t)count, (uint32_t)T, c, 0, W);
-    uint32_t* d_ws = nullptr;
-    BPP_TRY(msm_engine(ctx, d_s, (const uint32_t*)d_idx, (const uint32_t*)d_off, g.M, g.T, c, 0, W, tbl->d, &d_ws));
-    {
-      ProfScope ps(ctx, "msm_horner");
-      hipLaunchKernelGGL(k_msm_horner, dim3(grid_for(count, 64)), dim3(64), 0, ctx->stream, (const uint32_t*)d_ws, g,
-                         (uint32_t*)d_res);
-    }
-    BPP_TRY(ctx_check_launch(ctx, "k_msm_horner"));
+    BPP_TRY(msm_multi_dev(ctx, d_s, (const uint32_t*)d_idx, (const uint32_t*)d_off, (uint32_t)count, (uint32_t)T, c,
+                          tbl->d, nullptr, 0xffffffffu, (uint32_t*)d_res));
     return points_compress_p3(ctx, (const uint32_t*)d_res, count, out);
   });
 }

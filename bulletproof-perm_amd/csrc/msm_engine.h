@@ -32,6 +32,11 @@ h25519::ge horner_host_terms(const uint32_t* ws_words, uint32_t Wn, uint32_t nte
 int msm_single_dev(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx, const uint32_t* d_tbl, size_t n,
                    uint32_t c, uint32_t wb, uint32_t Wn, h25519::ge* out, const uint32_t* d_tbl1 = nullptr,
                    uint32_t n0 = 0xffffffffu);
+// M MSMs over device term lists (d_off: M + 1 offsets into d_scal / d_pidx;
+// T terms in all, T x ceil(254 / c) < 2^32) with the bucket engine and one
+// Horner lane per MSM -> d_res [M] extended points.  Queued on ctx's stream.
+int msm_multi_dev(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx, const uint32_t* d_off, uint32_t M,
+                  uint32_t T, uint32_t c, const uint32_t* d_tbl, const uint32_t* d_tbl1, uint32_t n0, uint32_t* d_res);
 int upload_scalars(bpp_ctx* ctx, const uint8_t* scalars, size_t n, const char* name, uint32_t** d_out);
 int points_compress_p3(bpp_ctx* ctx, const uint32_t* d_p3, size_t n, uint8_t* out_host);
 // same, encodings left on the device (d_out: n x 32 B)

@@ -129,6 +129,21 @@ int bpp_perm_verify_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t co
   });
 }
 
+int bpp_perm_verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* label,
+                               size_t llen, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out) {
+  // (no pass is ever left behind by a call that fails)
+  if (ok_out && count) memset(ok_out, 0, count);
+  return bpp_guard(ctx, [&]() -> int {
+    if (!ctx || !G || ((!proofs || !V || !ok_out) && count) || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
+    if (!count) return BPP_OK;
+    BPP_HIP(hipSetDevice(ctx->device));
+    const perm::Circuit C = perm::build(k);
+    const int rc = verify_batch_each(ctx, G, C, label, llen, count, proofs, V, ok_out);
+    if (rc != BPP_OK && rc != BPP_ERR_VERIFY) memset(ok_out, 0, count);
+    return rc;
+  });
+}
+
 int bpp_perm_verify_begin(uint32_t k, size_t count, const uint8_t* label, size_t llen, const uint8_t* proofs,
                           const uint8_t* V, uint8_t* r_out, bpp_verify_job** out) {
   return bpp_guard(nullptr, [&]() -> int {

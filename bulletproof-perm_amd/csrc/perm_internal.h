@@ -162,9 +162,11 @@ int verify_begin(const perm::Circuit& C, const uint8_t* label, size_t llen, size
                  size_t proof_stride, const uint8_t* V, std::unique_ptr<bpp_verify_job>& job);
 int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label, size_t llen, size_t count,
                      const uint8_t* proofs, const uint8_t* V, std::unique_ptr<bpp_verify_job>& job, size_t rfirst = 0,
-                     size_t rcount = SIZE_MAX, bool sync = true);
+                     size_t rcount = SIZE_MAX, bool sync = true, bool each = false);
 int verify_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
                  size_t count, const uint8_t* proofs, const uint8_t* V);
+int verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
+                      size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out);
 int verify_partial(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, const uint8_t seed[32], size_t first,
                    uint32_t wb, uint32_t we, h25519::ge* out);
 int verify_partial_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, const uint8_t seed[32], size_t first,

@@ -370,9 +370,12 @@ int verify_partial(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, con
 // stay in J.bad_h for verify_partial_dev to check after its own
 // synchronisation, so the weights, scalars and MSM are queued right behind
 // the replay with no host round trip (J.rs stays empty).
+// each (verify_batch_each): the decompression also keeps one flag per proof,
+// behind its verdict word in "vj_dbad" and set by the same memset (all ones;
+// cleared where a point of the proof does not decode).
 int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label, size_t llen, size_t count,
                      const uint8_t* proofs, const uint8_t* V, std::unique_ptr<bpp_verify_job>& job,
-                     size_t rfirst, size_t rcount, bool sync) {
+                     size_t rfirst, size_t rcount, bool sync, bool each) {
   job.reset(new bpp_verify_job);
   bpp_verify_job& J = *job;
   if (rcount == SIZE_MAX) rcount = count;
@@ -401,8 +404,10 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
   // (+1: the pad record of the replay's groups past the batch)
   BPP_TRY(ctx_ws(ctx, "vj_rec", (count + 1) * vrec_n(C) * 32, &d_rec));
   BPP_TRY(ctx_ws(ctx, "vj_x", npts * MSM_NIELS_WORDS * 4, &d_x));
-  BPP_TRY(ctx_ws(ctx, "vj_dbad", 8, &d_dbad));
-  BPP_HIP(hipMemsetAsync(d_dbad, 0xff, 8, ctx->stream));
+  const size_t dbad_bytes = 8 + (each ? count * 4 : 0);
+  BPP_TRY(ctx_ws(ctx, "vj_dbad", dbad_bytes, &d_dbad));
+  BPP_HIP(hipMemsetAsync(d_dbad, 0xff, dbad_bytes, ctx->stream));
+  uint32_t* d_pdec = each ? (uint32_t*)d_dbad + 2 : nullptr;
   {
     HostScope hs(ctx, "verify_upload");
     {
@@ -454,7 +459,7 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
         BPP_HIP(hipEventRecord(ctx->vj_ev_chunk[q], ctx->stream));
         BPP_HIP(hipStreamWaitEvent(kid->stream, ctx->vj_ev_chunk[q], 0));
         BPP_TRY(verify_decompress_dev(kid, C, (uint32_t)count, d_pf, d_V, (uint32_t*)d_x,
-                                      (unsigned long long*)d_dbad, (uint32_t)p0, (uint32_t)p1));
+                                      (unsigned long long*)d_dbad, (uint32_t)p0, (uint32_t)p1, 0, ~0u, d_pdec));
       }
       BPP_HIP(hipEventRecord(ctx->vj_ev_dec, kid->stream));
       ctx->vj_dec_pending = true;
@@ -632,6 +637,105 @@ int verify_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const 
   h25519::encode(e, res);
   static const uint8_t zero[32] = {0};
   return memcmp(e, zero, 32) == 0 ? BPP_OK : BPP_ERR_VERIFY;
+}
+
+// Per-proof verdicts of a device job whose batch check (verify_partial_dev)
+// has run and not passed: everything it needs is still on the device -- each
+// proof's own generator scalars ("vs_gen", k_verify_scalars' rows before the
+// merge), its proof-point scalars ("pv_s" behind the merged generators), the
+// decompressed points ("vj_x"), the decode flags (behind "vj_dbad"'s verdict
+// word) and the replay's verdicts (J.bad_h) -- so nothing is uploaded,
+// replayed, decompressed or expanded again.  R_p = sum_i gen[p][i] Gen_i +
+// sum_j s[p][j] X_{p,j} (NG + npt terms, still weighted by w_p != 0) through
+// the multi-MSM engine, in passes of proofs; ok[p] = R_p encodes as 0^32 and
+// proof p decoded and was not replay-rejected.  One synchronisation.
+static int verify_each_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, uint8_t* ok_out) {
+  const uint32_t n_p = J.C.n_p, n0 = (uint32_t)(2 * G->n + 2);
+  const size_t count = J.count, npt = J.npt, NG = 2 * (size_t)n_p + 2, TP = NG + npt;
+  if (n0 + count * npt >= 0x80000000ull) return BPP_ERR_LEN;  // (an engine entry is index | sign << 31)
+  const uint32_t c = msm_choose_c((double)TP), W = (254 + c - 1) / c;
+  // proofs per pass: the engine packs T W below 2^32 and keeps M W 2^(c-1)
+  // buckets (2^22 terms; 2^24 buckets of P3_BYTES = 2.5 GiB)
+  size_t per = std::min(((size_t)1 << 22) / TP, ((size_t)1 << 24) / ((size_t)W << (c - 1)));
+  if (const char* e = getenv("BPP_VERIFY_EACH_PROOFS"))  // (read per call, as BPP_MSM_FB)
+    per = std::min<size_t>(strtoull(e, nullptr, 10), ((size_t)1 << 24) / TP);
+  per = std::min(std::max<size_t>(per, 1), count);
+  void *d_gen, *d_sv, *d_x, *d_dbad, *d_rbad, *d_s, *d_idx, *d_off, *d_res, *d_enc;
+  BPP_TRY(ctx_ws(ctx, "vs_gen", count * NG * 32, &d_gen));
+  BPP_TRY(ctx_ws(ctx, "pv_s", (NG + count * npt) * 32 + 32, &d_sv));
+  BPP_TRY(ctx_ws(ctx, "vj_x", count * npt * MSM_NIELS_WORDS * 4, &d_x));
+  BPP_TRY(ctx_ws(ctx, "vj_dbad", 8 + count * 4, &d_dbad));
+  BPP_TRY(ctx_ws(ctx, "ve_rbad", count * 4, &d_rbad));
+  BPP_TRY(ctx_ws(ctx, "ve_s", per * TP * 32 + 32, &d_s));
+  BPP_TRY(ctx_ws(ctx, "ve_idx", per * TP * 4 + 4, &d_idx));
+  BPP_TRY(ctx_ws(ctx, "ve_off", (per + 1) * 4, &d_off));
+  BPP_TRY(ctx_ws(ctx, "ve_res", count * P3_BYTES, &d_res));
+  BPP_TRY(ctx_ws(ctx, "ve_enc", count * 32, &d_enc));
+  uint32_t* h_ok = nullptr;
+  BPP_TRY(ctx_zc_out(ctx, "ve_ok_h", count, &h_ok));
+  // (the replay's verdicts are in pinned host memory: one copy instead of a
+  // host read per term)
+  BPP_HIP(hipMemcpyAsync(d_rbad, J.bad_h, count * 4, hipMemcpyHostToDevice, ctx->stream));
+  for (size_t p0 = 0; p0 < count; p0 += per) {
+    const uint32_t M = (uint32_t)std::min(per, count - p0);
+    BPP_TRY(verify_each_terms_dev(ctx, J.C, (uint32_t)G->n, n0, (uint32_t)p0, M, (const uint32_t*)d_gen,
+                                  (const uint32_t*)d_sv, (const uint32_t*)d_rbad, (uint32_t*)d_s, (uint32_t*)d_idx,
+                                  (uint32_t*)d_off));
+    BPP_TRY(msm_multi_dev(ctx, (const uint32_t*)d_s, (const uint32_t*)d_idx, (const uint32_t*)d_off, M,
+                          (uint32_t)(M * TP), c, G->d_tbl, (const uint32_t*)d_x, n0, (uint32_t*)d_res + p0 * P3_WORDS));
+  }
+  BPP_TRY(points_compress_p3_dev(ctx, (const uint32_t*)d_res, count, (uint8_t*)d_enc));
+  BPP_TRY(verify_each_verdict_dev(ctx, (uint32_t)count, (const uint32_t*)d_enc, (const uint32_t*)d_dbad + 2,
+                                  (const uint32_t*)d_rbad, (uint8_t*)h_ok));
+  BPP_TRY(ctx_sync(ctx));
+  memcpy(ok_out, h_ok, count);
+  return BPP_OK;
+}
+
+// verify_batch that names the failing proofs: the same job and the same ONE
+// merged MSM; only when that does not pass, each proof's own MSM
+// (verify_each_dev).  ok_out [count]: 1 = proof p verifies alone.
+int verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
+                      size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out) {
+  uint8_t seed[32];
+  if (!perm::verify_seed(seed)) {
+    ctx->err = "getrandom failed";
+    return BPP_ERR_DEVICE;
+  }
+  std::unique_ptr<bpp_verify_job> job;
+  BPP_TRY(verify_begin_dev(ctx, C, label, llen, count, proofs, V, job, 0, SIZE_MAX, false, true));
+  const uint32_t c = msm_choose_c((double)verify_terms(*job));
+  h25519::ge res;
+  // (BPP_ERR_VERIFY: a replay verdict or an undecodable point, found after
+  // the MSM and its synchronisation, with the job's device state complete)
+  const int rc = verify_partial_dev(ctx, G, *job, seed, 0, 0, (254 + c - 1) / c, &res);
+  if (rc != BPP_OK && rc != BPP_ERR_VERIFY) return rc;
+  if (rc == BPP_OK) {
+    uint8_t e[32];
+    h25519::encode(e, res);
+    static const uint8_t zero[32] = {0};
+    if (memcmp(e, zero, 32) == 0) {
+      memset(ok_out, 1, count);
+      return BPP_OK;
+    }
+  }
+  BPP_TRY(verify_each_dev(ctx, G, *job, ok_out));
+  size_t bad = 0, first = count;
+  for (size_t p = count; p-- > 0;)
+    if (!ok_out[p]) {
+      ++bad;
+      first = p;
+    }
+  if (!bad) {
+    // every proof passes alone, yet the weighted sum did not: not reachable
+    // for sums of group elements; no pass is reported
+    memset(ok_out, 0, count);
+    ctx->err = "the batch check failed but no single proof did";
+    return BPP_ERR_DEVICE;
+  }
+  ctx->err = std::to_string(bad) + " of " + std::to_string(count) + " proofs failed, the first at index " +
+             std::to_string(first);
+  return BPP_ERR_VERIFY;
 }
 
 }  // namespace perm_impl

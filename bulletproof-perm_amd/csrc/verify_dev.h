@@ -45,9 +45,11 @@ int verify_replay_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, cons
 // launch per upload chunk).
 // [jlo, jlo + jn): the points of each proof to decode (V_0..V_{m-1} are
 // points 0..m-1, the proof's own m..npt-1; default all of them).
+// d_pdec (optional): [count] words, set nonzero by the caller first; proof
+// p's word is cleared if one of its points does not decode.
 int verify_decompress_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_proofs,
                           const uint32_t* d_V, uint32_t* d_tbl, unsigned long long* d_bad, uint32_t p0 = 0,
-                          uint32_t p1 = ~0u, uint32_t jlo = 0, uint32_t jn = ~0u);
+                          uint32_t p1 = ~0u, uint32_t jlo = 0, uint32_t jn = ~0u, uint32_t* d_pdec = nullptr);
 // The 52-word shared transcript prefix for verify_replay_dev.
 void verify_init_state(const perm::Circuit& C, const uint8_t* label, size_t llen, uint32_t out[52]);
 // out[i] = sum over the nb blocks (stride words apart) of block[b][i], i < n
@@ -59,3 +61,15 @@ int verify_sum_blocks_dev(bpp_ctx* ctx, uint32_t nb, uint32_t n, const uint32_t*
 // records (poly.hip).  seed: 8 words, may be pinned host memory.
 int verify_scalars_dev_rec(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_rec,
                            const uint32_t* seed, uint64_t first, uint32_t* d_sc);
+// Per-proof verdicts (bpp_perm_verify_batch_each).  Term lists of proofs [p0,
+// p0 + M) for the multi-MSM engine: d_scal / d_idx [M][NG + npt] (generator
+// scalars d_gen[p][NG] on generator slots of a set of gn generators, then the
+// proof-point scalars d_sv[NG + p npt ..) on points n0 + p npt + j), d_off
+// [M + 1] = m (NG + npt); zero scalars where d_rbad[p] (replay-rejected).
+int verify_each_terms_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t gn, uint32_t n0, uint32_t p0, uint32_t M,
+                          const uint32_t* d_gen, const uint32_t* d_sv, const uint32_t* d_rbad, uint32_t* d_scal,
+                          uint32_t* d_idx, uint32_t* d_off);
+// ok[p] = d_enc[p] is 0^32 and d_pdec[p] != 0 and d_rbad[p] == 0, one byte per
+// proof (ok may be pinned host memory, written in place).
+int verify_each_verdict_dev(bpp_ctx* ctx, uint32_t count, const uint32_t* d_enc, const uint32_t* d_pdec,
+                            const uint32_t* d_rbad, uint8_t* ok);

@@ -236,7 +236,9 @@ __global__ void __launch_bounds__(64) k_verify_replay_post(uint32_t count, uint3
 // Decompress every proof point straight from the uploaded proofs and V into
 // the MSM's Niels table (point i = p npt + j in vpts_n order), so that it
 // needs nothing from the replay and runs beside it on another stream.
-// *bad = the smallest index of an undecodable encoding (~0 if none).
+// *bad = the smallest index of an undecodable encoding (~0 if none); pdec
+// (optional, [count] words the caller set nonzero): pdec[p] = 0 for every
+// proof p with such a point (every lane stores the same value).
 // (VD_WPE waves per SIMD: unconstrained, the compiler takes 244 VGPRs for the
 // inverse square root, 2 waves per SIMD; config 5, interleaved A/B passes:
 // 0.594-0.607 ms unconstrained, 0.554-0.559 at 3 (167 VGPRs, spills outside
@@ -250,7 +252,7 @@ __global__ void __launch_bounds__(64) k_verify_replay_post(uint32_t count, uint3
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VD_WPE)))
 k_verify_decompress(size_t i0, size_t i1, uint32_t jlo, uint32_t jn, uint32_t m, uint32_t lg, uint32_t npt,
                     const uint32_t* __restrict__ proofs, uint32_t pw, const uint32_t* __restrict__ V,
-                    uint32_t* __restrict__ tbl, unsigned long long* __restrict__ bad) {
+                    uint32_t* __restrict__ tbl, unsigned long long* __restrict__ bad, uint32_t* __restrict__ pdec) {
   // lane -> (proof p, point j = jlo + j' with j' < jn): the V points (jlo =
   // 0, jn = m) or the proof's own points (jlo = m) can go separately
   const size_t t = i0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -271,6 +273,7 @@ k_verify_decompress(size_t i0, size_t i1, uint32_t jlo, uint32_t jn, uint32_t m,
   ge_p3 P;
   if (!ge_ristretto_decode(w, P)) {
     atomicMin(bad, (unsigned long long)i);
+    if (pdec) pdec[p] = 0u;
     P = ge_identity();
   }
   store_niels(tbl, (uint32_t)i, ge_niels_from_affine(P.X, P.Y));  // (Z = 1 after decode)
@@ -337,7 +340,7 @@ int verify_sum_blocks_dev(bpp_ctx* ctx, uint32_t nb, uint32_t n, const uint32_t*
 
 int verify_decompress_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_proofs,
                           const uint32_t* d_V, uint32_t* d_tbl, unsigned long long* d_bad, uint32_t p0, uint32_t p1,
-                          uint32_t jlo, uint32_t jn) {
+                          uint32_t jlo, uint32_t jn, uint32_t* d_pdec) {
   p1 = std::min(p1, count);
   const uint32_t npt = vpts_n(C);
   if (jlo >= npt) return BPP_OK;
@@ -347,7 +350,81 @@ int verify_decompress_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, 
   {
     ProfScope ps(ctx, "verify_decompress");
     hipLaunchKernelGGL(k_verify_decompress, dim3(grid_for(i1 - i0, 64)), dim3(64), 0, ctx->stream, i0, i1, jlo, jn, C.m,
-                       C.lg, npt, d_proofs, (uint32_t)(perm::proof_len(C.k) / 4), d_V, d_tbl, d_bad);
+                       C.lg, npt, d_proofs, (uint32_t)(perm::proof_len(C.k) / 4), d_V, d_tbl, d_bad, d_pdec);
   }
   return ctx_check_launch(ctx, "k_verify_decompress");
+}
+
+// ---------------------------------------------------------------------------
+// Per-proof verdicts (bpp_perm_verify_batch_each, slow path): each proof's own
+// MSM over the scalars the batch already left on the device.
+//
+// Proofs [p0, p0 + M) -> M contiguous term lists of TP = NG + npt terms each
+// for the multi-MSM engine: proof p's generator scalars gen[p][0..NG)
+// (k_verify_scalars' rows, before the merge) and its proof-point scalars
+// sv[NG + p npt ..); point indices = the generator slots (G[0..n_p), H[0..n_p),
+// B, Bb of a generator set of gn >= n_p), then n0 + p npt + j into the
+// decompressed proof points; off[m] = m TP.  A replay-rejected proof's record
+// is unspecified, so its scalars go in as zero (the engine takes canonical
+// scalars only; the proof's verdict is false whatever its sum).
+__global__ void __launch_bounds__(256) k_verify_each_terms(uint32_t p0, uint32_t M, uint32_t NG, uint32_t npt,
+                                                           uint32_t n_p, uint32_t gn, uint32_t n0,
+                                                           const uint32_t* __restrict__ gen,
+                                                           const uint32_t* __restrict__ sv,
+                                                           const uint32_t* __restrict__ rbad,
+                                                           uint32_t* __restrict__ scal, uint32_t* __restrict__ idx,
+                                                           uint32_t* __restrict__ off) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, TP = NG + npt;
+  if (t <= M) off[t] = t * TP;
+  if (t >= M * TP) return;
+  const uint32_t m = t / TP, i = t % TP, p = p0 + m;
+  uint32_t w[8];
+  if (i < NG)
+    ld8(gen + 8 * ((size_t)p * NG + i), w);
+  else
+    ld8(sv + 8 * ((size_t)NG + (size_t)p * npt + (i - NG)), w);
+  if (rbad[p]) {
+    _Pragma("unroll") for (int k = 0; k < 8; ++k) w[k] = 0;
+  }
+  st8(scal + 8 * (size_t)t, w);
+  idx[t] = i < n_p ? i : i < 2 * n_p ? gn + (i - n_p) : i < NG ? 2 * gn + (i - 2 * n_p) : n0 + p * npt + (i - NG);
+}
+
+// One lane per proof: ok[p] = its sum encodes as 0^32 (what the batch tests)
+// AND every point of it decoded (an undecodable point went in as the
+// identity) AND the replay accepted it (a rejected proof's scalars are zero,
+// and zero scalars sum to the identity).
+__global__ void __launch_bounds__(64) k_verify_each_verdict(uint32_t count, const uint32_t* __restrict__ enc,
+                                                            const uint32_t* __restrict__ pdec,
+                                                            const uint32_t* __restrict__ rbad,
+                                                            uint8_t* __restrict__ ok) {
+  const uint32_t p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= count) return;
+  uint32_t w[8];
+  ld8(enc + 8 * (size_t)p, w);
+  ok[p] = (w8_zero(w) && pdec[p] != 0 && rbad[p] == 0) ? 1 : 0;
+}
+
+int verify_each_terms_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t gn, uint32_t n0, uint32_t p0, uint32_t M,
+                          const uint32_t* d_gen, const uint32_t* d_sv, const uint32_t* d_rbad, uint32_t* d_scal,
+                          uint32_t* d_idx, uint32_t* d_off) {
+  if (!M) return BPP_OK;
+  const uint32_t NG = 2 * C.n_p + 2, npt = vpts_n(C);
+  {
+    ProfScope ps(ctx, "verify_each_terms");
+    hipLaunchKernelGGL(k_verify_each_terms, dim3(grid_for((size_t)M * (NG + npt), 256)), dim3(256), 0, ctx->stream, p0,
+                       M, NG, npt, C.n_p, gn, n0, d_gen, d_sv, d_rbad, d_scal, d_idx, d_off);
+  }
+  return ctx_check_launch(ctx, "k_verify_each_terms");
+}
+
+int verify_each_verdict_dev(bpp_ctx* ctx, uint32_t count, const uint32_t* d_enc, const uint32_t* d_pdec,
+                            const uint32_t* d_rbad, uint8_t* ok) {
+  if (!count) return BPP_OK;
+  {
+    ProfScope ps(ctx, "verify_each_verdict");
+    hipLaunchKernelGGL(k_verify_each_verdict, dim3(grid_for(count, 64)), dim3(64), 0, ctx->stream, count, d_enc,
+                       d_pdec, d_rbad, ok);
+  }
+  return ctx_check_launch(ctx, "k_verify_each_verdict");
 }

@@ -375,6 +375,26 @@ int bpp_perm_verify(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, const uint8_t* 
  * weights", "No inversions"). */
 int bpp_perm_verify_batch(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* label,
                           size_t llen, const uint8_t* proofs, const uint8_t* V);
+/* Batch verification that names the failing proofs: ok_out[p] (count bytes
+ * of ordinary host memory) = 1 if proof p verifies, else 0 -- what
+ * bpp_perm_verify returns for proof p alone.
+ *   BPP_OK          every proof verifies; ok_out is all ones.
+ *   BPP_ERR_VERIFY  at least one proof fails; ok_out is fully written.
+ *   any other error ok_out is all zero (whenever it was given): no call
+ *                   leaves a pass behind that it did not establish.
+ * Arguments as bpp_perm_verify_batch, and ok_out == NULL with count > 0 is
+ * BPP_ERR_ARG; all checked before any device work.  count == 0: BPP_OK,
+ * nothing written.
+ * A batch that passes costs what bpp_perm_verify_batch costs: the same
+ * upload, replay and ONE merged MSM, no further launch or wait.  Only when
+ * that check does not pass, every proof's own MSM (2 n_p + 2 generators +
+ * its m + 8 + 2 log2 n_p points) runs over the scalars and decompressed
+ * points the batch left on the device -- no second upload, replay,
+ * decompression or scalar expansion -- in passes of at most 2^22 / terms
+ * proofs (BPP_VERIFY_EACH_PROOFS=<n> overrides the proofs per pass), with one
+ * more wait at the end (DESIGN.md §5 "Per-proof verdicts"). */
+int bpp_perm_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* label,
+                               size_t llen, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out);
 
 /* Batch verification split for several GPUs (north_star: "the single large
  * verifier MSM partitions its bucket windows across GPUs"; reference verify
@@ -391,8 +411,9 @@ int bpp_perm_verify_begin(uint32_t k, size_t count, const uint8_t* label, size_t
  * be NULL).  r is byte-identical to bpp_perm_verify_begin's.  The job keeps
  * its records and points in ctx's workspaces: it is valid for
  * bpp_perm_verify_partial on the same ctx until the next verification on
- * that ctx -- bpp_perm_verify_begin_dev, bpp_perm_verify or
- * bpp_perm_verify_batch, which all replay through the same workspaces
+ * that ctx -- bpp_perm_verify_begin_dev, bpp_perm_verify,
+ * bpp_perm_verify_batch or bpp_perm_verify_batch_each, which all replay
+ * through the same workspaces
  * (BPP_ERR_ARG after that; a call refused for its arguments supersedes
  * nothing) -- and
  * bpp_perm_verify_scalars rejects it (BPP_ERR_ARG).  The proof points are
