@@ -684,6 +684,95 @@ class PermProver:
         return part.raw
 
 
+
+class DeckProver:
+    """Public-deck shuffle proof (bpp_deck_*): V_0..V_{k-1} commit to a
+    permutation of the PUBLIC deck, V_k to the transcript challenge -- k + 1
+    commitments and k - 1 gates where PermProver's two-half statement takes
+    2k + 1 and 2k.  deck: None (the cards 1..k) or k canonical 32-byte scalars
+    (or their 32 k bytes joined), shared by every proof."""
+
+    def __init__(self, gens: Gens, k: int, deck=None, label: bytes = b"bp-perm", ctx: "Context | None" = None):
+        self.gens = gens
+        self.ctx = ctx or gens.ctx
+        self.k = k
+        self.label = label
+        if deck is not None:
+            deck = bytes(deck) if isinstance(deck, (bytes, bytearray)) else _join(deck, 32, "deck")
+            if len(deck) != 32 * k:
+                raise ValueError("deck: expected k scalars of 32 bytes")
+        self.deck = deck
+        self.proof_len = int(self.ctx.lib.bpp_deck_proof_len(k))
+        self.m = k + 1
+
+    def _deck(self):
+        return _buf(self.deck) if self.deck is not None else None
+
+    def prove_batch(self, perms, seeds32: bytes | None = None, gammas=None, raw: bool = False):
+        """perms[p] = k indices, V_i of proof p committing to deck[perms[p][i]];
+        gammas[p] = the k blindings of V_0..V_{k-1} (None: drawn); seeds32 = 32
+        bytes per proof (None: the OS CSPRNG).  Returns what
+        PermProver.prove_batch returns; the batch's secrets are wiped."""
+        count = len(perms)
+        if gammas is not None and len(gammas) != count:
+            raise ValueError("perms and gammas must have one entry per proof")
+        if seeds32 is not None and len(seeds32) != 32 * count:
+            raise ValueError("seeds32 must hold 32 bytes per proof")
+        gb = None
+        if gammas is not None:
+            gb = b"".join(x if isinstance(x, (bytes, bytearray)) else _join(x, 32, "gammas") for x in gammas)
+            if len(gb) != 32 * self.k * count:
+                raise ValueError("gammas: expected k scalars of 32 bytes per proof")
+        flat = [int(i) for p in perms for i in p]
+        if len(flat) != self.k * count:
+            raise ValueError("perms: expected k indices per proof")
+        pm = (C.c_uint32 * max(len(flat), 1))(*flat)
+        pf = C.create_string_buffer(max(self.proof_len * count, 1))
+        V = C.create_string_buffer(max(32 * self.m * count, 1))
+        check(self.ctx.lib.bpp_deck_prove_batch(self.ctx.h, self.gens.h, self.k, count, self._deck(), pm,
+                                                _buf(gb) if gb is not None else None,
+                                                _buf(seeds32) if seeds32 is not None else None,
+                                                _buf(self.label), len(self.label), pf, V),
+              "bpp_deck_prove_batch", self.ctx.h)
+        praw, vraw = pf.raw[:self.proof_len * count], V.raw[:32 * self.m * count]
+        if raw:
+            return praw, vraw
+        return ([praw[i * self.proof_len:(i + 1) * self.proof_len] for i in range(count)],
+                [vraw[i * 32 * self.m:(i + 1) * 32 * self.m] for i in range(count)])
+
+    def verify(self, proof: bytes, V) -> bool:
+        vb = _join(V, 32, "V")
+        rc = self.ctx.lib.bpp_deck_verify(self.ctx.h, self.gens.h, self.k, self._deck(), _buf(self.label),
+                                          len(self.label), _buf(proof), len(proof), _buf(vb))
+        if rc == 6:
+            return False
+        check(rc, "bpp_deck_verify", self.ctx.h)
+        return True
+
+    _batch_buffers = PermProver._batch_buffers
+
+    def verify_batch(self, proofs, Vs) -> bool:
+        """proofs / Vs: sequences of per-proof bytes, or the two contiguous
+        buffers (prove_batch(..., raw=True))."""
+        pb, vb, count = self._batch_buffers(proofs, Vs)
+        rc = self.ctx.lib.bpp_deck_verify_batch(self.ctx.h, self.gens.h, self.k, count, self._deck(),
+                                                _buf(self.label), len(self.label), _buf(pb), _buf(vb))
+        if rc == 6:
+            return False
+        check(rc, "bpp_deck_verify_batch", self.ctx.h)
+        return True
+
+    def verify_batch_each(self, proofs, Vs) -> "list[bool]":
+        """One verdict per proof, what verify(proofs[i], Vs[i]) returns
+        (bpp_deck_verify_batch_each).  Inputs as verify_batch."""
+        pb, vb, count = self._batch_buffers(proofs, Vs)
+        ok = C.create_string_buffer(max(count, 1))
+        rc = self.ctx.lib.bpp_deck_verify_batch_each(self.ctx.h, self.gens.h, self.k, count, self._deck(),
+                                                     _buf(self.label), len(self.label), _buf(pb), _buf(vb), ok)
+        if rc != 6:
+            check(rc, "bpp_deck_verify_batch_each", self.ctx.h)
+        return [b != 0 for b in ok.raw[:count]]
+
 class VerifyJob:
     """Parsed proofs with their transcripts replayed: on the host
     (bpp_perm_verify_begin, ctx=None; no GPU) or on the GPU of `ctx`

@@ -95,6 +95,11 @@ SIGNATURES = {
     "bpp_perm_verify": (i32, [vp, vp, u32, vp, sz, vp, sz, vp]),
     "bpp_perm_verify_batch": (i32, [vp, vp, u32, sz, vp, sz, vp, vp]),
     "bpp_perm_verify_batch_each": (i32, [vp, vp, u32, sz, vp, sz, vp, vp, vp]),
+    "bpp_deck_proof_len": (sz, [u32]),
+    "bpp_deck_prove_batch": (i32, [vp, vp, u32, sz, vp, vp, vp, vp, vp, sz, vp, vp]),
+    "bpp_deck_verify": (i32, [vp, vp, u32, vp, vp, sz, vp, sz, vp]),
+    "bpp_deck_verify_batch": (i32, [vp, vp, u32, sz, vp, vp, sz, vp, vp]),
+    "bpp_deck_verify_batch_each": (i32, [vp, vp, u32, sz, vp, vp, sz, vp, vp, vp]),
     "bpp_perm_verify_begin": (i32, [u32, sz, vp, sz, vp, vp, vp, C.POINTER(vp)]),
     "bpp_perm_verify_begin_dev": (i32, [vp, u32, sz, vp, sz, vp, vp, vp, C.POINTER(vp)]),
     "bpp_perm_verify_terms": (i32, [vp, C.POINTER(sz)]),

@@ -25,11 +25,45 @@ struct Entry {
 
 struct Circuit {
   uint32_t k = 0, n = 0, n_p = 0, lg = 0, Q = 0, m = 0;
+  uint32_t nv = 0;  // commitments absorbed before the x_perm challenge: 2k (two halves) or k (deck circuit)
   std::vector<Entry> WL, WR, WO, WV;
-  std::vector<hsc::Sc> c;  // c[Q-1] = -x set per proof
+  std::vector<hsc::Sc> c;  // c[Q-1] = -x set per proof (deck circuit: c[Q-2] = deck_product(x) too)
+  // deck circuit (build_deck) only: the public deck and its transcript digest
+  bool deck = false;
+  std::vector<hsc::Sc> cards;
+  uint8_t deck_digest[32] = {0};
 };
 
 Circuit build(uint32_t k);
+
+// The deck circuit (bpp_deck_*): V_0..V_{k-1} commit to a permutation of the
+// PUBLIC deck d_0..d_{k-1}, V_k to x.  One product chain prod (v_i - x) of
+// n = k - 1 gates inside the proof; the deck's own product D = prod (d_i - x)
+// is a per-proof constant both sides compute.  v = [d_pi(0)..d_pi(k-1), x],
+// m = k + 1, Q = 2k:
+//   rows q = g (g < n):  a_L[g] = v_0 - x (g = 0) or a_O[g-1]
+//   rows q = n + g:      a_R[g] = v_{g+1} - x
+//   row 2k - 2:          a_O[k-2] = D
+//   row 2k - 1:          v_k = x  (c = -x: the last row, as in build)
+// n_p = max(4, next_pow2(k - 1)): no batched kernel has run below n_p = 4
+// (build's k = 2).  deck: k canonical scalars (32 bytes each; the caller has
+// checked them), or nullptr for 1..k.  deck_digest =
+// SHAKE256("bpperm-deck" || le32 k || d_0 || .. || d_{k-1})[0..32], absorbed
+// by transcript_prefix.
+Circuit build_deck(uint32_t k, const uint8_t* deck);
+// D = prod_i (d_i - x) of a deck circuit
+hsc::Sc deck_product(const Circuit& C, const hsc::Sc& x);
+// v = [cards[pi], x]; gate values of the one chain
+void witness_deck(const Circuit& C, const std::vector<uint32_t>& pi, const hsc::Sc& x, std::vector<hsc::Sc>& v,
+                  std::vector<hsc::Sc>& aL, std::vector<hsc::Sc>& aR, std::vector<hsc::Sc>& aO);
+// What every proof's transcript absorbs after Transcript(label) and before
+// V_0: dom-sep("acp v1", n_p), and the deck circuit's "deck" digest -- which
+// is what keeps a two-half proof of k' cards and a deck proof of 2k' cards
+// (same m, n_p and byte length) from verifying as each other.
+inline void transcript_prefix(const Circuit& C, merlin::Transcript& tr) {
+  tr.arithmetic_domain_sep(C.n_p);
+  if (C.deck) tr.append("deck", C.deck_digest, 32);
+}
 
 // v = [1..k, pi(1..k), x]; gate values (sound create_a)
 void witness(const Circuit& C, const std::vector<uint32_t>& pi, const hsc::Sc& x, std::vector<hsc::Sc>& v,
@@ -123,7 +157,8 @@ void draw_prover_randomness_x8(const Circuit& C, const Seed seeds[8], RandomDraw
 // out[j]->pi is left as it is.
 void draw_prover_host_x8(const Circuit& C, const Seed seeds[8], RandomDraws* const out[8], bool with_pi = true);
 
-size_t proof_len(uint32_t k);
+size_t proof_len(uint32_t k);        // two-half circuit of k cards
+size_t proof_len(const Circuit& C);  // either circuit: 32 (13 + 2 lg)
 
 // Batch-verification weight of proof p (its index in the batch) with weight
 // challenge r_p (its own transcript's "t-check-weight"):

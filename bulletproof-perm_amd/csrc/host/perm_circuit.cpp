@@ -27,6 +27,7 @@ Circuit build(uint32_t k) {
   while ((1u << C.lg) < C.n_p) ++C.lg;
   C.Q = 4 * k + 2;
   C.m = 2 * k + 1;
+  C.nv = 2 * k;
   const uint32_t X = 2 * k;
   const Sc one = hsc::one(), neg1 = hsc::neg(hsc::one());
   C.c.assign(C.Q, hsc::zero());
@@ -65,6 +66,76 @@ Circuit build(uint32_t k) {
   for (auto* W : {&C.WL, &C.WR, &C.WO, &C.WV})
     for (Entry& e : *W) e.valR = hsc::to_mont(e.val);
   return C;
+}
+
+Circuit build_deck(uint32_t k, const uint8_t* deck) {
+  Circuit C;
+  C.deck = true;
+  C.k = k;
+  C.n = k - 1;
+  C.n_p = 4;
+  while (C.n_p < C.n) C.n_p *= 2;
+  while ((1u << C.lg) < C.n_p) ++C.lg;
+  C.Q = 2 * k;
+  C.m = k + 1;
+  C.nv = k;
+  const uint32_t X = k, n = C.n;
+  const Sc one = hsc::one(), neg1 = hsc::neg(hsc::one());
+  C.c.assign(C.Q, hsc::zero());
+  for (uint32_t g = 0; g < n; ++g) {  // a_L rows
+    C.WL.push_back({g, g, one});
+    if (g == 0) {
+      C.WV.push_back({g, 0, one});
+      C.WV.push_back({g, X, neg1});
+    } else {
+      C.WO.push_back({g, g - 1, neg1});
+    }
+  }
+  for (uint32_t g = 0; g < n; ++g) {  // a_R rows
+    C.WR.push_back({n + g, g, one});
+    C.WV.push_back({n + g, g + 1, one});
+    C.WV.push_back({n + g, X, neg1});
+  }
+  C.WO.push_back({2 * k - 2, k - 2, one});  // a_O[k-2] = D (c[2k-2], per proof)
+  C.WV.push_back({2 * k - 1, X, one});
+  for (auto* W : {&C.WL, &C.WR, &C.WO, &C.WV})
+    for (Entry& e : *W) e.valR = hsc::to_mont(e.val);
+  C.cards.resize(k);
+  for (uint32_t i = 0; i < k; ++i) {
+    if (deck)
+      memcpy(C.cards[i].v, deck + 32 * (size_t)i, 32);  // (canonical Sc == its 32 bytes)
+    else
+      C.cards[i] = hsc::from_u64(i + 1);
+  }
+  merlin::Shake256 sh;
+  sh.update((const uint8_t*)"bpperm-deck", 11);
+  const uint8_t kb[4] = {(uint8_t)k, (uint8_t)(k >> 8), (uint8_t)(k >> 16), (uint8_t)(k >> 24)};
+  sh.update(kb, 4);
+  sh.update((const uint8_t*)C.cards.data(), 32 * (size_t)k);
+  sh.read(C.deck_digest, 32);
+  return C;
+}
+
+Sc deck_product(const Circuit& C, const Sc& x) {
+  Sc D = hsc::one();
+  for (const Sc& d : C.cards) D = hsc::mul(D, hsc::sub(d, x));
+  return D;
+}
+
+void witness_deck(const Circuit& C, const std::vector<uint32_t>& pi, const Sc& x, std::vector<Sc>& v,
+                  std::vector<Sc>& aL, std::vector<Sc>& aR, std::vector<Sc>& aO) {
+  const uint32_t k = C.k;
+  v.assign(C.m, hsc::zero());
+  for (uint32_t i = 0; i < k; ++i) v[i] = C.cards[pi[i]];
+  v[k] = x;
+  aL.assign(C.n_p, hsc::zero());
+  aR.assign(C.n_p, hsc::zero());
+  aO.assign(C.n_p, hsc::zero());
+  for (uint32_t g = 0; g + 1 < k; ++g) {
+    aL[g] = g == 0 ? hsc::sub(v[0], x) : aO[g - 1];
+    aR[g] = hsc::sub(v[g + 1], x);
+    aO[g] = hsc::mul(aL[g], aR[g]);
+  }
 }
 
 // gate values from v = [chain A's k values, chain B's k values, x]
@@ -177,6 +248,8 @@ size_t proof_len(uint32_t k) {
   // A_I A_O S T1 T3 T4 T5 T6 | tau_x mu t_hat | (L_j R_j) x lg | a b
   return 32 * (8 + 3 + 2 * lg + 2);
 }
+
+size_t proof_len(const Circuit& C) { return 32 * (8 + 3 + 2 * (size_t)C.lg + 2); }
 
 hsc::Sc batch_weight(const uint8_t seed[32], uint64_t p, const hsc::Sc& r) {
   merlin::Shake256 sh;

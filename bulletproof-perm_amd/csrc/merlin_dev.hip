@@ -65,10 +65,10 @@ __global__ void __launch_bounds__(64) k_ipa_transcript_step(uint32_t P, uint8_t*
 // after Transcript::new(label) + arithmetic_domain_sep(n_p) (init: 50 state
 // words + pos + pos_begin), append_point("V", V_i) for i < 2k and
 // x_perm = challenge_scalar("x_perm") (perm_prove.hip pedersen_V; the
-// reference's create, circuit_lib.rs:139-186, in sound form).  venc: [P][2k]
+// reference's create, circuit_lib.rs:139-186, in sound form).  venc: [P][nv]
 // encodings on the device.  states_out: [P][MERLIN_DEV_STATE_BYTES],
 // xperm_out: [P][8] canonical words (both may be pinned host memory).
-__global__ void __launch_bounds__(64) k_prove_v_transcript(uint32_t P, uint32_t k, const uint32_t* __restrict__ init,
+__global__ void __launch_bounds__(64) k_prove_v_transcript(uint32_t P, uint32_t nv, const uint32_t* __restrict__ init,
                                                            const uint32_t* __restrict__ venc,
                                                            uint8_t* __restrict__ states_out,
                                                            uint32_t* __restrict__ xperm_out) {
@@ -83,8 +83,8 @@ __global__ void __launch_bounds__(64) k_prove_v_transcript(uint32_t P, uint32_t 
     s.pos = init[50];
     s.pos_begin = init[51];
   }
-  const uint32_t* V = venc + (size_t)p * 2 * k * 8;
-  for (uint32_t j = 0; j < 2 * k; ++j) {
+  const uint32_t* V = venc + (size_t)p * nv * 8;
+  for (uint32_t j = 0; j < nv; ++j) {
     const uint4 a = reinterpret_cast<const uint4*>(V + 8 * j)[0], b = reinterpret_cast<const uint4*>(V + 8 * j)[1];
     const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     s.append32("V", 1, w);
@@ -98,12 +98,12 @@ __global__ void __launch_bounds__(64) k_prove_v_transcript(uint32_t P, uint32_t 
   sc_store(xperm_out + 8 * (size_t)p, x);
 }
 
-int prove_v_transcript_dev(bpp_ctx* ctx, uint32_t P, uint32_t k, const uint32_t* init, const uint32_t* d_venc,
+int prove_v_transcript_dev(bpp_ctx* ctx, uint32_t P, uint32_t nv, const uint32_t* init, const uint32_t* d_venc,
                            uint8_t* states_out, uint32_t* xperm_out) {
   if (!P) return BPP_OK;
   {
     ProfScope ps(ctx, "prove_v_transcript");
-    hipLaunchKernelGGL(k_prove_v_transcript, dim3((P + 63) / 64), dim3(64), 0, ctx->stream, P, k, init, d_venc,
+    hipLaunchKernelGGL(k_prove_v_transcript, dim3((P + 63) / 64), dim3(64), 0, ctx->stream, P, nv, init, d_venc,
                        states_out, xperm_out);
   }
   return ctx_check_launch(ctx, "k_prove_v_transcript");

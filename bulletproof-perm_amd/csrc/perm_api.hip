@@ -38,7 +38,7 @@ int bpp_perm_prove_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t cou
       return BPP_ERR_ARG;
     std::vector<perm::Seed> sd(count);
     for (size_t i = 0; i < count; ++i) sd[i] = perm::Seed::u64(seeds[i]);
-    return prove_batch_api(ctx, G, k, sd, label, llen, proofs_out, V_out);
+    return prove_batch_api(ctx, G, perm::build(k), sd, label, llen, proofs_out, V_out);
   });
 }
 
@@ -47,7 +47,7 @@ int bpp_perm_prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, si
   return bpp_guard(ctx, [&]() -> int {
     if (!ctx || !G || ((!proofs_out || !V_out) && count) || (!label && llen) || !k_in_range(k))
       return BPP_ERR_ARG;
-    return prove_batch_entropy(ctx, G, k, count, seeds32, label, llen, proofs_out, V_out);
+    return prove_batch_entropy(ctx, G, perm::build(k), count, seeds32, label, llen, proofs_out, V_out);
   });
 }
 
@@ -90,7 +90,110 @@ int bpp_perm_prove_shuffle_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, si
     if (!ctx || !G) return BPP_ERR_ARG;
     if (!count) return BPP_OK;
     const ShuffleIn sh = {cards, perms, gammas};
-    return prove_batch_entropy(ctx, G, k, count, seeds32, label, llen, proofs_out, V_out, &sh);
+    return prove_batch_entropy(ctx, G, perm::build(k), count, seeds32, label, llen, proofs_out, V_out, &sh);
+  });
+}
+
+// --- the deck circuit (perm.h build_deck): V_0..V_{k-1} commit to a
+// permutation of the call's PUBLIC deck
+
+// "every deck card is a canonical scalar" (deck == nullptr: 1..k)
+static int deck_canonical(bpp_ctx* ctx, uint32_t k, const uint8_t* deck) {
+  Sc t;
+  for (uint32_t i = 0; deck && i < k; ++i)
+    if (!hsc::from_canonical(t, deck + 32 * (size_t)i)) {
+      if (ctx) ctx->err = "deck card " + std::to_string(i) + " is not a canonical scalar";
+      return BPP_ERR_NONCANONICAL;
+    }
+  return BPP_OK;
+}
+
+size_t bpp_deck_proof_len(uint32_t k) {
+  if (!k_in_range(k)) return 0;
+  uint32_t n_p = 4, lg = 2;  // n_p = max(4, next_pow2(k - 1))
+  for (; n_p < k - 1; n_p *= 2) ++lg;
+  return 32 * (8 + 3 + 2 * (size_t)lg + 2);
+}
+
+int bpp_deck_prove_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* deck,
+                         const uint32_t* perms, const uint8_t* gammas, const uint8_t* seeds32, const uint8_t* label,
+                         size_t llen, uint8_t* proofs_out, uint8_t* V_out) {
+  return bpp_guard(ctx, [&]() -> int {
+    if (((!perms || !proofs_out || !V_out) && count) || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
+    // the whole witness is checked before any device work and before any
+    // output byte is written (bpp_perm_prove_shuffle_batch's checks, in its
+    // order): every perm a bijection on [0, k), every deck card and supplied
+    // blinding a canonical scalar
+    std::vector<int> bad(count, BPP_OK);
+    par::for_each(count, [&](size_t p) {
+      std::vector<uint8_t> seen(k, 0);
+      const uint32_t* pm = perms + p * (size_t)k;
+      for (uint32_t i = 0; i < k; ++i) {
+        if (pm[i] >= k || seen[pm[i]]) {
+          bad[p] = BPP_ERR_ARG;
+          return;
+        }
+        seen[pm[i]] = 1;
+      }
+      Sc t;
+      if (gammas)
+        for (uint32_t i = 0; i < k; ++i)
+          if (!hsc::from_canonical(t, gammas + (p * (size_t)k + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
+      t = hsc::zero();
+    });
+    for (size_t p = 0; p < count; ++p)
+      if (bad[p] == BPP_ERR_ARG) {
+        if (ctx) ctx->err = "deck proof " + std::to_string(p) + ": perm is not a bijection on [0, k)";
+        return BPP_ERR_ARG;
+      }
+    BPP_TRY(deck_canonical(ctx, k, deck));
+    for (size_t p = 0; p < count; ++p)
+      if (bad[p] != BPP_OK) {
+        if (ctx) ctx->err = "deck proof " + std::to_string(p) + ": non-canonical blinding";
+        return bad[p];
+      }
+    if (!ctx || !G) return BPP_ERR_ARG;
+    if (!count) return BPP_OK;
+    const ShuffleIn sh = {nullptr, perms, gammas};
+    return prove_batch_entropy(ctx, G, perm::build_deck(k, deck), count, seeds32, label, llen, proofs_out, V_out, &sh);
+  });
+}
+
+int bpp_deck_verify(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, const uint8_t* deck, const uint8_t* label,
+                    size_t llen, const uint8_t* proof, size_t proof_len, const uint8_t* V) {
+  return bpp_guard(ctx, [&]() -> int {
+    if (!ctx || !G || !proof || !V || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
+    BPP_TRY(deck_canonical(ctx, k, deck));
+    if (proof_len != bpp_deck_proof_len(k)) return BPP_ERR_VERIFY;
+    BPP_HIP(hipSetDevice(ctx->device));
+    return verify_batch(ctx, G, perm::build_deck(k, deck), label, llen, 1, proof, V);
+  });
+}
+
+int bpp_deck_verify_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* deck,
+                          const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V) {
+  return bpp_guard(ctx, [&]() -> int {
+    if (!ctx || !G || ((!proofs || !V) && count) || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
+    BPP_TRY(deck_canonical(ctx, k, deck));
+    if (!count) return BPP_OK;
+    BPP_HIP(hipSetDevice(ctx->device));
+    return verify_batch(ctx, G, perm::build_deck(k, deck), label, llen, count, proofs, V);
+  });
+}
+
+int bpp_deck_verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* deck,
+                               const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
+                               uint8_t* ok_out) {
+  // (no pass is ever left behind by a call that fails)
+  if (ok_out && count) memset(ok_out, 0, count);
+  return bpp_guard(ctx, [&]() -> int {
+    if (!ctx || !G || ((!proofs || !V || !ok_out) && count) || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
+    BPP_TRY(deck_canonical(ctx, k, deck));
+    if (!count) return BPP_OK;
+    BPP_HIP(hipSetDevice(ctx->device));
+    const int rc = verify_batch_each(ctx, G, perm::build_deck(k, deck), label, llen, count, proofs, V, ok_out);
+    if (rc != BPP_OK && rc != BPP_ERR_VERIFY) memset(ok_out, 0, count);
+    return rc;
   });
 }
 

@@ -48,7 +48,7 @@ inline void serialize(const perm::Circuit& C, const Proof& P, uint8_t* out) {
 }
 
 inline bool deserialize(const perm::Circuit& C, const uint8_t* in, size_t len, const uint8_t* V, Proof& P) {
-  if (len != perm::proof_len(C.k)) return false;
+  if (len != perm::proof_len(C)) return false;
   size_t o = 0;
   auto pt = [&](Enc32& e) {
     memcpy(e.data(), in + o, 32);
@@ -88,12 +88,12 @@ inline void proof_points(const Proof& P, uint8_t* out) {
   for (auto& r : P.ipa.R) add(r);
 }
 
-// A caller-supplied shuffle (bpp_perm_prove_shuffle_batch): this batch's
-// slices of the caller's arrays, validated by the entry point.
+// A caller-supplied shuffle (bpp_perm_prove_shuffle_batch, bpp_deck_prove_batch):
+// this batch's slices of the caller's arrays, validated by the entry point.
 struct ShuffleIn {
-  const uint8_t* cards;   // [P][k] canonical scalars
+  const uint8_t* cards;   // [P][k] canonical scalars; nullptr with the deck circuit (the deck is the circuit's)
   const uint32_t* perms;  // [P][k], each a bijection on [0, k)
-  const uint8_t* gammas;  // nullptr (drawn), or [P][2k] canonical scalars
+  const uint8_t* gammas;  // nullptr (drawn), or [P][C.nv] canonical scalars
 };
 
 // One proof's Fiat-Shamir challenges (verify_replay).
@@ -148,10 +148,10 @@ namespace perm_impl BPP_HIDDEN {
 // --- prover (perm_prove.hip)
 int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
                 const uint8_t* label, size_t llen, std::vector<Proof>& Ps, const ShuffleIn* sh = nullptr);
-int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, const std::vector<perm::Seed>& seeds,
+int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
                     const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out, bool wipe = false,
                     const ShuffleIn* sh = nullptr);
-int prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* seeds32,
+int prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, size_t count, const uint8_t* seeds32,
                         const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out,
                         const ShuffleIn* sh = nullptr);
 int prove_wipe(bpp_ctx* ctx);

@@ -103,6 +103,11 @@ bool dev_v_transcript() {
   return e && atoi(e) != 0;
 }
 
+bool deck_host_witness() {
+  const char* e = getenv("BPP_DECK_HOST_WITNESS");
+  return e && atoi(e) != 0;
+}
+
 // Per-proof prover state carried between the lockstep phases.  The states
 // (and their vectors) persist per driver thread across batches: a host
 // profile of 8 batches in flight spent ~20 % of the host CPU in malloc /
@@ -120,7 +125,7 @@ struct ProverScratch {
   // not reuse them
   std::vector<uint32_t> idx, map, off;
   size_t key_P = 0;
-  uint32_t key_k = 0;
+  uint32_t key_k = 0, key_gates = 0;  // (k and C.n: the two circuits of one k differ)
   const bpp_gens* key_G = nullptr;
   size_t key_n = 0;
 };
@@ -257,17 +262,21 @@ struct ProveBatch {
   const ShuffleIn* const sh;  // a caller's shuffle: read by draws_upload and Vx_witness only
   const size_t P = seeds.size();
   const uint32_t k = C.k, n_p = C.n_p, m = C.m;
+  const uint32_t nv = C.nv;          // V commitments before x_perm (2k; the deck circuit's k)
   const uint32_t per = 3 + 5 * n_p;  // A_I/A_O/S terms per proof
-  // the witness on the device (k_witness) while its prefix products fit the
-  // workgroup's LDS; the host restatement beyond that
-  const bool dev_witness = (2 * (size_t)k + 512) * 32 <= 64 * 1024;
+  // the witness on the device (k_witness, k_witness_deck) while its prefix
+  // products fit the workgroup's LDS; the host restatement beyond that
+  // (BPP_DECK_HOST_WITNESS=1: the deck circuit's host witness at every k, for
+  // the test that compares the two paths)
+  const bool dev_witness = C.deck ? k <= DECK_WITNESS_DEV_MAX && !deck_host_witness()
+                                  : (2 * (size_t)k + 512) * 32 <= 64 * 1024;
   // (a plain reference: pool workers must reach THIS thread's states, a
   // thread_local named inside their lambdas would be their own)
   std::vector<std::unique_ptr<ProverState>>& S = prover_states_tl();
   ProverScratch& scr = prover_scratch_tl();
   std::vector<merlin::Transcript*> trs = std::vector<merlin::Transcript*>(P);  // this batch's (lockstep_phase)
   // device arrays: the drawn blindings [P][m], the A_I/A_O/S scalars [P][per], pi, the V phase's values /
-  // blindings [P][2k] and gamma_2k / 2 [P] ("pv_v", "pv_g", "pv_gx", taken once), and the IPA inputs
+  // blindings [P][nv] and gamma_nv / 2 [P] ("pv_v", "pv_g", "pv_gx", taken once), and the IPA inputs
   uint32_t *d_gamma = nullptr, *d_s = nullptr, *d_pi = nullptr;
   uint32_t *d_v = nullptr, *d_g = nullptr, *d_gx_half = nullptr;
   uint32_t *d_l = nullptr, *d_r = nullptr, *d_hf = nullptr;
@@ -317,8 +326,9 @@ int ProveBatch::draws_upload() {
   // shuffle appends its cards and V blindings (32-byte aligned: the kernels
   // read them with 16-byte loads) to the same buffer and the same copy
   const size_t rng_bytes = P * tlen + (size_t)P * k * 4;
-  const size_t sh_off = (rng_bytes + 31) & ~(size_t)31, cards_bytes = (size_t)P * k * 32;
-  const size_t gam_bytes = sh && sh->gammas ? (size_t)P * 2 * k * 32 : 0;
+  // (the deck circuit's cards are the call's, public: "pb_deck" below)
+  const size_t sh_off = (rng_bytes + 31) & ~(size_t)31, cards_bytes = sh && sh->cards ? (size_t)P * k * 32 : 0;
+  const size_t gam_bytes = sh && sh->gammas ? (size_t)P * nv * 32 : 0;
   const size_t in_bytes = sh ? sh_off + cards_bytes + gam_bytes : rng_bytes;
   BPP_TRY(ctx_ws(ctx, "pb_rng_in", in_bytes, &dst));
   d_pi = (uint32_t*)((uint8_t*)dst + P * tlen);
@@ -343,15 +353,15 @@ int ProveBatch::draws_upload() {
       const size_t i = 8 * gi + j;
       if (sh) {
         S[i]->d.pi.assign(sh->perms + i * k, sh->perms + (i + 1) * k);
-        memcpy(stage + sh_off + i * 32 * (size_t)k, sh->cards + i * 32 * (size_t)k, 32 * (size_t)k);
+        if (sh->cards) memcpy(stage + sh_off + i * 32 * (size_t)k, sh->cards + i * 32 * (size_t)k, 32 * (size_t)k);
         if (sh->gammas)
-          memcpy(stage + sh_off + cards_bytes + i * 64 * (size_t)k, sh->gammas + i * 64 * (size_t)k, 64 * (size_t)k);
-        if (!dev_witness) {  // (canonical Sc == its 32 bytes)
+          memcpy(stage + sh_off + cards_bytes + i * 32 * (size_t)nv, sh->gammas + i * 32 * (size_t)nv, 32 * (size_t)nv);
+        if (!dev_witness && sh->cards) {  // (canonical Sc == its 32 bytes)
           S[i]->cards.resize(k);
           memcpy(S[i]->cards.data(), sh->cards + i * 32 * (size_t)k, 32 * (size_t)k);
         }
       }
-      S[i]->tr.arithmetic_domain_sep(n_p);
+      perm::transcript_prefix(C, S[i]->tr);
       uint64_t tm[7];
       draw_template(sd[j], tm);
       memcpy(stage + i * tlen, tm, tlen);
@@ -361,10 +371,24 @@ int ProveBatch::draws_upload() {
   BPP_TRY(ctx_h2d_staged(ctx, dst, stage, in_bytes));  // (pis follows the templates)
   // (the V commitments' inputs in the same launch: values 1..k and pi + 1,
   // gamma copies and gamma_2k / 2, into the V phase's workspaces)
-  BPP_TRY(ctx_ws(ctx, "pv_v", (size_t)P * 2 * k * 32, (void**)&d_v));
-  BPP_TRY(ctx_ws(ctx, "pv_g", (size_t)P * 2 * k * 32, (void**)&d_g));
-  BPP_TRY(ctx_ws(ctx, "pv_gx", (size_t)P * 32, (void**)&d_gx_half));  // gamma_2k / 2 for V_2k
-  if (sh) {
+  BPP_TRY(ctx_ws(ctx, "pv_v", (size_t)P * nv * 32, (void**)&d_v));
+  BPP_TRY(ctx_ws(ctx, "pv_g", (size_t)P * nv * 32, (void**)&d_g));
+  BPP_TRY(ctx_ws(ctx, "pv_gx", (size_t)P * 32, (void**)&d_gx_half));  // gamma_nv / 2 for V_nv
+  if (C.deck) {
+    // the draws alone, then the V inputs deck[perm] from the call's deck (and
+    // the caller's blindings over the drawn gamma_0..k-1)
+    if (!sh) {
+      ctx->err = "prove_batch: the deck circuit takes a caller's perms";
+      return BPP_ERR_ARG;
+    }
+    void* d_deck = nullptr;
+    BPP_TRY(ctx_ws(ctx, "pb_deck", (size_t)k * 32, &d_deck));
+    BPP_TRY(ctx_h2d_const(ctx, "pb_deck", d_deck, C.cards.data(), (size_t)k * 32));
+    const uint8_t* dsh = (const uint8_t*)dst + sh_off;
+    BPP_TRY(draws_dev(ctx, C, (uint32_t)P, (const uint64_t*)dst, seeds[0].len, per, d_gamma, d_s));
+    BPP_TRY(deck_inputs_dev(ctx, C, (uint32_t)P, (const uint32_t*)d_deck, d_pi,
+                            gam_bytes ? (const uint32_t*)dsh : nullptr, d_gamma, d_v, d_g, d_gx_half));
+  } else if (sh) {
     // the draws alone, then the V inputs from the uploaded cards and perms
     // (and the caller's blindings over the drawn gamma_0..2k-1)
     const uint8_t* dsh = (const uint8_t*)dst + sh_off;
@@ -379,14 +403,16 @@ int ProveBatch::draws_upload() {
   return BPP_OK;
 }
 
-// V_0..V_2k-1 of every proof: one fixed-base launch over device inputs
-// (values 1..k, pi + 1 and gamma, written by k_draws), encodings back to the host
+// V_0..V_{nv-1} of every proof (nv = 2k, or the deck circuit's k): one
+// fixed-base launch over device inputs (values 1..k, pi + 1 and gamma, written
+// by k_draws; a caller's, by k_shuffle_inputs / k_deck_inputs), encodings back
+// to the host
 int ProveBatch::pedersen_V() {
   HostScope hs(ctx, "pb_pedersen_V");
-  const size_t nv = (size_t)P * 2 * k;
+  const size_t nv = (size_t)P * this->nv;  // (all proofs')
   uint32_t* denc = nullptr;  // encodings written in place by k_compress_p3 (ctx_zc_out)
   BPP_TRY(ctx_zc_out(ctx, "pv_enc_h", nv * 32, &denc));
-  // the 2k V appends and x_perm on the device (k_prove_v_transcript, one
+  // the nv V appends and x_perm on the device (k_prove_v_transcript, one
   // lane per proof; the host's share of a batch was ~10 us of CPU per
   // proof here, its largest transcript phase): encodings to the device,
   // copied back for the proofs, and the transcript states imported after
@@ -411,7 +437,7 @@ int ProveBatch::pedersen_V() {
       BPP_TRY(ctx_zc_out(ctx, "pv_states", P * MERLIN_DEV_STATE_BYTES, &hs_));
       BPP_TRY(ctx_zc_out(ctx, "pv_xperm", P * 32, &h_xp));
       h_st = (uint8_t*)hs_;
-      BPP_TRY(prove_v_transcript_dev(ctx, (uint32_t)P, k, h_init, (const uint32_t*)dvenc, h_st, h_xp));
+      BPP_TRY(prove_v_transcript_dev(ctx, (uint32_t)P, this->nv, h_init, (const uint32_t*)dvenc, h_st, h_xp));
     }
   }
   std::vector<Enc32>& V = scr.V;
@@ -422,26 +448,26 @@ int ProveBatch::pedersen_V() {
     memcpy(V.data(), denc, nv * 32);
   }
   par::for_each(P, [&](size_t p) {
-    Ps[p].V.assign(V.begin() + p * 2 * k, V.begin() + (p + 1) * 2 * k);
+    Ps[p].V.assign(V.begin() + p * this->nv, V.begin() + (p + 1) * this->nv);
     if (dev_v) {
       merlin_state_import(S[p]->tr, h_st + p * MERLIN_DEV_STATE_BYTES);
       memcpy(&S[p]->x_perm, h_xp + 8 * p, 32);  // (canonical Sc == its 32 bytes)
     }
   });
   if (!dev_v) {
-    // the 2k "V" appends and x_perm of eight proofs at a time in lockstep
+    // the nv "V" appends and x_perm of eight proofs at a time in lockstep
     // on the 8-way Keccak (byte-identical; 2.5x on this phase's ~26 us of
     // permutations per proof)
     merlin::lockstep_phase(
-        trs, for_groups, 2 * k, [](size_t) { return "V"; },
-        [&](size_t p, size_t i) { return V[p * 2 * k + i].data(); }, 1, [](size_t) { return "x_perm"; },
+        trs, for_groups, this->nv, [](size_t) { return "V"; },
+        [&](size_t p, size_t i) { return V[p * this->nv + i].data(); }, 1, [](size_t) { return "x_perm"; },
         [&](size_t p, size_t, const Sc& c) { S[p]->x_perm = c; });
   }
   return BPP_OK;
 }
 
-// V_2k = commit(x_perm, gamma_2k): halved scalars (x_perm / 2 from the
-// host, gamma_2k / 2 from k_draws), encoded as 2 (C / 2) on the host
+// V_nv = commit(x_perm, gamma_nv): halved scalars (x_perm / 2 from the
+// host, gamma_nv / 2 from k_draws), encoded as 2 (C / 2) on the host
 int ProveBatch::pedersen_Vx_witness() {
   HostScope hs(ctx, "pb_pedersen_Vx_witness");
   std::vector<Sc> vh(2 * P);  // x_perm / 2 (V_2k), then x_perm (the device witness)
@@ -452,7 +478,12 @@ int ProveBatch::pedersen_Vx_witness() {
   uint32_t* d_vh = nullptr;
   BPP_TRY(upload_sc(ctx, vh, "pv_vx", &d_vh));
   // (a caller's shuffle: both chains' values, as committed)
-  if (dev_witness) BPP_TRY(witness_dev(ctx, C, (uint32_t)P, d_pi, d_vh + 8 * P, per, d_s, sh ? d_v : nullptr));
+  if (dev_witness) {
+    if (C.deck)
+      BPP_TRY(witness_deck_dev(ctx, C, (uint32_t)P, d_v, d_vh + 8 * P, per, d_s));
+    else
+      BPP_TRY(witness_dev(ctx, C, (uint32_t)P, d_pi, d_vh + 8 * P, per, d_s, sh ? d_v : nullptr));
+  }
   uint32_t* h_p3 = nullptr;  // written in place by the kernel (ctx_zc_out)
   BPP_TRY(ctx_zc_out(ctx, "pv_p3_h", P * P3_BYTES, &h_p3));
   BPP_TRY(pedersen_dev(ctx, G, d_vh, d_gx_half, P, nullptr, h_p3));
@@ -464,7 +495,9 @@ int ProveBatch::pedersen_Vx_witness() {
     S[p]->tr.append_point("V", Vx[p].data());
     if (!dev_witness) {
       ProverState& st = *S[p];
-      if (sh)
+      if (C.deck)
+        perm::witness_deck(C, st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
+      else if (sh)
         perm::witness(C, st.cards.data(), st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
       else
         perm::witness(C, st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
@@ -484,7 +517,7 @@ int ProveBatch::msm_AI_AO_S() {
   std::vector<uint32_t>&idx = scr.idx, &map = scr.map, &off = scr.off;
   const uint32_t n = C.n;                       // real gates; n_p - n padding gates are zero
   const uint32_t per_c = 3 + 3 * n + 2 * n_p;  // MSM terms per proof
-  if (scr.key_P != P || scr.key_k != k || scr.key_G != G || scr.key_n != G->n) {
+  if (scr.key_P != P || scr.key_k != k || scr.key_gates != n || scr.key_G != G || scr.key_n != G->n) {
     idx.resize((size_t)P * per_c);
     map.resize((size_t)P * per_c);
     off.resize(3 * P + 1);
@@ -510,6 +543,7 @@ int ProveBatch::msm_AI_AO_S() {
     off[3 * P] = (uint32_t)(P * per_c);
     scr.key_P = P;
     scr.key_k = k;
+    scr.key_gates = n;
     scr.key_G = G;
     scr.key_n = G->n;
   }
@@ -648,6 +682,11 @@ namespace perm_impl BPP_HIDDEN {
 // blindings) instead of the seed's: no pi stream is read, the uploaded cards
 // and perms feed k_shuffle_inputs and k_witness_cards, and the V commitments
 // take full-width values; every other step is the same launch sequence.
+// With the deck circuit (perm::build_deck; sh carries perms and optional
+// blindings, no cards) the V phase commits deck[perm] over C.nv = k
+// commitments (k_deck_inputs), the witness is the one chain of k_witness_deck
+// or perm::witness_deck, and the transcripts start from the deck digest
+// (perm::transcript_prefix); the steps after V_k are the same.
 int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
                 const uint8_t* label, size_t llen, std::vector<Proof>& Ps, const ShuffleIn* sh) {
   const size_t P = seeds.size();
@@ -670,15 +709,15 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
 
 // wipe: prove_wipe after the batch, on ctx (this thread) and on every child
 // context inside its sub-batch thread (whose prover states are its own)
-int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, const std::vector<perm::Seed>& seeds,
+int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
                     const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out, bool wipe,
                     const ShuffleIn* sh) {
   const size_t count = seeds.size();
   if (!count) return BPP_OK;
-  const perm::Circuit C = perm::build(k);
+  const uint32_t k = C.k;
   BPP_TRY(gens_cover(ctx, G, C.n_p));
   BPP_HIP(hipSetDevice(ctx->device));
-  const size_t pl = perm::proof_len(k);
+  const size_t pl = perm::proof_len(C);
   std::vector<Proof>& Ps = proofs_tl();  // reused batch after batch (ProverState note; the workers see this thread's)
   Ps.resize(count);
   // Sub-batches in flight on S streams (child contexts), one host thread
@@ -712,8 +751,8 @@ int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, const std::vect
         std::vector<perm::Seed> part(seeds.begin() + b, seeds.begin() + e);
         ShuffleIn shs;  // this sub-batch's slices of the caller's witness
         if (sh)
-          shs = {sh->cards + b * 32 * (size_t)k, sh->perms + b * (size_t)k,
-                 sh->gammas ? sh->gammas + b * 64 * (size_t)k : nullptr};
+          shs = {sh->cards ? sh->cards + b * 32 * (size_t)k : nullptr, sh->perms + b * (size_t)k,
+                 sh->gammas ? sh->gammas + b * 32 * (size_t)C.nv : nullptr};
         rcs[s] = prove_batch(kc, G, C, part, label, llen, sub, sh ? &shs : nullptr);
         if (rcs[s] == BPP_OK)
           for (size_t i = b; i < e; ++i) Ps[i] = std::move(sub[i - b]);
@@ -746,7 +785,7 @@ int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, const std::vect
 // with its wipe, then the entropy and the seeds zeroed -- they live on this
 // stack and heap, where bpp_debug_secret_residue does not look -- and ctx's
 // own wipe.
-int prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* seeds32,
+int prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, size_t count, const uint8_t* seeds32,
                         const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out, const ShuffleIn* sh) {
   std::vector<uint8_t> ent;
   if (!seeds32 && count) {
@@ -759,7 +798,7 @@ int prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t coun
   }
   std::vector<perm::Seed> sd(count);
   for (size_t i = 0; i < count; ++i) sd[i] = perm::Seed::bytes32(seeds32 + 32 * i);
-  const int rc = prove_batch_api(ctx, G, k, sd, label, llen, proofs_out, V_out, true, sh);
+  const int rc = prove_batch_api(ctx, G, C, sd, label, llen, proofs_out, V_out, true, sh);
   if (!ent.empty()) memset(ent.data(), 0, ent.size());
   for (perm::Seed& x : sd) memset(x.b, 0, sizeof x.b);
   const int wrc = prove_wipe(ctx);

@@ -98,12 +98,12 @@ namespace perm_impl BPP_HIDDEN {
 // Verifier, phase 1: replay one proof's transcript (all Fiat-Shamir
 // challenges; point validation as validate_and_append_point).
 static bool verify_replay(const perm::Circuit& C, const Proof& P, merlin::Transcript& tr, VerifyChallenges& ch) {
-  const uint32_t k = C.k, n_p = C.n_p, m = C.m;
+  const uint32_t nv = C.nv, n_p = C.n_p, m = C.m;
   if (P.V.size() != m || P.ipa.L.size() != C.lg || P.ipa.R.size() != C.lg) return false;
-  tr.arithmetic_domain_sep(n_p);
-  for (uint32_t j = 0; j < 2 * k; ++j) tr.append_point("V", P.V[j].data());
+  perm::transcript_prefix(C, tr);
+  for (uint32_t j = 0; j < nv; ++j) tr.append_point("V", P.V[j].data());
   ch.x_perm = tr.challenge_scalar("x_perm");
-  tr.append_point("V", P.V[2 * k].data());
+  tr.append_point("V", P.V[nv].data());
   if (!tr.validate_and_append_point("A_I", P.AI.data())) return false;
   if (!tr.validate_and_append_point("A_O", P.AO.data())) return false;
   if (!tr.validate_and_append_point("S", P.S.data())) return false;
@@ -164,6 +164,7 @@ static void verify_expand(const perm::Circuit& C, const Proof& P, const VerifyCh
                         zWV = perm::zW(C.WV, zq, m);
   std::vector<Sc> c = C.c;
   c[C.Q - 1] = hsc::neg(ch.x_perm);
+  if (C.deck) c[C.Q - 2] = perm::deck_product(C, ch.x_perm);
   const Sc a = P.ipa.a, b = P.ipa.b;
   const Sc uyaR = hsc::to_mont(mul(mul(U, Y), a)), ubR = hsc::to_mont(mul(U, b)), xR_ = hsc::to_mont(x),
            u2R = hsc::to_mont(U2);
@@ -216,7 +217,7 @@ int verify_begin(const perm::Circuit& C, const uint8_t* label, size_t llen, size
   J.ch.resize(count);
   std::vector<uint8_t> ok(count, 0);
   par::for_each(count, [&](size_t p) {
-    if (!deserialize(C, proofs + p * proof_stride, perm::proof_len(C.k), V + p * 32 * C.m, J.Ps[p])) return;
+    if (!deserialize(C, proofs + p * proof_stride, perm::proof_len(C), V + p * 32 * C.m, J.Ps[p])) return;
     merlin::Transcript tr(label, llen);
     VerifyChallenges& ch = J.ch[p];
     if (!verify_replay(C, J.Ps[p], tr, ch)) return;
@@ -391,7 +392,7 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
   if (count > (1u << 26) || rfirst > count || rcount > count - rfirst) return BPP_ERR_ARG;
   J.dgen = ++ctx->vjob_gen;
   if (!count) return BPP_OK;
-  const size_t plen = perm::proof_len(C.k), vbytes = (size_t)C.m * 32, npts = count * J.npt;
+  const size_t plen = perm::proof_len(C), vbytes = (size_t)C.m * 32, npts = count * J.npt;
   bpp_ctx* kid = nullptr;
   BPP_TRY(ctx_child(ctx, VJ_CHILD, &kid));
   if (!ctx->vj_ev_dec) BPP_HIP(hipEventCreateWithFlags(&ctx->vj_ev_dec, hipEventDisableTiming));

@@ -58,3 +58,18 @@ int shuffle_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const u
 // (k_witness_cards; d_pi is not read).
 int witness_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_pi, const uint32_t* d_x,
                 uint32_t per, uint32_t* d_sc, const uint32_t* d_vals = nullptr);
+
+// The deck circuit (perm.h build_deck).  deck_inputs_dev (k_deck_inputs), after
+// draws_dev without d_v on the same stream: d_v [P][k] = deck[perm] (d_deck [k]
+// canonical scalars, the call's; d_perm [P][k] u32 < k), d_g [P][k] = the drawn
+// gamma_0..k-1 or, when d_gammas ([P][k]) is non-null, the caller's, which then
+// replace d_gamma's ([P][k + 1]) too; d_gx_half [P] = gamma_k / 2.
+int deck_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_deck, const uint32_t* d_perm,
+                    const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v, uint32_t* d_g, uint32_t* d_gx_half);
+// witness_deck_dev (k_witness_deck): a_L, a_R, a_O of the one chain over d_vals
+// (d_v above) into their slots of d_sc, for k <= DECK_WITNESS_DEV_MAX -- the
+// kernel's own LDS budget, (k + 2 x 256) x 32 B <= 64 KB; the host witness
+// (perm::witness_deck) beyond.
+#define DECK_WITNESS_DEV_MAX 1536u
+int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals, const uint32_t* d_x,
+                     uint32_t per, uint32_t* d_sc);

@@ -485,13 +485,20 @@ __global__ void __launch_bounds__(64 * (VC_W + 1)) k_verify_consts(uint32_t coun
 #ifndef VS_WPE
 #define VS_WPE 4
 #endif
-__global__ void __launch_bounds__(POLY_T) __attribute__((amdgpu_waves_per_eu(VS_WPE))) k_verify_scalars(
-    uint32_t n_p, uint32_t m, uint32_t Q, uint32_t lg, const uint32_t* __restrict__ rec,
-    const uint32_t* __restrict__ kc, const uint32_t* __restrict__ cp, const uint32_t* __restrict__ ce,
-    const uint32_t* __restrict__ cR, uint32_t* __restrict__ gen, uint32_t* __restrict__ sc_out, uint32_t NG,
-    uint32_t npt) {
+//
+// DECK (the deck circuit, perm.h build_deck): the circuit's second per-proof
+// constant c[Q-2] = D = prod_i (deck_i - x_perm) over the call's public deck
+// (deck [k] canonical scalars in device memory, once per call): per-lane
+// strided partial products, then a tree over the workgroup in LDS (blockDim
+// more scalars behind the reduction scratch), added to <z^Q, c> by lane 0.
+template <bool DECK>
+FE_INLINE void verify_scalars_body(uint32_t* lds, uint32_t n_p, uint32_t m, uint32_t Q, uint32_t lg,
+                                   const uint32_t* __restrict__ rec, const uint32_t* __restrict__ kc,
+                                   const uint32_t* __restrict__ cp, const uint32_t* __restrict__ ce,
+                                   const uint32_t* __restrict__ cR, uint32_t* __restrict__ gen,
+                                   uint32_t* __restrict__ sc_out, uint32_t NG, uint32_t npt,
+                                   const uint32_t* __restrict__ deck, uint32_t k) {
   __builtin_amdgcn_s_setprio(2);  // (ahead of the proof-point decompression beside it)
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const uint32_t NY = min(n_p, (uint32_t)POW_LO);
   uint32_t* zt = lds;                // [Q + 1] z^e, Montgomery
   uint32_t* yt = zt + 8 * (Q + 1);   // [NY] y^e
@@ -580,6 +587,24 @@ __global__ void __launch_bounds__(POLY_T) __attribute__((amdgpu_waves_per_eu(VS_
   VS_T(5);
   sc_block_sum<2>(acc, red);
   VS_T(6);
+  if constexpr (DECK) {
+    uint32_t* prod = red + (POLY_T / 64) * 2 * 8;  // [blockDim] partial products
+    const sc nxp = ldk(VK_NXP);
+    sc pr = oneR;
+    for (uint32_t i = threadIdx.x; i < k; i += blockDim.x)
+      pr = sc_mont(pr, sc_add(sc_to_mont(sc_load(deck + 8 * (size_t)i)), nxp));
+    __syncthreads();  // (red: lane 0 has read the block sums)
+    sc_store(prod + 8 * threadIdx.x, pr);
+    __syncthreads();
+    for (uint32_t n = blockDim.x; n > 1;) {  // any blockDim: the upper half folds onto the lower
+      const uint32_t h = (n + 1) / 2;
+      if (threadIdx.x < n / 2)
+        sc_store(prod + 8 * threadIdx.x, sc_mont(sc_load(prod + 8 * threadIdx.x), sc_load(prod + 8 * (threadIdx.x + h))));
+      n = h;
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) acc[1] = sc_add(acc[1], sc_mont(sc_load(zp + 8 * (Q - 2)), sc_load(prod)));
+  }
   if (threadIdx.x == 0) {
     // B: wt (r F t_hat - r x^2 (delta' + F zc) + w F (a b - t_hat)); B_blinding: wt F (r tau_x + mu)
     const sc tB =
@@ -588,6 +613,25 @@ __global__ void __launch_bounds__(POLY_T) __attribute__((amdgpu_waves_per_eu(VS_
     sc_store(gen + 8 * (gb + 2 * n_p + 1), sc_from_mont(ldk(VK_BB)));
   }
   VS_T(7);
+}
+
+__global__ void __launch_bounds__(POLY_T) __attribute__((amdgpu_waves_per_eu(VS_WPE))) k_verify_scalars(
+    uint32_t n_p, uint32_t m, uint32_t Q, uint32_t lg, const uint32_t* __restrict__ rec,
+    const uint32_t* __restrict__ kc, const uint32_t* __restrict__ cp, const uint32_t* __restrict__ ce,
+    const uint32_t* __restrict__ cR, uint32_t* __restrict__ gen, uint32_t* __restrict__ sc_out, uint32_t NG,
+    uint32_t npt) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  verify_scalars_body<false>(lds, n_p, m, Q, lg, rec, kc, cp, ce, cR, gen, sc_out, NG, npt, nullptr, 0);
+}
+
+// dynamic LDS = k_verify_scalars' + blockDim x 32 B
+__global__ void __launch_bounds__(POLY_T) __attribute__((amdgpu_waves_per_eu(VS_WPE))) k_verify_scalars_deck(
+    uint32_t n_p, uint32_t m, uint32_t Q, uint32_t lg, const uint32_t* __restrict__ rec,
+    const uint32_t* __restrict__ kc, const uint32_t* __restrict__ cp, const uint32_t* __restrict__ ce,
+    const uint32_t* __restrict__ cR, uint32_t* __restrict__ gen, uint32_t* __restrict__ sc_out, uint32_t NG,
+    uint32_t npt, const uint32_t* __restrict__ deck, uint32_t k) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  verify_scalars_body<true>(lds, n_p, m, Q, lg, rec, kc, cp, ce, cR, gen, sc_out, NG, npt, deck, k);
 }
 
 // sc_out[i] = sum_p gen[p][i] (one workgroup per generator column)
@@ -768,6 +812,126 @@ __global__ void __launch_bounds__(256) k_witness_cards(uint32_t k, uint32_t n_p,
   witness_body<true>(lds, k, n_p, per, nullptr, vals, xs, sc_out);
 }
 
+// The deck circuit's witness (perm.h build_deck; host restatement
+// witness_deck), one proof per workgroup, ONE chain: with d[i] = vals[p][i] -
+// x (vals [P][k] canonical: the values the V phase commits, deck[perm], written
+// by k_deck_inputs) and their inclusive prefix products A, gate g < k - 1 is
+// (A[g], d[g+1], A[g+1]); padding gates are zero.  The prefix-product scan of
+// witness_body: per-lane chunks, then a Hillis-Steele scan of the chunk
+// products in LDS.  dynamic LDS = (k + 2 blockDim) x 32 B -- half the
+// two-chain kernel's -- so at 256 lanes the device witness reaches k <= 1536
+// ((1536 + 512) x 32 B = 64 KB; DECK_WITNESS_DEV_MAX); the host witness beyond.
+__global__ void __launch_bounds__(256) k_witness_deck(uint32_t k, uint32_t n_p, uint32_t per,
+                                                     const uint32_t* __restrict__ vals,
+                                                     const uint32_t* __restrict__ xs, uint32_t* __restrict__ sc_out) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  uint32_t* pref = lds;          // [k] prefix products: Montgomery, then canonical
+  uint32_t* scan = lds + 8 * k;  // [2 buffers][blockDim] chunk products
+  const uint32_t p = blockIdx.x, nt = blockDim.x, t = threadIdx.x;
+  const sc x = sc_load(xs + 8 * (size_t)p);
+  sc one = sc_zero();
+  one.v[0] = 1;
+  const sc oneR = sc_to_mont(one);
+  const uint32_t* vp = vals + 8 * (size_t)p * k;
+  auto dd = [&](uint32_t i) { return sc_sub(sc_load(vp + 8 * (size_t)i), x); };
+  // lane t owns elements [i0, i1); nch lanes own any
+  const uint32_t C = (k + nt - 1) / nt, nch = (k + C - 1) / C, i0 = min(t * C, k), i1 = min(i0 + C, k);
+  sc run = oneR;
+  for (uint32_t i = i0; i < i1; ++i) {
+    run = sc_mont(run, sc_to_mont(dd(i)));
+    sc_store(pref + 8 * i, run);
+  }
+  uint32_t cur = 0;
+  sc_store(scan + 8 * t, run);
+  __syncthreads();
+  for (uint32_t d = 1; d < nch; d <<= 1) {
+    const uint32_t* src = scan + 8 * nt * cur;
+    uint32_t* dst = scan + 8 * nt * (cur ^ 1);
+    if (t < nch) {
+      sc a = sc_load(src + 8 * t);
+      if (t >= d) a = sc_mont(sc_load(src + 8 * (t - d)), a);
+      sc_store(dst + 8 * t, a);
+    }
+    cur ^= 1;
+    __syncthreads();
+  }
+  // canonical prefixes: mont(e, P) for the canonical product e of the earlier
+  // chunks and Montgomery P is e P canonical
+  if (t < nch) {
+    const sc e = t > 0 ? sc_from_mont(sc_load(scan + 8 * nt * cur + 8 * (t - 1))) : one;
+    for (uint32_t i = i0; i < i1; ++i) sc_store(pref + 8 * i, sc_mont(e, sc_load(pref + 8 * i)));
+  }
+  __syncthreads();
+  uint32_t* o = sc_out + 8 * (size_t)p * per;
+  for (uint32_t g = t; g < n_p; g += nt) {
+    sc aL = sc_zero(), aR = sc_zero(), aO = sc_zero();
+    if (g + 1 < k) {
+      aL = sc_load(pref + 8 * g);
+      aR = dd(g + 1);
+      aO = sc_load(pref + 8 * (g + 1));
+    }
+    sc_store(o + 8 * (1 + g), aL);
+    sc_store(o + 8 * (1 + n_p + g), aR);
+    sc_store(o + 8 * (2 + 2 * n_p + g), aO);
+  }
+}
+
+// The V phase's inputs of a deck proof (bpp_deck_prove_batch), one lane per
+// commitment input (P x m lanes, m = k + 1, after k_draws with v = nullptr on
+// the same stream): v[p][i] = deck[perm[p][i]] (i < k; the deck [k] is the
+// call's, shared by its proofs; perm is a bijection on [0, k), checked by the
+// entry point before any device work -- the index is clamped all the same),
+// g[p][i] = the blinding of V_i: the drawn gamma[p][i], or the caller's
+// gammas[p][i] ([P][k]), which then also replaces gamma[p][i] (k_poly_coef
+// reads it for tau_x); gx_half[p] = gamma_k / 2 (always drawn).
+__global__ void __launch_bounds__(256) k_deck_inputs(uint32_t P, uint32_t k, const uint32_t* __restrict__ deck,
+                                                    const uint32_t* __restrict__ perm,
+                                                    const uint32_t* __restrict__ gammas,
+                                                    uint32_t* __restrict__ gamma, uint32_t* __restrict__ v,
+                                                    uint32_t* __restrict__ g, uint32_t* __restrict__ gx_half) {
+  const uint32_t m = k + 1;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)P * m) return;
+  const uint32_t p = (uint32_t)(t / m), j = (uint32_t)(t % m);
+  uint32_t* gm = gamma + 8 * ((size_t)p * m + j);
+  if (j == k) {
+    sc_store(gx_half + 8 * (size_t)p, sc_half(sc_load(gm)));
+    return;
+  }
+  const uint32_t src = min(perm[(size_t)p * k + j], k - 1);
+  const size_t o = 8 * ((size_t)p * k + j);
+  sc_store(v + o, sc_load(deck + 8 * (size_t)src));
+  sc x;
+  if (gammas) {
+    x = sc_load(gammas + o);
+    sc_store(gm, x);
+  } else {
+    x = sc_load(gm);
+  }
+  sc_store(g + o, x);
+}
+
+int deck_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_deck, const uint32_t* d_perm,
+                    const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v, uint32_t* d_g, uint32_t* d_gx_half) {
+  if (!P) return BPP_OK;
+  const size_t nt = (size_t)P * C.m;
+  hipLaunchKernelGGL(k_deck_inputs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, P, C.k, d_deck,
+                     d_perm, d_gammas, d_gamma, d_v, d_g, d_gx_half);
+  return ctx_check_launch(ctx, "k_deck_inputs");
+}
+
+int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals, const uint32_t* d_x,
+                     uint32_t per, uint32_t* d_sc) {
+  if (!P) return BPP_OK;
+  if (C.k > DECK_WITNESS_DEV_MAX) {
+    ctx->err = "witness_deck_dev: k beyond the kernel's LDS budget";
+    return BPP_ERR_LEN;
+  }
+  const size_t lds = ((size_t)C.k + 2 * 256) * 32;
+  hipLaunchKernelGGL(k_witness_deck, dim3(P), dim3(256), lds, ctx->stream, C.k, C.n_p, per, d_vals, d_x, d_sc);
+  return ctx_check_launch(ctx, "k_witness_deck");
+}
+
 // The V phase's inputs of a caller-supplied shuffle, one lane per commitment
 // input (P x m lanes, after k_draws with v = nullptr on the same stream):
 // v[p][i] = cards[p][i], v[p][k + i] = cards[p][perm[p][i]] (i < k; perm is a
@@ -891,6 +1055,12 @@ void build_csr(const perm::Circuit& C, std::vector<uint32_t>& cp, std::vector<ui
 }
 
 unsigned poly_block(uint32_t n_p) { return n_p < 64 ? 64u : (n_p > POLY_T ? POLY_T : n_p); }
+// lanes per proof of k_poly_coef / k_verify_scalars; the deck circuit's in
+// whole waves (its m = k + 1 reaches n_p + 2)
+unsigned poly_block(const perm::Circuit& C) {
+  const unsigned nt = poly_block(std::max(C.n_p, C.m));
+  return C.deck ? std::min<unsigned>(POLY_T, (nt + 63) & ~63u) : nt;
+}
 
 }  // namespace
 
@@ -913,7 +1083,7 @@ int poly_coef_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32
   }
   BPP_TRY(ctx_h2d_const(ctx, "poly_cp", d_cp, cp.data(), cp.size() * 4));  // the circuit: same every batch
   BPP_TRY(ctx_h2d_const(ctx, "poly_ce", d_ce, ce.data(), ce.size() * 4));
-  const unsigned nt = poly_block(std::max(C.n_p, C.m));
+  const unsigned nt = poly_block(C);
   const size_t lds = ((size_t)C.Q + 1 + 2 * std::min(C.n_p, (uint32_t)POW_LO)) * 32 + (POLY_T / 64) * POLY_NT * 32;
   {
     ProfScope ps(ctx, "poly_coef");
@@ -982,18 +1152,27 @@ int verify_scalars_dev_rec(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count,
   BPP_TRY(ctx_h2d_const(ctx, "vs_cp", d_cp, cp.data(), cp.size() * 4));  // the circuit: same every batch
   BPP_TRY(ctx_h2d_const(ctx, "vs_ce", d_ce, ce.data(), ce.size() * 4));
   BPP_TRY(ctx_h2d_const(ctx, "vs_c", d_c, cw.data(), cw.size() * 4));
-  const unsigned nt = poly_block(std::max(C.n_p, C.m));
+  const unsigned nt = poly_block(C);
   const size_t lds = ((size_t)C.Q + 1 + 2 * std::min(C.n_p, (uint32_t)POW_LO)) * 32 + (POLY_T / 64) * 2 * 32;
   if (C.lg > VC_LGMAX) return BPP_ERR_LEN;  // (k_verify_consts' LDS tables)
-  void* d_kc = nullptr;
+  void *d_kc = nullptr, *d_deck = nullptr;
   BPP_TRY(ctx_ws(ctx, "vs_kc", (size_t)count * VK_N * 32, &d_kc));
+  if (C.deck) {  // the call's public deck, for c[Q-2] = prod (d_i - x_perm)
+    BPP_TRY(ctx_ws(ctx, "vs_deck", (size_t)C.k * 32, &d_deck));
+    BPP_TRY(ctx_h2d_const(ctx, "vs_deck", d_deck, C.cards.data(), (size_t)C.k * 32));
+  }
   {
     ProfScope ps(ctx, "verify_scalars");
     hipLaunchKernelGGL(k_verify_consts, dim3((count + VC_P - 1) / VC_P), dim3(64 * (VC_W + 1)), 0, ctx->stream, count,
                        C.lg, first, seed, d_rec, (uint32_t*)d_kc, NG, C.m, npt, d_sc);
-    hipLaunchKernelGGL(k_verify_scalars, dim3(count), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, C.lg, d_rec,
-                       (const uint32_t*)d_kc, (const uint32_t*)d_cp, (const uint32_t*)d_ce, (const uint32_t*)d_c,
-                       (uint32_t*)d_gen, d_sc, NG, npt);
+    if (C.deck)
+      hipLaunchKernelGGL(k_verify_scalars_deck, dim3(count), dim3(nt), lds + (size_t)nt * 32, ctx->stream, C.n_p, C.m,
+                         C.Q, C.lg, d_rec, (const uint32_t*)d_kc, (const uint32_t*)d_cp, (const uint32_t*)d_ce,
+                         (const uint32_t*)d_c, (uint32_t*)d_gen, d_sc, NG, npt, (const uint32_t*)d_deck, C.k);
+    else
+      hipLaunchKernelGGL(k_verify_scalars, dim3(count), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, C.lg, d_rec,
+                         (const uint32_t*)d_kc, (const uint32_t*)d_cp, (const uint32_t*)d_ce, (const uint32_t*)d_c,
+                         (uint32_t*)d_gen, d_sc, NG, npt);
     hipLaunchKernelGGL(k_verify_merge, dim3(NG), dim3(POLY_T), 0, ctx->stream, count, NG, (const uint32_t*)d_gen,
                        d_sc);
   }

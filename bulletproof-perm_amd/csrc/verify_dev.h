@@ -31,7 +31,7 @@ inline uint32_t vpts_n(const perm::Circuit& C) { return C.m + 8 + 2 * C.lg; }
 // Replays `count` transcripts on the device, one per 16-lane group
 // (k_verify_replay_g, then k_verify_reduce and k_verify_replay_post): d_proofs [count][proof_len] and d_V [count][m][32] on
 // the device; init = the 52-word transcript state every proof shares (the
-// label's Transcript::new and arithmetic_domain_sep(n_p); verify_init_state).
+// label's Transcript::new and perm::transcript_prefix; verify_init_state).
 // Writes d_rec (the challenges and the proof's scalars), r_out ([count][32],
 // the t-check weight challenges) and bad ([count] u32, nonzero where a point
 // is the identity encoding, a scalar is not canonical or a challenge is

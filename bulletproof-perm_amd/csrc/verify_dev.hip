@@ -60,11 +60,12 @@ FE_INLINE bool w8_zero(const uint32_t w[8]) {
 #define RG_SCR_OFF GRP_SCR_OFF
 #endif
 // Proofs [p0, p1) of a batch of `total` (ch and okw indexed by batch proof;
-// ch[total] is the pad).  (The transcript in two launches -- its V part as
+// ch[total] is the pad); nv = the commitments absorbed before x_perm
+// (Circuit::nv: 2k, or the deck circuit's k), m = nv + 1.  (The transcript in two launches -- its V part as
 // soon as the V bytes landed, the rest from the saved sponges -- was measured
 // behind a switch since removed and lost: profiles/r05_verify_ab.txt.)
 template <bool STAGED>
-__global__ void __launch_bounds__(64) k_verify_replay_g(uint32_t p0, uint32_t p1, uint32_t total, uint32_t k,
+__global__ void __launch_bounds__(64) k_verify_replay_g(uint32_t p0, uint32_t p1, uint32_t total, uint32_t nv,
                                                         uint32_t lg, uint32_t n_p, const uint32_t* __restrict__ init,
                                                         const uint32_t* __restrict__ proofs, uint32_t pw,
                                                         const uint32_t* __restrict__ V, uint32_t* __restrict__ ch,
@@ -78,7 +79,7 @@ __global__ void __launch_bounds__(64) k_verify_replay_g(uint32_t p0, uint32_t p1
   const uint32_t pg = p0 + blockIdx.x * RG_GROUPS + g;
   const bool live = pg < p1;
   const uint32_t p = live ? pg : p1 - 1;
-  const uint32_t m = 2 * k + 1, nch = 6 + lg;
+  const uint32_t m = nv + 1, nch = 6 + lg;
   GroupStrobe t;
   t.st = sp + g * RG_GS;
   t.scr = t.st + RG_SCR_OFF;
@@ -115,13 +116,13 @@ __global__ void __launch_bounds__(64) k_verify_replay_g(uint32_t p0, uint32_t p1
   uint32_t* CH = ch + (size_t)(live ? p : total) * nch * 16;
   uint32_t w[8];
   bool ok = true;
-  for (uint32_t j = 0; j < 2 * k; ++j) {
+  for (uint32_t j = 0; j < nv; ++j) {
     ld8(PV + 8 * j, w);
     APPEND32("V", 1, w, PV + 8 * j);
   }
   t.challenge64_to("x_perm", 6, CH, true);
-  ld8(PV + 16 * k, w);
-  APPEND32("V", 1, w, PV + 16 * k);
+  ld8(PV + 8 * nv, w);
+  APPEND32("V", 1, w, PV + 8 * nv);
   ld8(PP, w);
   ok &= !w8_zero(w);
   APPEND32("A_I", 3, w, PP);
@@ -283,7 +284,7 @@ static unsigned grid_for(size_t n, unsigned t) { return (unsigned)((n + t - 1) /
 
 void verify_init_state(const perm::Circuit& C, const uint8_t* label, size_t llen, uint32_t out[52]) {
   merlin::Transcript tr(label, llen);
-  tr.arithmetic_domain_sep(C.n_p);
+  perm::transcript_prefix(C, tr);
   memcpy(out, tr.s.st, 200);
   out[50] = tr.s.pos;
   out[51] = tr.s.pos_begin;
@@ -292,7 +293,7 @@ void verify_init_state(const perm::Circuit& C, const uint8_t* label, size_t llen
 int verify_replay_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_init,
                       const uint32_t* d_proofs, const uint32_t* d_V, uint32_t* d_rec, uint32_t* r_out, uint32_t* bad) {
   if (!count) return BPP_OK;
-  const uint32_t pw = (uint32_t)(perm::proof_len(C.k) / 4);
+  const uint32_t pw = (uint32_t)(perm::proof_len(C) / 4);
   const uint32_t nch = 6 + C.lg;
   void *d_ch = nullptr, *d_ok = nullptr;
   BPP_TRY(ctx_ws(ctx, "vj_ch", ((size_t)count + 1) * nch * 64, &d_ch));
@@ -303,10 +304,10 @@ int verify_replay_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, cons
     const size_t stage = (size_t)RG_GROUPS * (pw + 8 * (size_t)C.m) * 4;
     if (stage <= 48 * 1024)
       hipLaunchKernelGGL(k_verify_replay_g<true>, dim3(grid_for(count, RG_GROUPS)), dim3(64), stage, ctx->stream, 0u,
-                         count, count, C.k, C.lg, C.n_p, d_init, d_proofs, pw, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok);
+                         count, count, C.nv, C.lg, C.n_p, d_init, d_proofs, pw, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok);
     else
       hipLaunchKernelGGL(k_verify_replay_g<false>, dim3(grid_for(count, RG_GROUPS)), dim3(64), 0, ctx->stream, 0u,
-                         count, count, C.k, C.lg, C.n_p, d_init, d_proofs, pw, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok);
+                         count, count, C.nv, C.lg, C.n_p, d_init, d_proofs, pw, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok);
   }
   BPP_TRY(ctx_check_launch(ctx, "k_verify_replay_g"));
   {
@@ -350,7 +351,7 @@ int verify_decompress_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, 
   {
     ProfScope ps(ctx, "verify_decompress");
     hipLaunchKernelGGL(k_verify_decompress, dim3(grid_for(i1 - i0, 64)), dim3(64), 0, ctx->stream, i0, i1, jlo, jn, C.m,
-                       C.lg, npt, d_proofs, (uint32_t)(perm::proof_len(C.k) / 4), d_V, d_tbl, d_bad, d_pdec);
+                       C.lg, npt, d_proofs, (uint32_t)(perm::proof_len(C) / 4), d_V, d_tbl, d_bad, d_pdec);
   }
   return ctx_check_launch(ctx, "k_verify_decompress");
 }

@@ -396,6 +396,56 @@ int bpp_perm_verify_batch(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t co
 int bpp_perm_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* label,
                                size_t llen, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out);
 
+/* ------------------------------------- public-deck shuffle proof (sound) */
+/* The FIRST shuffle of a game starts from a deck every player knows.  These
+ * entry points prove "V_0..V_{k-1} commit to a permutation of the PUBLIC deck
+ * d_0..d_{k-1}" (V_k commits to the transcript challenge x_perm): k + 1
+ * commitments instead of 2k + 1 and one product chain inside the proof -- the
+ * deck's own product D = prod (d_i - x_perm) is computed by both sides -- so
+ * n = k - 1 gates, Q = 2k rows, n_p = max(4, next_pow2(k - 1)) <=
+ * bpp_gens_len(g) (64 for 52 cards, against 128).  The two-half statement
+ * above remains the one for re-shuffling a deck that is already committed.
+ *   deck    NULL (the cards 1..k), or k x 32 B canonical scalars, shared by
+ *           every proof of the call.  Repeats, 0 and l - 1 are allowed;
+ *           equality is as MULTISETS, as above.  A card >= l ->
+ *           BPP_ERR_NONCANONICAL, in the verifiers too.
+ *   perms   count x k u32: V_i commits to deck[perm[i]].
+ *   gammas  NULL, or count x k x 32 B: the blindings of V_0..V_{k-1}.
+ *   V_out / V   count x (k + 1) x 32 B.
+ * Proof bytes (bpp_deck_proof_len(k); 800 at k = 52): the layout of
+ * bpp_perm_proof_len with this circuit's lg = log2 n_p.
+ * Transcript: Transcript(label), dom-sep("acp v1", n_p),
+ * append_message("deck", SHAKE256("bpperm-deck" || le32 k || d_0 || .. ||
+ * d_{k-1})[0..32]), V_0..V_{k-1}, challenge x_perm, V_k, A_I A_O S and on as
+ * above.  The "deck" message binds the proof to the deck, and keeps a two-half
+ * proof of k' cards and a deck proof of 2k' cards -- same commitment count,
+ * n_p and byte length -- from verifying as each other.
+ * Randomness: seeds32 as bpp_perm_prove_batch_entropy; indexed draws in the
+ * order gamma[k + 1], alpha, beta, rho, s_L[n_p], s_R[n_p], tau[5] with this
+ * circuit's n_p; supplied gammas replace draws 0..k-1; no pi stream is read.
+ * Checks: those of bpp_perm_prove_shuffle_batch in its order, before any
+ * device work and before any output byte is written -- a perm that is not a
+ * bijection on [0, k) -> BPP_ERR_ARG; a deck card or gamma >= l ->
+ * BPP_ERR_NONCANONICAL (neither needs ctx or g); then the k / g / null checks.
+ * Secret lifetime: that of bpp_perm_prove_batch_entropy; the staged and
+ * uploaded perms and gammas and the committed values are part of what is
+ * zeroed and of what bpp_debug_secret_residue counts (the deck is public).
+ * The verifiers mirror bpp_perm_verify, _verify_batch and _verify_batch_each
+ * (the ok_out contract and count == 0 included).  The device witness covers
+ * k <= 1536, the host witness beyond.  The multi-GPU job API takes two-half
+ * proofs only. */
+size_t bpp_deck_proof_len(uint32_t k);
+int bpp_deck_prove_batch(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* deck,
+                         const uint32_t* perms, const uint8_t* gammas, const uint8_t* seeds32, const uint8_t* label,
+                         size_t llen, uint8_t* proofs_out, uint8_t* V_out);
+int bpp_deck_verify(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, const uint8_t* deck, const uint8_t* label,
+                    size_t llen, const uint8_t* proof, size_t proof_len, const uint8_t* V);
+int bpp_deck_verify_batch(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* deck,
+                          const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V);
+int bpp_deck_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* deck,
+                               const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
+                               uint8_t* ok_out);
+
 /* Batch verification split for several GPUs (north_star: "the single large
  * verifier MSM partitions its bucket windows across GPUs"; reference verify
  * circuit_lib.rs:478-585).  Host phase, no GPU: parse `count` proofs, replay
