@@ -24,7 +24,7 @@ from ._lib import BppError, check
 MSM_INFLIGHT = 4  # BPP_MSM_INFLIGHT (include/bpperm.h)
 
 __all__ = ["Context", "PointTable", "BppError", "vartime_multiscalar_mul", "default_context", "VerifyJob",
-           "partials_is_identity"]
+           "partials_is_identity", "Circuit", "CircuitProver"]
 
 
 def _buf(b: bytes):
@@ -772,6 +772,152 @@ class DeckProver:
         if rc != 6:
             check(rc, "bpp_deck_verify_batch_each", self.ctx.h)
         return [b != 0 for b in ok.raw[:count]]
+
+
+class _CircuitDescC(C.Structure):
+    _fields_ = [("m_in", C.c_uint32), ("n_gates", C.c_uint32), ("n_aux", C.c_uint32), ("n_asserts", C.c_uint32),
+                ("side_aux", C.POINTER(C.c_uint32)), ("lc_off", C.POINTER(C.c_uint32)),
+                ("lc_var", C.POINTER(C.c_uint32)), ("lc_coef", C.c_char_p)]
+
+
+class Circuit:
+    """A compiled caller-defined circuit (bpp_circuit_create; no GPU): desc is
+    a gadgets.CircuitDesc (or anything with its fields).  n_p, Q, m, digest and
+    proof_len are the compiled statement's; matrix() and eval() expose the
+    compiled rows and the host witness."""
+
+    def __init__(self, desc):
+        self.lib = _lib.load()
+        self.desc = desc
+        u32a = lambda xs: (C.c_uint32 * max(len(xs), 1))(*xs)
+        self._keep = (u32a(desc.side_aux), u32a(desc.lc_off), u32a(desc.lc_var), b"".join(desc.lc_coef))
+        d = _CircuitDescC(desc.m_in, desc.n_gates, desc.n_aux, desc.n_asserts, self._keep[0], self._keep[1],
+                          self._keep[2], self._keep[3])
+        h = C.c_void_p()
+        check(self.lib.bpp_circuit_create(C.byref(d), C.byref(h)), "bpp_circuit_create")
+        self.h = h
+        n_p, Q, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        dg = C.create_string_buffer(32)
+        check(self.lib.bpp_circuit_info(h, C.byref(n_p), C.byref(Q), C.byref(m), dg), "bpp_circuit_info")
+        self.n_p, self.Q, self.m, self.digest = n_p.value, Q.value, m.value, dg.raw
+        self.m_in, self.n_aux = desc.m_in, desc.n_aux
+        self.proof_len = int(self.lib.bpp_circuit_proof_len(h))
+
+    def close(self):
+        if self.h:
+            self.lib.bpp_circuit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def matrix(self, which: int):
+        """Triplets (q, col, val bytes) of W_L, W_R, W_O, W_V (which = 0..3) or
+        of c (which = 4: (q, 0, c[q]))."""
+        n = C.c_size_t(0)
+        rc = self.lib.bpp_circuit_matrix(self.h, which, None, None, None, C.byref(n))
+        if rc not in (0, 2):
+            check(rc, "bpp_circuit_matrix")
+        cnt = n.value
+        q, col = (C.c_uint32 * max(cnt, 1))(), (C.c_uint32 * max(cnt, 1))()
+        val = C.create_string_buffer(max(32 * cnt, 1))
+        check(self.lib.bpp_circuit_matrix(self.h, which, q, col, val, C.byref(n)), "bpp_circuit_matrix")
+        return [(q[i], col[i], val.raw[32 * i:32 * i + 32]) for i in range(cnt)]
+
+    def eval(self, v, aux, x: bytes):
+        """The host witness: (a_L, a_R, a_O) as lists of n_p 32-byte scalars,
+        and 1 + the first assert that does not hold (0: all hold)."""
+        vb, ab = _join(v, 32, "v"), _join(aux, 32, "aux")
+        outs = [C.create_string_buffer(32 * self.n_p) for _ in range(3)]
+        bad = C.c_uint32()
+        check(self.lib.bpp_circuit_eval(self.h, _buf(vb), _buf(ab), _buf(x), *outs, C.byref(bad)), "bpp_circuit_eval")
+        return tuple([o.raw[32 * i:32 * i + 32] for i in range(self.n_p)] for o in outs) + (bad.value,)
+
+
+class CircuitProver:
+    """Proofs of a caller-defined circuit (bpp_circuit_*), mirroring DeckProver:
+    circuit is a Circuit, or a description it is compiled from."""
+
+    def __init__(self, gens: Gens, circuit, label: bytes = b"bp-perm", ctx: "Context | None" = None):
+        self.gens = gens
+        self.ctx = ctx or gens.ctx
+        self.circuit = circuit if isinstance(circuit, Circuit) else Circuit(circuit)
+        self.label = label
+        self.proof_len = self.circuit.proof_len
+        self.m = self.circuit.m
+
+    def prove_batch(self, v, aux=None, seeds32: bytes | None = None, gammas=None, raw: bool = False,
+                    out: "tuple | None" = None):
+        """v[p] = the m_in committed inputs of proof p, aux[p] = its n_aux
+        auxiliary values, gammas[p] = the m_in blindings of V_0..V_{m_in-1}
+        (None: drawn) -- 32-byte scalars (or each proof's joined); seeds32 = 32
+        bytes per proof (None: the OS CSPRNG).  out = (proofs, V) ctypes buffers
+        to write into instead of fresh ones.  Returns what
+        DeckProver.prove_batch returns; the batch's secrets are wiped."""
+        c = self.circuit
+        count = len(v)
+        row = lambda rows, what: b"".join(x if isinstance(x, (bytes, bytearray)) else _join(x, 32, what) for x in rows)
+        vb = row(v, "v")
+        if len(vb) != 32 * c.m_in * count:
+            raise ValueError("v: expected m_in scalars of 32 bytes per proof")
+        ab = row(aux, "aux") if aux is not None else b""
+        if len(ab) != 32 * c.n_aux * count:
+            raise ValueError("aux: expected n_aux scalars of 32 bytes per proof")
+        gb = None
+        if gammas is not None:
+            gb = row(gammas, "gammas")
+            if len(gb) != 32 * c.m_in * count:
+                raise ValueError("gammas: expected m_in scalars of 32 bytes per proof")
+        if seeds32 is not None and len(seeds32) != 32 * count:
+            raise ValueError("seeds32 must hold 32 bytes per proof")
+        if out is None:
+            pf = C.create_string_buffer(max(self.proof_len * count, 1))
+            V = C.create_string_buffer(max(32 * self.m * count, 1))
+        else:
+            pf, V = out
+        check(self.ctx.lib.bpp_circuit_prove_batch(self.ctx.h, self.gens.h, c.h, count, _buf(vb), _buf(ab),
+                                                   _buf(gb) if gb is not None else None,
+                                                   _buf(seeds32) if seeds32 is not None else None,
+                                                   _buf(self.label), len(self.label), pf, V),
+              "bpp_circuit_prove_batch", self.ctx.h)
+        praw, vraw = pf.raw[:self.proof_len * count], V.raw[:32 * self.m * count]
+        if raw:
+            return praw, vraw
+        return ([praw[i * self.proof_len:(i + 1) * self.proof_len] for i in range(count)],
+                [vraw[i * 32 * self.m:(i + 1) * 32 * self.m] for i in range(count)])
+
+    def verify(self, proof: bytes, V) -> bool:
+        vb = _join(V, 32, "V")
+        rc = self.ctx.lib.bpp_circuit_verify(self.ctx.h, self.gens.h, self.circuit.h, _buf(self.label),
+                                             len(self.label), _buf(proof), len(proof), _buf(vb))
+        if rc == 6:
+            return False
+        check(rc, "bpp_circuit_verify", self.ctx.h)
+        return True
+
+    _batch_buffers = PermProver._batch_buffers
+
+    def verify_batch(self, proofs, Vs) -> bool:
+        pb, vb, count = self._batch_buffers(proofs, Vs)
+        rc = self.ctx.lib.bpp_circuit_verify_batch(self.ctx.h, self.gens.h, self.circuit.h, count, _buf(self.label),
+                                                   len(self.label), _buf(pb), _buf(vb))
+        if rc == 6:
+            return False
+        check(rc, "bpp_circuit_verify_batch", self.ctx.h)
+        return True
+
+    def verify_batch_each(self, proofs, Vs) -> "list[bool]":
+        pb, vb, count = self._batch_buffers(proofs, Vs)
+        ok = C.create_string_buffer(max(count, 1))
+        rc = self.ctx.lib.bpp_circuit_verify_batch_each(self.ctx.h, self.gens.h, self.circuit.h, count,
+                                                        _buf(self.label), len(self.label), _buf(pb), _buf(vb), ok)
+        if rc != 6:
+            check(rc, "bpp_circuit_verify_batch_each", self.ctx.h)
+        return [b != 0 for b in ok.raw[:count]]
+
 
 class VerifyJob:
     """Parsed proofs with their transcripts replayed: on the host

@@ -100,6 +100,16 @@ SIGNATURES = {
     "bpp_deck_verify": (i32, [vp, vp, u32, vp, vp, sz, vp, sz, vp]),
     "bpp_deck_verify_batch": (i32, [vp, vp, u32, sz, vp, vp, sz, vp, vp]),
     "bpp_deck_verify_batch_each": (i32, [vp, vp, u32, sz, vp, vp, sz, vp, vp, vp]),
+    "bpp_circuit_create": (i32, [vp, C.POINTER(vp)]),
+    "bpp_circuit_destroy": (None, [vp]),
+    "bpp_circuit_info": (i32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), vp]),
+    "bpp_circuit_proof_len": (sz, [vp]),
+    "bpp_circuit_matrix": (i32, [vp, u32, vp, vp, vp, C.POINTER(sz)]),
+    "bpp_circuit_eval": (i32, [vp, vp, vp, vp, vp, vp, vp, C.POINTER(u32)]),
+    "bpp_circuit_prove_batch": (i32, [vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, vp, vp]),
+    "bpp_circuit_verify": (i32, [vp, vp, vp, vp, sz, vp, sz, vp]),
+    "bpp_circuit_verify_batch": (i32, [vp, vp, vp, sz, vp, sz, vp, vp]),
+    "bpp_circuit_verify_batch_each": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, vp]),
     "bpp_perm_verify_begin": (i32, [u32, sz, vp, sz, vp, vp, vp, C.POINTER(vp)]),
     "bpp_perm_verify_begin_dev": (i32, [vp, u32, sz, vp, sz, vp, vp, vp, C.POINTER(vp)]),
     "bpp_perm_verify_terms": (i32, [vp, C.POINTER(sz)]),

@@ -1,0 +1,239 @@
+"""Caller-defined circuits for bpp_circuit_* (include/bpperm.h): a builder that
+writes the description arrays, and four gadgets built on it.  Pure Python: no
+library call, no GPU.
+
+    b = CircuitBuilder()
+    v = b.input()
+    l, r, o = b.mul(v - 3, v - 7)      # defined sides: linear combinations
+    b.assert_zero(o)                   # v is 3 or 7
+    desc = b.build()                   # -> CircuitDesc (the arrays of bpp_circuit_desc)
+
+A linear combination (LC) is built from b.input(), b.challenge, b.one, wires
+and integers with +, -, unary - and * by an integer; coefficients are mod l.
+A defined side may read wires of EARLIER gates only.  b.free_mul() makes a gate
+whose two sides are fed from the per-proof auxiliary values (its two aux
+indices are 2t, 2t + 1 for the t-th free gate, left then right).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Callable, Sequence
+
+L = 2**252 + 27742317777372353535851937790883648493
+SIDE_LC = 0xFFFFFFFF
+
+_ONE, _V, _X, _W = 0, 1, 2, 3  # variable kinds, in id order
+
+
+class LC:
+    """A sparse linear combination: {(kind, index, part): coefficient mod l}."""
+
+    __slots__ = ("t",)
+
+    def __init__(self, terms=None):
+        self.t = {k: c % L for k, c in (terms or {}).items() if c % L}
+
+    @staticmethod
+    def of(x) -> "LC":
+        if isinstance(x, LC):
+            return x
+        if isinstance(x, int):
+            return LC({(_ONE, 0, 0): x})
+        raise TypeError(f"not a linear combination: {x!r}")
+
+    def __add__(self, o):
+        o = LC.of(o)
+        t = dict(self.t)
+        for k, c in o.t.items():
+            t[k] = t.get(k, 0) + c
+        return LC(t)
+
+    __radd__ = __add__
+
+    def __neg__(self):
+        return LC({k: -c for k, c in self.t.items()})
+
+    def __sub__(self, o):
+        return self + (-LC.of(o))
+
+    def __rsub__(self, o):
+        return LC.of(o) - self
+
+    def __mul__(self, a):
+        if not isinstance(a, int):
+            raise TypeError("an LC is scaled by an integer; products are gates (CircuitBuilder.mul)")
+        return LC({k: c * a for k, c in self.t.items()})
+
+    __rmul__ = __mul__
+
+
+@dataclass
+class CircuitDesc:
+    """The arrays of bpp_circuit_desc.  lc_coef: one 32-byte little-endian
+    scalar per term."""
+    m_in: int
+    n_gates: int
+    n_aux: int
+    n_asserts: int
+    side_aux: list
+    lc_off: list
+    lc_var: list
+    lc_coef: list
+    # the gadget's hint function: v (m_in ints) -> aux (n_aux ints); None when n_aux = 0
+    aux_of: "Callable[[Sequence[int]], list] | None" = field(default=None, compare=False)
+
+    def coef_bytes(self) -> bytes:
+        return b"".join(self.lc_coef)
+
+
+class CircuitBuilder:
+    def __init__(self):
+        self.m_in = 0
+        self.n_aux = 0
+        self.sides = []    # per gate: [left, right], each an LC (defined) or an aux index (free)
+        self.asserts = []
+        self.one = LC({(_ONE, 0, 0): 1})
+        self.challenge = LC({(_X, 0, 0): 1})
+
+    def input(self) -> LC:
+        self.m_in += 1
+        return LC({(_V, self.m_in - 1, 0): 1})
+
+    def inputs(self, n: int) -> list:
+        return [self.input() for _ in range(n)]
+
+    def _wires(self, g: int):
+        return tuple(LC({(_W, g, s): 1}) for s in range(3))
+
+    def mul(self, left, right):
+        """A gate with defined sides; returns its wires (l, r, o)."""
+        g = len(self.sides)
+        for side in (LC.of(left), LC.of(right)):
+            for (kind, h, _s) in side.t:
+                if kind == _W and h >= g:
+                    raise ValueError(f"gate {g}: a definition reads a wire of gate {h}")
+        self.sides.append([LC.of(left), LC.of(right)])
+        return self._wires(g)
+
+    def free_mul(self):
+        """A gate with both sides free (aux indices n_aux, n_aux + 1); returns
+        its wires (l, r, o)."""
+        self.sides.append([self.n_aux, self.n_aux + 1])
+        self.n_aux += 2
+        return self._wires(len(self.sides) - 1)
+
+    def assert_zero(self, lc):
+        self.asserts.append(LC.of(lc))
+
+    def build(self, aux_of=None) -> CircuitDesc:
+        m_in, n = self.m_in, len(self.sides)
+        if not m_in or not n:
+            raise ValueError("a circuit needs an input and a gate")
+
+        def var_id(key):
+            kind, i, s = key
+            return {_ONE: 0, _V: 1 + i, _X: 1 + m_in, _W: 2 + m_in + 3 * i + s}[kind]
+
+        side_aux, lc_off, lc_var, lc_coef = [], [0], [], []
+
+        def emit(lc: LC):
+            for vid, c in sorted((var_id(k), c) for k, c in lc.t.items()):
+                lc_var.append(vid)
+                lc_coef.append(c.to_bytes(32, "little"))
+            lc_off.append(len(lc_var))
+
+        for sides in self.sides:
+            for s in sides:
+                if isinstance(s, LC):
+                    side_aux.append(SIDE_LC)
+                    emit(s)
+                else:
+                    side_aux.append(s)
+                    lc_off.append(len(lc_var))
+        for a in self.asserts:
+            emit(a)
+        return CircuitDesc(m_in, n, self.n_aux, len(self.asserts), side_aux, lc_off, lc_var, lc_coef, aux_of)
+
+
+# --------------------------------------------------------------------- gadgets
+
+def two_half_shuffle(k: int) -> CircuitDesc:
+    """bpp_perm_*'s statement as a program: v_0..v_{k-1} and v_k..v_{2k-1} hold
+    the same multiset.  Compiles to exactly the two-half circuit's matrices: two
+    product chains prod (v_i - x), a negation gate, a difference gate whose
+    output is asserted 0."""
+    if k < 2:
+        raise ValueError("k >= 2")
+    b = CircuitBuilder()
+    v = b.inputs(2 * k)
+    x = b.challenge
+    o = [None] * (2 * k)
+    for g in range(k - 1):  # chain A
+        o[g] = b.mul(v[0] - x if g == 0 else o[g - 1], v[g + 1] - x)[2]
+    for g in range(k - 1, 2 * k - 2):  # chain B
+        o[g] = b.mul(v[k] - x if g == k - 1 else o[g - 1], v[g + 2] - x)[2]
+    o[2 * k - 2] = b.mul(o[2 * k - 3], -1)[2]
+    o[2 * k - 1] = b.mul(o[k - 2] + o[2 * k - 2], 1)[2]
+    b.assert_zero(o[2 * k - 1])
+    return b.build()
+
+
+def member_of(values: Sequence[int]) -> CircuitDesc:
+    """v_0 is one of `values`: prod (v_0 - s_i) = 0, len(values) - 1 gates (one
+    gate for one or two values)."""
+    s = [int(a) % L for a in values]
+    if not s:
+        raise ValueError("member_of: an empty set")
+    b = CircuitBuilder()
+    v = b.input()
+    o = b.mul(v - s[0], v - s[1] if len(s) > 1 else 1)[2]
+    for a in s[2:]:
+        o = b.mul(o, v - a)[2]
+    b.assert_zero(o)
+    return b.build()
+
+
+def in_range(nbits: int) -> CircuitDesc:
+    """v_0 < 2^nbits.  Each bit takes a gate with both sides free (l = bit, r =
+    1 - bit), an assert o = 0 and an assert l + r - 1 = 0; one more assert
+    covers the weighted bit sum.  aux_of(v) gives the 2 nbits hints."""
+    if not 1 <= nbits <= 252:
+        raise ValueError("1 <= nbits <= 252")
+    b = CircuitBuilder()
+    v = b.input()
+    total = LC()
+    for i in range(nbits):
+        l, r, o = b.free_mul()
+        b.assert_zero(o)
+        b.assert_zero(l + r - 1)
+        total = total + l * (1 << i)
+    b.assert_zero(total - v)
+
+    def aux_of(vals):
+        x = int(vals[0]) % L
+        out = []
+        for i in range(nbits):
+            bit = (x >> i) & 1
+            out += [bit, 1 - bit]
+        return out
+
+    return b.build(aux_of)
+
+
+def same_multiset(k: int) -> CircuitDesc:
+    """Two hidden hands v_0..v_{k-1} and v_k..v_{2k-1} hold the same multiset:
+    prod (v_i - x) over each hand, 2k - 2 gates, one assert on the difference
+    of the two products."""
+    if k < 2:
+        raise ValueError("k >= 2")
+    b = CircuitBuilder()
+    v = b.inputs(2 * k)
+    x = b.challenge
+    ends = []
+    for base in (0, k):
+        o = b.mul(v[base] - x, v[base + 1] - x)[2]
+        for i in range(2, k):
+            o = b.mul(o, v[base + i] - x)[2]
+        ends.append(o)
+    b.assert_zero(ends[0] - ends[1])
+    return b.build()

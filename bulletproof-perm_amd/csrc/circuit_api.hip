@@ -1,0 +1,159 @@
+// Caller-defined circuits: the C ABI (bpp_circuit_*, include/bpperm.h) --
+// argument checks, bpp_guard and marshalling.  The compile and the host
+// witness are host/circuit.cpp; the prover is perm_prove.hip with the circuit
+// form of ShuffleIn, the verifier perm_verify.hip unchanged.
+#include <string>
+
+#include "host/circuit.h"
+#include "perm_internal.h"
+
+using namespace perm_impl;
+
+static_assert(circuit::OK == BPP_OK && circuit::ERR_ARG == BPP_ERR_ARG && circuit::ERR_LEN == BPP_ERR_LEN &&
+                  circuit::ERR_NONCANONICAL == BPP_ERR_NONCANONICAL && circuit::SIDE_LC == BPP_SIDE_LC,
+              "host/circuit.h restates these");
+
+struct bpp_circuit {
+  perm::Circuit C;  // (C.program: the compiled program)
+};
+
+extern "C" {
+
+int bpp_circuit_create(const bpp_circuit_desc* desc, bpp_circuit** out) {
+  return bpp_guard(nullptr, [&]() -> int {
+    if (!desc || !out) return BPP_ERR_ARG;
+    *out = nullptr;
+    const circuit::Desc d = {desc->m_in,   desc->n_gates, desc->n_aux,  desc->n_asserts,
+                             desc->side_aux, desc->lc_off,  desc->lc_var, desc->lc_coef};
+    std::unique_ptr<bpp_circuit> c(new bpp_circuit());
+    std::string err;
+    BPP_TRY(circuit::compile(d, c->C, err));
+    *out = c.release();
+    return BPP_OK;
+  });
+}
+
+void bpp_circuit_destroy(bpp_circuit* c) { delete c; }
+
+int bpp_circuit_info(const bpp_circuit* c, uint32_t* n_p, uint32_t* Q, uint32_t* m, uint8_t digest[32]) {
+  if (!c) return BPP_ERR_ARG;
+  if (n_p) *n_p = c->C.n_p;
+  if (Q) *Q = c->C.Q;
+  if (m) *m = c->C.m;
+  if (digest) memcpy(digest, c->C.program_digest, 32);
+  return BPP_OK;
+}
+
+size_t bpp_circuit_proof_len(const bpp_circuit* c) { return c ? perm::proof_len(c->C) : 0; }
+
+int bpp_circuit_matrix(const bpp_circuit* c, uint32_t which, uint32_t* q, uint32_t* col, uint8_t* val, size_t* count) {
+  return bpp_guard(nullptr, [&]() -> int {
+    if (!c || !count || which > 4) return BPP_ERR_ARG;
+    const std::vector<perm::Entry>* const W[4] = {&c->C.WL, &c->C.WR, &c->C.WO, &c->C.WV};
+    const size_t cap = *count, n = which < 4 ? W[which]->size() : c->C.c.size();
+    *count = n;
+    if (cap < n) return BPP_ERR_LEN;
+    if (n && (!q || !col || !val)) return BPP_ERR_ARG;
+    for (size_t i = 0; i < n; ++i) {
+      q[i] = which < 4 ? (*W[which])[i].q : (uint32_t)i;
+      col[i] = which < 4 ? (*W[which])[i].col : 0;
+      hsc::to_bytes(val + 32 * i, which < 4 ? (*W[which])[i].val : c->C.c[i]);
+    }
+    return BPP_OK;
+  });
+}
+
+int bpp_circuit_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* aux, const uint8_t x[32], uint8_t* aL,
+                     uint8_t* aR, uint8_t* aO, uint32_t* bad_assert) {
+  return bpp_guard(nullptr, [&]() -> int {
+    if (!c || !v || !x || !aL || !aR || !aO || !bad_assert) return BPP_ERR_ARG;
+    const circuit::Program& P = *c->C.program;
+    if (!aux && P.n_aux) return BPP_ERR_ARG;
+    std::vector<Sc> vs(P.m_in), as(P.n_aux), L, R, O;
+    Sc xs;
+    for (uint32_t j = 0; j < P.m_in; ++j)
+      if (!hsc::from_canonical(vs[j], v + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
+    for (uint32_t j = 0; j < P.n_aux; ++j)
+      if (!hsc::from_canonical(as[j], aux + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
+    if (!hsc::from_canonical(xs, x)) return BPP_ERR_NONCANONICAL;
+    circuit::eval(P, c->C.n_p, vs.data(), as.data(), xs, L, R, O, bad_assert);
+    memcpy(aL, L.data(), 32 * (size_t)c->C.n_p);  // (canonical Sc == its 32 bytes)
+    memcpy(aR, R.data(), 32 * (size_t)c->C.n_p);
+    memcpy(aO, O.data(), 32 * (size_t)c->C.n_p);
+    for (auto* s : {&vs, &as, &L, &R, &O}) std::fill(s->begin(), s->end(), hsc::zero());
+    return BPP_OK;
+  });
+}
+
+int bpp_circuit_prove_batch(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count, const uint8_t* v,
+                            const uint8_t* aux, const uint8_t* gammas, const uint8_t* seeds32, const uint8_t* label,
+                            size_t llen, uint8_t* proofs_out, uint8_t* V_out) {
+  return bpp_guard(ctx, [&]() -> int {
+    if (!c || (!label && llen)) return BPP_ERR_ARG;
+    const uint32_t m_in = c->C.nv, n_aux = c->C.program->n_aux;
+    if ((!v || (!aux && n_aux) || !proofs_out || !V_out) && count) return BPP_ERR_ARG;
+    // every scalar of the witness is checked before any device work and
+    // before any output byte is written (it needs neither the context nor
+    // the generators, whose null checks follow)
+    std::vector<int> bad(count, BPP_OK);
+    par::for_each(count, [&](size_t p) {
+      Sc t;
+      for (uint32_t i = 0; i < m_in; ++i)
+        if (!hsc::from_canonical(t, v + (p * (size_t)m_in + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
+      for (uint32_t i = 0; i < n_aux; ++i)
+        if (!hsc::from_canonical(t, aux + (p * (size_t)n_aux + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
+      if (gammas)
+        for (uint32_t i = 0; i < m_in; ++i)
+          if (!hsc::from_canonical(t, gammas + (p * (size_t)m_in + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
+      t = hsc::zero();
+    });
+    for (size_t p = 0; p < count; ++p)
+      if (bad[p] != BPP_OK) {
+        if (ctx) ctx->err = "circuit proof " + std::to_string(p) + ": non-canonical value, auxiliary value or blinding";
+        return bad[p];
+      }
+    if (!ctx || !G) return BPP_ERR_ARG;
+    if (!count) return BPP_OK;
+    ShuffleIn sh = {nullptr, nullptr, gammas};
+    sh.v = v;
+    sh.aux = aux;
+    return prove_batch_entropy(ctx, G, c->C, count, seeds32, label, llen, proofs_out, V_out, &sh);
+  });
+}
+
+int bpp_circuit_verify(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, const uint8_t* label, size_t llen,
+                       const uint8_t* proof, size_t proof_len, const uint8_t* V) {
+  return bpp_guard(ctx, [&]() -> int {
+    if (!ctx || !G || !c || !proof || !V || (!label && llen)) return BPP_ERR_ARG;
+    if (proof_len != perm::proof_len(c->C)) return BPP_ERR_VERIFY;
+    BPP_HIP(hipSetDevice(ctx->device));
+    return verify_batch(ctx, G, c->C, label, llen, 1, proof, V);
+  });
+}
+
+int bpp_circuit_verify_batch(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count, const uint8_t* label,
+                             size_t llen, const uint8_t* proofs, const uint8_t* V) {
+  return bpp_guard(ctx, [&]() -> int {
+    if (!ctx || !G || !c || ((!proofs || !V) && count) || (!label && llen)) return BPP_ERR_ARG;
+    if (!count) return BPP_OK;
+    BPP_HIP(hipSetDevice(ctx->device));
+    return verify_batch(ctx, G, c->C, label, llen, count, proofs, V);
+  });
+}
+
+int bpp_circuit_verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count,
+                                  const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
+                                  uint8_t* ok_out) {
+  // (no pass is ever left behind by a call that fails)
+  if (ok_out && count) memset(ok_out, 0, count);
+  return bpp_guard(ctx, [&]() -> int {
+    if (!ctx || !G || !c || ((!proofs || !V || !ok_out) && count) || (!label && llen)) return BPP_ERR_ARG;
+    if (!count) return BPP_OK;
+    BPP_HIP(hipSetDevice(ctx->device));
+    const int rc = verify_batch_each(ctx, G, c->C, label, llen, count, proofs, V, ok_out);
+    if (rc != BPP_OK && rc != BPP_ERR_VERIFY) memset(ok_out, 0, count);
+    return rc;
+  });
+}
+
+}  // extern "C"

@@ -10,10 +10,15 @@
 #include <stdint.h>
 
 #include <array>
+#include <memory>
 #include <vector>
 
 #include "merlin.h"
 #include "scalar.h"
+
+namespace circuit {
+struct Program;  // circuit.h
+}
 
 namespace perm {
 
@@ -32,6 +37,10 @@ struct Circuit {
   bool deck = false;
   std::vector<hsc::Sc> cards;
   uint8_t deck_digest[32] = {0};
+  // caller-defined circuit (circuit.h compile) only: the gate program the
+  // witness is evaluated from, and its description's transcript digest
+  std::shared_ptr<const circuit::Program> program;
+  uint8_t program_digest[32] = {0};
 };
 
 Circuit build(uint32_t k);
@@ -57,12 +66,29 @@ hsc::Sc deck_product(const Circuit& C, const hsc::Sc& x);
 void witness_deck(const Circuit& C, const std::vector<uint32_t>& pi, const hsc::Sc& x, std::vector<hsc::Sc>& v,
                   std::vector<hsc::Sc>& aL, std::vector<hsc::Sc>& aR, std::vector<hsc::Sc>& aO);
 // What every proof's transcript absorbs after Transcript(label) and before
-// V_0: dom-sep("acp v1", n_p), and the deck circuit's "deck" digest -- which
-// is what keeps a two-half proof of k' cards and a deck proof of 2k' cards
-// (same m, n_p and byte length) from verifying as each other.
+// V_0: dom-sep("acp v1", n_p), then the statement's label and digest -- "deck"
+// and the deck's digest, "circuit" and the program's, nothing for the two-half
+// circuit -- which is what keeps proofs of one shape (same m, n_p and byte
+// length: a two-half proof of k' cards, a deck proof of 2k' cards, a program
+// that restates either) from verifying as each other.
+inline const char* statement_label(const Circuit& C) { return C.deck ? "deck" : C.program ? "circuit" : nullptr; }
 inline void transcript_prefix(const Circuit& C, merlin::Transcript& tr) {
   tr.arithmetic_domain_sep(C.n_p);
-  if (C.deck) tr.append("deck", C.deck_digest, 32);
+  if (const char* s = statement_label(C)) tr.append(s, C.deck ? C.deck_digest : C.program_digest, 32);
+}
+
+// Dynamic LDS of the one-workgroup-per-proof kernels k_poly_coef and
+// k_verify_scalars (poly.hip launches them with exactly these; kPolyLanes =
+// POLY_T = POW_LO): z^0..z^Q, two tables of min(n_p, kPolyLanes) powers, and
+// the workgroup-sum scratch of 7 (2) scalars per wave.  kLdsMax: what one
+// workgroup may take.
+constexpr uint32_t kPolyLanes = 256;
+constexpr size_t kLdsMax = 64 * 1024;
+inline size_t poly_coef_lds(uint32_t Q, uint32_t n_p) {
+  return ((size_t)Q + 1 + 2 * (n_p < kPolyLanes ? n_p : kPolyLanes)) * 32 + (kPolyLanes / 64) * 7 * 32;
+}
+inline size_t verify_scalars_lds(uint32_t Q, uint32_t n_p) {
+  return ((size_t)Q + 1 + 2 * (n_p < kPolyLanes ? n_p : kPolyLanes)) * 32 + (kPolyLanes / 64) * 2 * 32;
 }
 
 // v = [1..k, pi(1..k), x]; gate values (sound create_a)

@@ -90,10 +90,15 @@ inline void proof_points(const Proof& P, uint8_t* out) {
 
 // A caller-supplied shuffle (bpp_perm_prove_shuffle_batch, bpp_deck_prove_batch):
 // this batch's slices of the caller's arrays, validated by the entry point.
+// The circuit form (bpp_circuit_prove_batch; C.program set): v, aux and gammas,
+// no cards and no perms.
 struct ShuffleIn {
   const uint8_t* cards;   // [P][k] canonical scalars; nullptr with the deck circuit (the deck is the circuit's)
   const uint32_t* perms;  // [P][k], each a bijection on [0, k)
   const uint8_t* gammas;  // nullptr (drawn), or [P][C.nv] canonical scalars
+  const uint8_t* v = nullptr;    // [P][m_in] canonical scalars: the committed inputs
+  const uint8_t* aux = nullptr;  // [P][n_aux] canonical scalars: the free gate sides' values
+  size_t first = 0;              // this slice's first proof in the caller's batch (error messages)
 };
 
 // One proof's Fiat-Shamir challenges (verify_replay).

@@ -18,6 +18,7 @@
 #include <thread>
 
 #include "perm_internal.h"
+#include "host/circuit.h"
 #include "layout.h"
 #include "merlin_dev.h"
 #include "poly.h"
@@ -108,6 +109,14 @@ bool deck_host_witness() {
   return e && atoi(e) != 0;
 }
 
+// BPP_CIRCUIT_HOST_WITNESS=1: a caller-defined circuit's witness on the host
+// (circuit::eval, bpp_circuit_eval's code) at every size, for the test that
+// compares the two paths
+bool circuit_host_witness() {
+  const char* e = getenv("BPP_CIRCUIT_HOST_WITNESS");
+  return e && atoi(e) != 0;
+}
+
 // Per-proof prover state carried between the lockstep phases.  The states
 // (and their vectors) persist per driver thread across batches: a host
 // profile of 8 batches in flight spent ~20 % of the host CPU in malloc /
@@ -125,7 +134,7 @@ struct ProverScratch {
   // not reuse them
   std::vector<uint32_t> idx, map, off;
   size_t key_P = 0;
-  uint32_t key_k = 0, key_gates = 0;  // (k and C.n: the two circuits of one k differ)
+  uint32_t key_k = 0, key_gates = 0, key_np = 0;  // (k, C.n and C.n_p: the circuits of one k differ, a program has k = 0)
   const bpp_gens* key_G = nullptr;
   size_t key_n = 0;
 };
@@ -134,7 +143,8 @@ struct ProverState {
   merlin::Transcript tr;
   perm::RandomDraws d;  // pi, gamma, alpha, beta, rho, s_L, s_R, tau
   std::vector<Sc> vals, aL, aR, aO;
-  std::vector<Sc> cards;  // a caller-supplied deck, kept for the host witness (k > 768) only
+  std::vector<Sc> cards;  // a caller-supplied deck (k > 768) or a program's inputs, kept for the host witness only
+  std::vector<Sc> aux;    // a program's auxiliary values, likewise
   Sc x_perm, w;
   Sc t[7];
 };
@@ -211,7 +221,7 @@ int prove_wipe(bpp_ctx* ctx) {
   for (auto& S : prover_states_tl()) {
     perm::RandomDraws& d = S->d;
     std::fill(d.pi.begin(), d.pi.end(), 0u);
-    for (auto* v : {&d.gamma, &d.sL, &d.sR, &d.taus, &S->vals, &S->aL, &S->aR, &S->aO, &S->cards})
+    for (auto* v : {&d.gamma, &d.sL, &d.sR, &d.taus, &S->vals, &S->aL, &S->aR, &S->aO, &S->cards, &S->aux})
       std::fill(v->begin(), v->end(), hsc::zero());
     d.alpha = d.beta = d.rho = hsc::zero();
     for (Sc& t : S->t) t = hsc::zero();
@@ -268,8 +278,11 @@ struct ProveBatch {
   // products fit the workgroup's LDS; the host restatement beyond that
   // (BPP_DECK_HOST_WITNESS=1: the deck circuit's host witness at every k, for
   // the test that compares the two paths)
-  const bool dev_witness = C.deck ? k <= DECK_WITNESS_DEV_MAX && !deck_host_witness()
-                                  : (2 * (size_t)k + 512) * 32 <= 64 * 1024;
+  // a caller-defined circuit fits k_witness_program's LDS by construction
+  // (circuit::lds_fits); BPP_CIRCUIT_HOST_WITNESS=1: its host witness
+  const bool dev_witness = C.program ? !circuit_host_witness()
+                           : C.deck  ? k <= DECK_WITNESS_DEV_MAX && !deck_host_witness()
+                                     : (2 * (size_t)k + 512) * 32 <= 64 * 1024;
   // (a plain reference: pool workers must reach THIS thread's states, a
   // thread_local named inside their lambdas would be their own)
   std::vector<std::unique_ptr<ProverState>>& S = prover_states_tl();
@@ -279,6 +292,7 @@ struct ProveBatch {
   // blindings [P][nv] and gamma_nv / 2 [P] ("pv_v", "pv_g", "pv_gx", taken once), and the IPA inputs
   uint32_t *d_gamma = nullptr, *d_s = nullptr, *d_pi = nullptr;
   uint32_t *d_v = nullptr, *d_g = nullptr, *d_gx_half = nullptr;
+  const uint32_t* d_aux = nullptr;  // a program's uploaded auxiliary values [P][n_aux]
   uint32_t *d_l = nullptr, *d_r = nullptr, *d_hf = nullptr;
   MsmPoints pts;
   std::vector<Sc> zwvg = std::vector<Sc>(P);  // <z^Q W_V, gamma> per proof (k_poly_coef)
@@ -327,9 +341,17 @@ int ProveBatch::draws_upload() {
   // read them with 16-byte loads) to the same buffer and the same copy
   const size_t rng_bytes = P * tlen + (size_t)P * k * 4;
   // (the deck circuit's cards are the call's, public: "pb_deck" below)
-  const size_t sh_off = (rng_bytes + 31) & ~(size_t)31, cards_bytes = sh && sh->cards ? (size_t)P * k * 32 : 0;
+  // (a caller-defined circuit: its inputs v in the cards' place, then aux)
+  const uint32_t n_aux = C.program ? C.program->n_aux : 0;
+  if (C.program && !(sh && sh->v && (sh->aux || !n_aux))) {
+    ctx->err = "prove_batch: a caller-defined circuit takes the caller's v and aux";
+    return BPP_ERR_ARG;
+  }
+  const size_t sh_off = (rng_bytes + 31) & ~(size_t)31;
+  const size_t cards_bytes = C.program ? (size_t)P * nv * 32 : sh && sh->cards ? (size_t)P * k * 32 : 0;
+  const size_t aux_bytes = (size_t)P * n_aux * 32;
   const size_t gam_bytes = sh && sh->gammas ? (size_t)P * nv * 32 : 0;
-  const size_t in_bytes = sh ? sh_off + cards_bytes + gam_bytes : rng_bytes;
+  const size_t in_bytes = sh ? sh_off + cards_bytes + aux_bytes + gam_bytes : rng_bytes;
   BPP_TRY(ctx_ws(ctx, "pb_rng_in", in_bytes, &dst));
   d_pi = (uint32_t*)((uint8_t*)dst + P * tlen);
   // (one staging region: a second take could recycle the arena under the first;
@@ -351,7 +373,22 @@ int ProveBatch::draws_upload() {
     perm::draw_prover_host_x8(C, sd, d, !sh);
     for (size_t j = 0; j < 8 && 8 * gi + j < P; ++j) {
       const size_t i = 8 * gi + j;
-      if (sh) {
+      if (C.program) {
+        S[i]->d.pi.clear();
+        memcpy(stage + sh_off + i * 32 * (size_t)nv, sh->v + i * 32 * (size_t)nv, 32 * (size_t)nv);
+        if (n_aux)
+          memcpy(stage + sh_off + cards_bytes + i * 32 * (size_t)n_aux, sh->aux + i * 32 * (size_t)n_aux,
+                 32 * (size_t)n_aux);
+        if (sh->gammas)
+          memcpy(stage + sh_off + cards_bytes + aux_bytes + i * 32 * (size_t)nv, sh->gammas + i * 32 * (size_t)nv,
+                 32 * (size_t)nv);
+        if (!dev_witness) {  // (canonical Sc == its 32 bytes)
+          S[i]->cards.resize(nv);
+          memcpy(S[i]->cards.data(), sh->v + i * 32 * (size_t)nv, 32 * (size_t)nv);
+          S[i]->aux.resize(n_aux);
+          if (n_aux) memcpy(S[i]->aux.data(), sh->aux + i * 32 * (size_t)n_aux, 32 * (size_t)n_aux);
+        }
+      } else if (sh) {
         S[i]->d.pi.assign(sh->perms + i * k, sh->perms + (i + 1) * k);
         if (sh->cards) memcpy(stage + sh_off + i * 32 * (size_t)k, sh->cards + i * 32 * (size_t)k, 32 * (size_t)k);
         if (sh->gammas)
@@ -365,7 +402,7 @@ int ProveBatch::draws_upload() {
       uint64_t tm[7];
       draw_template(sd[j], tm);
       memcpy(stage + i * tlen, tm, tlen);
-      memcpy(pis + i * 4 * (size_t)k, S[i]->d.pi.data(), 4 * (size_t)k);
+      if (k) memcpy(pis + i * 4 * (size_t)k, S[i]->d.pi.data(), 4 * (size_t)k);
     }
   });
   BPP_TRY(ctx_h2d_staged(ctx, dst, stage, in_bytes));  // (pis follows the templates)
@@ -374,7 +411,16 @@ int ProveBatch::draws_upload() {
   BPP_TRY(ctx_ws(ctx, "pv_v", (size_t)P * nv * 32, (void**)&d_v));
   BPP_TRY(ctx_ws(ctx, "pv_g", (size_t)P * nv * 32, (void**)&d_g));
   BPP_TRY(ctx_ws(ctx, "pv_gx", (size_t)P * 32, (void**)&d_gx_half));  // gamma_nv / 2 for V_nv
-  if (C.deck) {
+  if (C.program) {
+    // the draws alone, then the V inputs from the uploaded values (and the
+    // caller's blindings over the drawn gamma_0..m_in-1)
+    const uint8_t* dsh = (const uint8_t*)dst + sh_off;
+    d_aux = (const uint32_t*)(dsh + cards_bytes);
+    BPP_TRY(draws_dev(ctx, C, (uint32_t)P, (const uint64_t*)dst, seeds[0].len, per, d_gamma, d_s));
+    BPP_TRY(circuit_inputs_dev(ctx, C, (uint32_t)P, (const uint32_t*)dsh,
+                               gam_bytes ? (const uint32_t*)(dsh + cards_bytes + aux_bytes) : nullptr, d_gamma, d_v,
+                               d_g, d_gx_half));
+  } else if (C.deck) {
     // the draws alone, then the V inputs deck[perm] from the call's deck (and
     // the caller's blindings over the drawn gamma_0..k-1)
     if (!sh) {
@@ -478,7 +524,11 @@ int ProveBatch::pedersen_Vx_witness() {
   uint32_t* d_vh = nullptr;
   BPP_TRY(upload_sc(ctx, vh, "pv_vx", &d_vh));
   // (a caller's shuffle: both chains' values, as committed)
-  if (dev_witness) {
+  uint32_t* h_fail = nullptr;  // a program's failing assert per proof, written in place (ctx_zc_out)
+  if (dev_witness && C.program) {
+    BPP_TRY(ctx_zc_out(ctx, "wp_fail_h", P * 4, &h_fail));
+    BPP_TRY(witness_program_dev(ctx, C, (uint32_t)P, d_v, d_aux, d_vh + 8 * P, per, d_s, h_fail));
+  } else if (dev_witness) {
     if (C.deck)
       BPP_TRY(witness_deck_dev(ctx, C, (uint32_t)P, d_v, d_vh + 8 * P, per, d_s));
     else
@@ -490,12 +540,16 @@ int ProveBatch::pedersen_Vx_witness() {
   std::vector<Enc32> Vx(P);
   BPP_TRY(ctx_sync(ctx));
   BPP_TRY(points_double_encode_host(ctx, h_p3, P, Vx[0].data()));
+  std::vector<uint32_t> bad(P, 0);  // a program's 1 + first failing assert
+  if (h_fail) memcpy(bad.data(), h_fail, P * 4);
   par::for_each(P, [&](size_t p) {
     Ps[p].V.push_back(Vx[p]);
     S[p]->tr.append_point("V", Vx[p].data());
     if (!dev_witness) {
       ProverState& st = *S[p];
-      if (C.deck)
+      if (C.program)
+        circuit::eval(*C.program, n_p, st.cards.data(), st.aux.data(), st.x_perm, st.aL, st.aR, st.aO, &bad[p]);
+      else if (C.deck)
         perm::witness_deck(C, st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
       else if (sh)
         perm::witness(C, st.cards.data(), st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
@@ -503,6 +557,12 @@ int ProveBatch::pedersen_Vx_witness() {
         perm::witness(C, st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
     }
   });
+  for (size_t p = 0; p < P; ++p)
+    if (bad[p]) {
+      ctx->err = "circuit proof " + std::to_string((sh ? sh->first : 0) + p) + ": assert " +
+                 std::to_string(bad[p] - 1) + " does not hold";
+      return BPP_ERR_ARG;
+    }
   return gens_points(ctx, G, &pts);  // (the MSM and IPA phases' points)
 }
 
@@ -517,7 +577,7 @@ int ProveBatch::msm_AI_AO_S() {
   std::vector<uint32_t>&idx = scr.idx, &map = scr.map, &off = scr.off;
   const uint32_t n = C.n;                       // real gates; n_p - n padding gates are zero
   const uint32_t per_c = 3 + 3 * n + 2 * n_p;  // MSM terms per proof
-  if (scr.key_P != P || scr.key_k != k || scr.key_gates != n || scr.key_G != G || scr.key_n != G->n) {
+  if (scr.key_P != P || scr.key_k != k || scr.key_gates != n || scr.key_np != n_p || scr.key_G != G || scr.key_n != G->n) {
     idx.resize((size_t)P * per_c);
     map.resize((size_t)P * per_c);
     off.resize(3 * P + 1);
@@ -544,6 +604,7 @@ int ProveBatch::msm_AI_AO_S() {
     scr.key_P = P;
     scr.key_k = k;
     scr.key_gates = n;
+    scr.key_np = n_p;
     scr.key_G = G;
     scr.key_n = G->n;
   }
@@ -687,6 +748,12 @@ namespace perm_impl BPP_HIDDEN {
 // commitments (k_deck_inputs), the witness is the one chain of k_witness_deck
 // or perm::witness_deck, and the transcripts start from the deck digest
 // (perm::transcript_prefix); the steps after V_k are the same.
+// With a caller-defined circuit (circuit::compile; sh carries v, aux and
+// optional blindings, no cards and no perms) the V phase commits the caller's
+// m_in values (k_circuit_inputs), the witness is the program interpreted by
+// k_witness_program or circuit::eval -- an assert that does not hold ends the
+// batch there with BPP_ERR_ARG -- and the transcripts start from the program's
+// digest; the steps after V_{m_in} are the same.
 int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
                 const uint8_t* label, size_t llen, std::vector<Proof>& Ps, const ShuffleIn* sh) {
   const size_t P = seeds.size();
@@ -750,9 +817,15 @@ int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, con
         std::vector<Proof> sub;
         std::vector<perm::Seed> part(seeds.begin() + b, seeds.begin() + e);
         ShuffleIn shs;  // this sub-batch's slices of the caller's witness
-        if (sh)
-          shs = {sh->cards ? sh->cards + b * 32 * (size_t)k : nullptr, sh->perms + b * (size_t)k,
+        if (sh) {
+          shs = {sh->cards ? sh->cards + b * 32 * (size_t)k : nullptr, sh->perms ? sh->perms + b * (size_t)k : nullptr,
                  sh->gammas ? sh->gammas + b * 32 * (size_t)C.nv : nullptr};
+          if (C.program) {
+            shs.v = sh->v + b * 32 * (size_t)C.nv;
+            shs.aux = sh->aux ? sh->aux + b * 32 * (size_t)C.program->n_aux : nullptr;
+          }
+          shs.first = sh->first + b;
+        }
         rcs[s] = prove_batch(kc, G, C, part, label, llen, sub, sh ? &shs : nullptr);
         if (rcs[s] == BPP_OK)
           for (size_t i = b; i < e; ++i) Ps[i] = std::move(sub[i - b]);

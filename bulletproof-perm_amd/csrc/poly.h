@@ -71,5 +71,22 @@ int deck_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint
 // kernel's own LDS budget, (k + 2 x 256) x 32 B <= 64 KB; the host witness
 // (perm::witness_deck) beyond.
 #define DECK_WITNESS_DEV_MAX 1536u
+
+// A caller-defined circuit (host/circuit.h).  circuit_inputs_dev
+// (k_circuit_inputs), after draws_dev without d_v on the same stream: d_v
+// [P][m_in] = the caller's values (d_vals [P][m_in] canonical), d_g [P][m_in] =
+// the drawn gamma_0..m_in-1 or, when d_gammas ([P][m_in]) is non-null, the
+// caller's, which then replace d_gamma's ([P][m_in + 1]) too; d_gx_half [P] =
+// gamma_m_in / 2.
+int circuit_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
+                       const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v, uint32_t* d_g,
+                       uint32_t* d_gx_half);
+// witness_program_dev (k_witness_program): every proof's workgroup interprets
+// C.program over its own values (d_vals [P][m_in], d_aux [P][n_aux], d_x [P],
+// canonical): a_L, a_R, a_O into their slots of d_sc, and into fail[p] (pinned
+// host memory, valid after the next ctx_sync) 1 + the first assert that does
+// not hold, or 0.
+int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
+                        const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail);
 int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals, const uint32_t* d_x,
                      uint32_t per, uint32_t* d_sc);

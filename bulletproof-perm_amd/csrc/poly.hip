@@ -22,6 +22,7 @@
 
 #include "ctx.h"
 #include "poly.h"
+#include "host/circuit.h"
 #include "verify_dev.h"
 #include "keccak_dev.cuh"
 #include "sc25519.cuh"
@@ -136,6 +137,7 @@ FE_INLINE sc col_sum_block(const uint32_t* __restrict__ cp, const uint32_t* __re
 // grid = P proofs, block = poly_block(max(n_p, m)); dynamic LDS = (Q + 1 + 2 min(n_p, POW_LO)) * 32 + (POLY_T / 64) * 7 * 32
 // t_out[p] = t_1..t_6, <z^Q W_V, gamma_p> (gamma: [P][m] canonical)
 #define POLY_NT 7
+static_assert(POLY_T == perm::kPolyLanes && POLY_NT == 7, "perm::poly_coef_lds / verify_scalars_lds state these");
 __global__ void __launch_bounds__(POLY_T) k_poly_coef(uint32_t n_p, uint32_t m, uint32_t Q, uint32_t per,
                                                    const uint32_t* __restrict__ sc_in,
                                                    const uint32_t* __restrict__ ch,
@@ -932,6 +934,201 @@ int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uin
   return ctx_check_launch(ctx, "k_witness_deck");
 }
 
+// The V phase's inputs of a caller-defined circuit (bpp_circuit_prove_batch),
+// one lane per commitment input (P x m lanes, m = m_in + 1, after k_draws with
+// v = nullptr on the same stream): v[p][j] = vals[p][j] (j < m_in), g[p][j] =
+// the blinding of V_j: the drawn gamma[p][j], or the caller's gammas[p][j]
+// ([P][m_in]), which then also replaces gamma[p][j] (k_poly_coef reads it for
+// tau_x); gx_half[p] = gamma_m_in / 2 (always drawn).
+__global__ void __launch_bounds__(256) k_circuit_inputs(uint32_t P, uint32_t m_in, const uint32_t* __restrict__ vals,
+                                                       const uint32_t* __restrict__ gammas,
+                                                       uint32_t* __restrict__ gamma, uint32_t* __restrict__ v,
+                                                       uint32_t* __restrict__ g, uint32_t* __restrict__ gx_half) {
+  const uint32_t m = m_in + 1;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)P * m) return;
+  const uint32_t p = (uint32_t)(t / m), j = (uint32_t)(t % m);
+  uint32_t* gm = gamma + 8 * ((size_t)p * m + j);
+  if (j == m_in) {
+    sc_store(gx_half + 8 * (size_t)p, sc_half(sc_load(gm)));
+    return;
+  }
+  const size_t o = 8 * ((size_t)p * m_in + j);
+  sc_store(v + o, sc_load(vals + o));
+  sc x;
+  if (gammas) {
+    x = sc_load(gammas + o);
+    sc_store(gm, x);
+  } else {
+    x = sc_load(gm);
+  }
+  sc_store(g + o, x);
+}
+
+int circuit_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
+                       const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v, uint32_t* d_g,
+                       uint32_t* d_gx_half) {
+  if (!P) return BPP_OK;
+  const size_t nt = (size_t)P * C.m;
+  hipLaunchKernelGGL(k_circuit_inputs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, P, C.nv, d_vals,
+                     d_gammas, d_gamma, d_v, d_g, d_gx_half);
+  return ctx_check_launch(ctx, "k_circuit_inputs");
+}
+
+// The witness of a caller-defined circuit (host/circuit.h; host restatement
+// circuit::eval), one proof per workgroup, every workgroup interpreting the
+// same program on its own proof's data: prog = the program's device image
+// (side_aux [2n], then lc_off, lc_wire, level_off, level_gate, the terms'
+// flagged variable ids and their 32-byte-aligned Montgomery coefficients at the
+// given word offsets).  The 3n wire values live in LDS in Montgomery form (wire
+// id 3h + {0, 1, 2} = l_h, r_h, o_h).  First every gate side, one lane each:
+// an aux load, or the part of its combination over {1, v_j, x} (a col_sum-style
+// term loop up to lc_wire) -- no side waits for another here.  Then the gates
+// by dependency level: within a level one lane per gate adds the wire terms of
+// both sides and forms the product, then a barrier -- a definition reads wires
+// of lower levels only.  A term of coefficient 1 or -1 (the id's flag) adds or
+// subtracts its value without a multiply, so a product chain's level is one
+// multiply deep.  a_L, a_R, a_O go canonical into their slots of the [P][per]
+// array, padding gates zero.  The asserts are evaluated by the same lanes;
+// fail[p] = 1 + the first that does not hold, or 0.
+//
+// A level is a chain of dependent loads (gate index -> term offsets -> ids and
+// coefficients -> values) in front of its multiplies; from global memory those
+// round trips, not the arithmetic, were the kernel's time (0.38 ms for 384
+// proofs of the two-half circuit at 52 cards, 54 levels).  STAGE: the device
+// image and the proof's inputs (Montgomery form) are copied into LDS first and
+// every level reads them there; taken whenever they fit beside the wires
+// (circuit::witness_program_staged_lds), the plain form beyond.
+// dynamic LDS = 32 B (the fail word) + 3n x 32 B [+ m_in x 32 B + the image].
+template <bool STAGE>
+FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, uint32_t n_p, uint32_t n_aux, uint32_t A,
+                                    uint32_t nlev, uint32_t per, const uint32_t* __restrict__ prog,
+                                    uint32_t prog_words, uint32_t o_lc, uint32_t o_wire, uint32_t o_lev, uint32_t o_gate,
+                                    uint32_t o_var, uint32_t o_coef, const uint32_t* __restrict__ vals,
+                                    const uint32_t* __restrict__ aux, const uint32_t* __restrict__ xs,
+                                    uint32_t* __restrict__ sc_out, uint32_t* __restrict__ fail) {
+  uint32_t* bad = lds;                        // 1 + the first failing assert (8 words kept for alignment)
+  uint32_t* wires = lds + 8;                  // [3n] Montgomery
+  uint32_t* vm = wires + 8 * 3 * (size_t)n;   // STAGE: [m_in] inputs, Montgomery
+  uint32_t* image = vm + 8 * (size_t)m_in;    // STAGE: [prog_words] the device image
+  const uint32_t p = blockIdx.x, nt = blockDim.x, t = threadIdx.x;
+  const uint32_t* vp = vals + 8 * (size_t)p * m_in;
+  const uint32_t* pg = prog;
+  if constexpr (STAGE) {
+    for (uint32_t i = t; i < prog_words; i += nt) image[i] = prog[i];
+    for (uint32_t j = t; j < m_in; j += nt) sc_store(vm + 8 * (size_t)j, sc_to_mont(sc_load(vp + 8 * (size_t)j)));
+    pg = image;
+  }
+  const uint32_t *side_aux = pg, *lc_off = pg + o_lc, *lc_wire = pg + o_wire, *lev_off = pg + o_lev,
+                 *lev_gate = pg + o_gate, *tvar = pg + o_var, *tcoef = pg + o_coef;
+  const sc oneR = sc_one_mont(), xR = sc_to_mont(sc_load(xs + 8 * (size_t)p));
+  if (t == 0) *bad = 0xFFFFFFFFu;
+  __syncthreads();
+  auto input = [&](uint32_t j) {  // v_j, Montgomery
+    if constexpr (STAGE) return sc_load(vm + 8 * (size_t)j);
+    return sc_to_mont(sc_load(vp + 8 * (size_t)j));
+  };
+  auto terms = [&](sc acc, uint32_t b, uint32_t e_end) {  // acc + terms [b, e_end), Montgomery
+    for (uint32_t e = b; e < e_end; ++e) {
+      const uint32_t tv = tvar[e], var = tv & circuit::kTermVar;
+      const sc val = var == 0 ? oneR
+                              : var <= m_in ? input(var - 1)
+                                            : var == m_in + 1 ? xR : sc_load(wires + 8 * (size_t)(var - 2 - m_in));
+      if (tv & circuit::kTermOne)
+        acc = sc_add(acc, val);
+      else if (tv & circuit::kTermNeg)
+        acc = sc_sub(acc, val);
+      else
+        acc = sc_add(acc, sc_mont(val, sc_load(tcoef + 8 * (size_t)e)));
+    }
+    return acc;
+  };
+  for (uint32_t u = t; u < 2 * n; u += nt) {  // side u = 2g + s
+    const uint32_t a = side_aux[u];
+    const sc v = a == 0xFFFFFFFFu ? terms(sc_zero(), lc_off[u], lc_wire[u])
+                                  : sc_to_mont(sc_load(aux + 8 * ((size_t)p * n_aux + a)));
+    sc_store(wires + 8 * (3 * (size_t)(u >> 1) + (u & 1u)), v);
+  }
+  __syncthreads();
+  for (uint32_t lev = 0; lev < nlev; ++lev) {
+    for (uint32_t u = lev_off[lev] + t; u < lev_off[lev + 1]; u += nt) {
+      const uint32_t g = lev_gate[u];
+      sc side[2];
+      _Pragma("unroll") for (uint32_t s = 0; s < 2; ++s) {
+        const uint32_t i = 2 * g + s, wb = lc_wire[i], we = lc_off[i + 1];
+        side[s] = sc_load(wires + 8 * (3 * (size_t)g + s));
+        if (wb < we) {  // (a free side's combination is empty)
+          side[s] = terms(side[s], wb, we);
+          sc_store(wires + 8 * (3 * (size_t)g + s), side[s]);
+        }
+      }
+      sc_store(wires + 8 * (3 * (size_t)g + 2), sc_mont(side[0], side[1]));
+    }
+    __syncthreads();
+  }
+  uint32_t* o = sc_out + 8 * (size_t)p * per;
+  for (uint32_t g = t; g < n_p; g += nt) {
+    sc w[3] = {sc_zero(), sc_zero(), sc_zero()};
+    if (g < n)
+      _Pragma("unroll") for (uint32_t s = 0; s < 3; ++s) w[s] = sc_from_mont(sc_load(wires + 8 * (3 * (size_t)g + s)));
+    sc_store(o + 8 * (1 + g), w[0]);
+    sc_store(o + 8 * (1 + n_p + g), w[1]);
+    sc_store(o + 8 * (2 + 2 * n_p + g), w[2]);
+  }
+  for (uint32_t a = t; a < A; a += nt) {
+    const sc r = sc_from_mont(terms(sc_zero(), lc_off[2 * n + a], lc_off[2 * n + a + 1]));
+    uint32_t nz = 0;
+    _Pragma("unroll") for (int i = 0; i < 8; ++i) nz |= r.v[i];
+    if (nz) atomicMin(bad, a + 1);
+  }
+  __syncthreads();
+  if (t == 0) fail[p] = *bad == 0xFFFFFFFFu ? 0u : *bad;
+}
+
+#define WITNESS_PROGRAM_ARGS                                                                                         \
+  uint32_t m_in, uint32_t n, uint32_t n_p, uint32_t n_aux, uint32_t A, uint32_t nlev, uint32_t per,                  \
+      const uint32_t *__restrict__ prog, uint32_t prog_words, uint32_t o_lc, uint32_t o_wire, uint32_t o_lev,       \
+      uint32_t o_gate, uint32_t o_var, uint32_t o_coef, const uint32_t *__restrict__ vals, const uint32_t *__restrict__ aux,         \
+      const uint32_t *__restrict__ xs, uint32_t *__restrict__ sc_out, uint32_t *__restrict__ fail
+#define WITNESS_PROGRAM_PASS \
+  m_in, n, n_p, n_aux, A, nlev, per, prog, prog_words, o_lc, o_wire, o_lev, o_gate, o_var, o_coef, vals, aux, xs, \
+      sc_out, fail
+__global__ void __launch_bounds__(256) k_witness_program(WITNESS_PROGRAM_ARGS) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  witness_program_body<true>(lds, WITNESS_PROGRAM_PASS);
+}
+// the plain form: program and inputs read from global memory
+__global__ void __launch_bounds__(256) k_witness_program_global(WITNESS_PROGRAM_ARGS) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  witness_program_body<false>(lds, WITNESS_PROGRAM_PASS);
+}
+
+int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
+                        const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail) {
+  if (!P) return BPP_OK;
+  const circuit::Program& G = *C.program;
+  const bool stage = circuit::witness_program_staged_lds(G) <= perm::kLdsMax;
+  const size_t lds = stage ? circuit::witness_program_staged_lds(G) : circuit::witness_program_lds(G.n);
+  if (lds > perm::kLdsMax) {
+    ctx->err = "witness_program_dev: gates beyond the kernel's LDS budget";
+    return BPP_ERR_LEN;
+  }
+  void* d_prog = nullptr;
+  BPP_TRY(ctx_ws(ctx, "wp_prog", G.dev.size() * 4, &d_prog));
+  BPP_TRY(ctx_h2d_const(ctx, "wp_prog", d_prog, G.dev.data(), G.dev.size() * 4));  // the circuit: same every batch
+  // whole waves, no more lanes than the padded gates (narrow levels leave the
+  // rest waiting at the barriers)
+  const unsigned nt = std::min<unsigned>(256, std::max<unsigned>(64, (C.n_p + 63) & ~63u));
+  {
+    ProfScope ps(ctx, "witness_program");
+    hipLaunchKernelGGL(stage ? k_witness_program : k_witness_program_global, dim3(P), dim3(nt), lds, ctx->stream,
+                       G.m_in, G.n, C.n_p, G.n_aux, G.A, (uint32_t)G.level_off.size() - 1, per,
+                       (const uint32_t*)d_prog, (uint32_t)G.dev.size(), G.dev_lc_off, G.dev_lc_wire, G.dev_level_off,
+                       G.dev_level_gate, G.dev_vars, G.dev_coefs, d_vals, d_aux, d_x, d_sc, fail);
+  }
+  return ctx_check_launch(ctx, stage ? "k_witness_program" : "k_witness_program_global");
+}
+
 // The V phase's inputs of a caller-supplied shuffle, one lane per commitment
 // input (P x m lanes, after k_draws with v = nullptr on the same stream):
 // v[p][i] = cards[p][i], v[p][k + i] = cards[p][perm[p][i]] (i < k; perm is a
@@ -985,7 +1182,10 @@ int witness_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t
   const unsigned nt = (2 * (size_t)C.k + 4 * 256) * 32 <= 64 * 1024 ? 256 : 128;
   const size_t lds = (2 * (size_t)C.k + 4 * nt) * 32;
   if (d_vals) {
-    hipLaunchKernelGGL(k_witness_cards, dim3(P), dim3(nt), lds, ctx->stream, C.k, C.n_p, per, d_vals, d_x, d_sc);
+    {
+      ProfScope ps(ctx, "witness_cards");
+      hipLaunchKernelGGL(k_witness_cards, dim3(P), dim3(nt), lds, ctx->stream, C.k, C.n_p, per, d_vals, d_x, d_sc);
+    }
     return ctx_check_launch(ctx, "k_witness_cards");
   }
   hipLaunchKernelGGL(k_witness, dim3(P), dim3(nt), lds, ctx->stream, C.k, C.n_p, per, d_pi, d_x, d_sc);
@@ -1055,11 +1255,12 @@ void build_csr(const perm::Circuit& C, std::vector<uint32_t>& cp, std::vector<ui
 }
 
 unsigned poly_block(uint32_t n_p) { return n_p < 64 ? 64u : (n_p > POLY_T ? POLY_T : n_p); }
-// lanes per proof of k_poly_coef / k_verify_scalars; the deck circuit's in
-// whole waves (its m = k + 1 reaches n_p + 2)
+// lanes per proof of k_poly_coef / k_verify_scalars; the deck circuit's and a
+// caller-defined circuit's in whole waves (the deck's m = k + 1 reaches n_p + 2,
+// a program's m exceeds n_p by any amount)
 unsigned poly_block(const perm::Circuit& C) {
   const unsigned nt = poly_block(std::max(C.n_p, C.m));
-  return C.deck ? std::min<unsigned>(POLY_T, (nt + 63) & ~63u) : nt;
+  return C.deck || C.program ? std::min<unsigned>(POLY_T, (nt + 63) & ~63u) : nt;
 }
 
 }  // namespace
@@ -1084,7 +1285,7 @@ int poly_coef_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32
   BPP_TRY(ctx_h2d_const(ctx, "poly_cp", d_cp, cp.data(), cp.size() * 4));  // the circuit: same every batch
   BPP_TRY(ctx_h2d_const(ctx, "poly_ce", d_ce, ce.data(), ce.size() * 4));
   const unsigned nt = poly_block(C);
-  const size_t lds = ((size_t)C.Q + 1 + 2 * std::min(C.n_p, (uint32_t)POW_LO)) * 32 + (POLY_T / 64) * POLY_NT * 32;
+  const size_t lds = perm::poly_coef_lds(C.Q, C.n_p);
   {
     ProfScope ps(ctx, "poly_coef");
     hipLaunchKernelGGL(k_poly_coef, dim3(P), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, per, d_sc,
@@ -1153,7 +1354,7 @@ int verify_scalars_dev_rec(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count,
   BPP_TRY(ctx_h2d_const(ctx, "vs_ce", d_ce, ce.data(), ce.size() * 4));
   BPP_TRY(ctx_h2d_const(ctx, "vs_c", d_c, cw.data(), cw.size() * 4));
   const unsigned nt = poly_block(C);
-  const size_t lds = ((size_t)C.Q + 1 + 2 * std::min(C.n_p, (uint32_t)POW_LO)) * 32 + (POLY_T / 64) * 2 * 32;
+  const size_t lds = perm::verify_scalars_lds(C.Q, C.n_p);
   if (C.lg > VC_LGMAX) return BPP_ERR_LEN;  // (k_verify_consts' LDS tables)
   void *d_kc = nullptr, *d_deck = nullptr;
   BPP_TRY(ctx_ws(ctx, "vs_kc", (size_t)count * VK_N * 32, &d_kc));

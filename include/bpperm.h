@@ -446,6 +446,101 @@ int bpp_deck_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size
                                const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
                                uint8_t* ok_out);
 
+/* -------------------------------------- caller-defined circuits (sound) */
+/* After the shuffle a game needs predicates over the commitments it produced
+ * ("the card I play is one of these 13", "this value is below 2^6", "these two
+ * hands hold the same multiset").  A statement is a gate program in the style
+ * of an R1CS constraint system, compiled once (bpp_circuit_create) to the
+ * arithmetic circuit W_L a_L + W_R a_R + W_O a_O = W_V v + c that the two
+ * built-in statements are instances of, then proved and verified in batches
+ * over the same GPU path.
+ * Variables: the committed inputs v_0..v_{m_in-1} (per proof); the challenge x
+ * (x_perm: squeezed after V_0..V_{m_in-1}, committed as V_{m_in} and bound by
+ * the library's own last row); the wires l_h, r_h, o_h = l_h r_h of n_gates
+ * multiplication gates.  A gate side is DEFINED -- a sparse linear combination
+ * over {1, v_j, x, wires of gates h < g} -- or FREE: fed from the per-proof
+ * auxiliary value aux_t, supplied before x exists (bits and other hints).
+ * n_asserts assert rows each force a combination over ANY variable to 0.
+ * Rows: defined left sides by gate, defined right sides by gate, the asserts,
+ * then v_{m_in} = x.  Defined side of gate g at row q: 1 at (q, g) of its own
+ * matrix, a wire term a -> -a in the wire's matrix, a v_j or x term -> W_V = a,
+ * the constant -> c[q] = a.  Assert row: wire terms +a, v and x terms -a, the
+ * constant -a.  Q = defined sides + n_asserts + 1, m = m_in + 1, n_p = max(4,
+ * next_pow2(n_gates)) <= bpp_gens_len(g), proof bytes 32 (13 + 2 log2 n_p).
+ * The two-half circuit written this way compiles to bpp_perm_*'s matrices; the
+ * deck circuit cannot be written (its constant depends on x).
+ * Inside one combination the variable ids are strictly increasing and every
+ * coefficient is canonical and nonzero, so one description has one digest:
+ * SHAKE256("bpperm-circuit" || le32 m_in || le32 n_gates || le32 n_aux ||
+ * le32 n_asserts || side_aux || lc_off || lc_var || lc_coef)[0..32].
+ * Transcript: Transcript(label), dom-sep("acp v1", n_p),
+ * append_message("circuit", digest), V_0..V_{m_in-1}, challenge x_perm,
+ * V_{m_in}, A_I A_O S and on as bpp_perm_*.  Draws: gamma[m], alpha, beta, rho,
+ * s_L[n_p], s_R[n_p], tau[5] by index as above; supplied gammas replace draws
+ * 0..m_in-1; no pi stream is read.
+ * Bounds (BPP_ERR_LEN beyond them): every per-proof kernel keeps its tables in
+ * one workgroup's 64 KB of LDS -- (Q + 1 + 2 min(n_p, 256)) x 32 B + 896 B for
+ * the polynomial and verifier kernels, i.e. Q <= 1507 at n_p >= 256, and
+ * 3 n_gates x 32 B + 32 B for the witness kernel, i.e. n_gates <= 682.  512
+ * gates with both sides defined (Q = 1025 + n_asserts) fit. */
+typedef struct bpp_circuit bpp_circuit;
+#define BPP_SIDE_LC 0xFFFFFFFFu
+typedef struct {
+  uint32_t m_in, n_gates, n_aux, n_asserts;
+  const uint32_t* side_aux; /* [2n]: side 2g = left of gate g, 2g+1 = right; BPP_SIDE_LC = defined, else aux index */
+  const uint32_t* lc_off;   /* [2n + A + 1] term offsets; LC 2g, 2g+1 = gate g's sides (empty when free), then the asserts */
+  const uint32_t* lc_var;   /* 0 = one; 1+j = v_j; 1+m_in = x; 2+m_in+3h+{0,1,2} = l_h, r_h, o_h */
+  const uint8_t* lc_coef;   /* [T][32] canonical, nonzero */
+} bpp_circuit_desc;
+/* Validates and compiles desc (no GPU; the arrays are copied).  BPP_ERR_ARG:
+ * m_in = 0 or n_gates = 0, an id or aux index out of range, a definition that
+ * reads a wire of gate h >= g, a nonempty combination on a free side, unsorted
+ * or duplicate ids, a zero coefficient, a non-monotone lc_off;
+ * BPP_ERR_NONCANONICAL: a coefficient >= l; BPP_ERR_LEN: beyond the bounds
+ * above. */
+int bpp_circuit_create(const bpp_circuit_desc* desc, bpp_circuit** out);
+void bpp_circuit_destroy(bpp_circuit* c);
+/* n_p, Q, m = m_in + 1 and the 32-byte digest (any of them may be NULL). */
+int bpp_circuit_info(const bpp_circuit* c, uint32_t* n_p, uint32_t* Q, uint32_t* m, uint8_t digest[32]);
+size_t bpp_circuit_proof_len(const bpp_circuit* c);
+/* The compiled rows, for audit (no GPU).  which = 0..3: W_L, W_R, W_O, W_V as
+ * (q, col, val) triplets; which = 4: c as (q, 0, c[q]) for every row (c[Q-1],
+ * set per proof to -x, reads 0).  *count in: the capacity of q / col / val
+ * (count x 4, x 4, x 32 B; they may be NULL with capacity 0); out: the number
+ * of triplets.  BPP_ERR_LEN if the capacity is short (count is still set). */
+int bpp_circuit_matrix(const bpp_circuit* c, uint32_t which, uint32_t* q, uint32_t* col, uint8_t* val, size_t* count);
+/* The host witness (no GPU): a_L, a_R, a_O (n_p x 32 B each, padding gates
+ * zero) from v (m_in x 32 B), aux (n_aux x 32 B) and x, canonical scalars
+ * (BPP_ERR_NONCANONICAL otherwise); *bad_assert = 1 + the first assert that
+ * does not hold, or 0.  The code BPP_CIRCUIT_HOST_WITNESS=1 runs in the prover. */
+int bpp_circuit_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* aux, const uint8_t x[32], uint8_t* aL,
+                     uint8_t* aR, uint8_t* aO, uint32_t* bad_assert);
+/* Proves count statements of c:
+ *   v       count x m_in x 32 B: the committed inputs (proof-major);
+ *   aux     count x n_aux x 32 B: the free sides' values (NULL when n_aux = 0);
+ *   gammas  NULL, or count x m_in x 32 B: the blindings of V_0..V_{m_in-1};
+ *   seeds32, label, proofs_out as bpp_deck_prove_batch; V_out count x (m_in + 1) x 32 B.
+ * Every v, aux and gamma is checked canonical before any device work
+ * (BPP_ERR_NONCANONICAL).  If an assert does not hold for some proof the call
+ * returns BPP_ERR_ARG, bpp_ctx_last_error names the proof and the assert, no
+ * output byte is written, and the batch's secrets are wiped as on success
+ * (the lifetime of bpp_perm_prove_batch_entropy; v, aux and gammas are part of
+ * what is zeroed).  The witness is interpreted on the GPU (k_witness_program);
+ * BPP_CIRCUIT_HOST_WITNESS=1 selects the host witness. */
+int bpp_circuit_prove_batch(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit* c, size_t count, const uint8_t* v,
+                            const uint8_t* aux, const uint8_t* gammas, const uint8_t* seeds32, const uint8_t* label,
+                            size_t llen, uint8_t* proofs_out, uint8_t* V_out);
+/* The verifiers mirror bpp_deck_verify, _verify_batch and _verify_batch_each
+ * with c in place of (k, deck): the same kernels and launches as
+ * bpp_perm_verify*.  The multi-GPU job API takes two-half proofs only. */
+int bpp_circuit_verify(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit* c, const uint8_t* label, size_t llen,
+                       const uint8_t* proof, size_t proof_len, const uint8_t* V);
+int bpp_circuit_verify_batch(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit* c, size_t count, const uint8_t* label,
+                             size_t llen, const uint8_t* proofs, const uint8_t* V);
+int bpp_circuit_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit* c, size_t count,
+                                  const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
+                                  uint8_t* ok_out);
+
 /* Batch verification split for several GPUs (north_star: "the single large
  * verifier MSM partitions its bucket windows across GPUs"; reference verify
  * circuit_lib.rs:478-585).  Host phase, no GPU: parse `count` proofs, replay
