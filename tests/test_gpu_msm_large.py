@@ -1,8 +1,10 @@
-"""Large-size MSM parity (the single-MSM sort paths, n >= 2^14: two-pass
-radix sort by default, the one-pass LDS sort under BPP_MSM_LDS_SORT=1).
+"""Large-size MSM parity (the single-MSM sort paths, n >= 2^14: the one-pass
+LDS sort from 16384 terms, where c = 11; the two-pass radix sort from 26331
+terms, where c reaches 12, unless BPP_MSM_LDS_SORT=1 keeps the LDS sort).
 
-Exact: GPU vs the serial C restatement of dalek's MSM (oracle/c) at 2^14 and
-2^17 terms.  Full size (BASELINE config 3, 2^20 terms): size-independent
+Exact: GPU vs the serial C restatement of dalek's MSM (oracle/c) at 2^14 (LDS
+sort) and 2^17 terms (radix sort, and the LDS sort by the switch); each case
+asserts which front end ran.  Full size (BASELINE config 3, 2^20 terms): size-independent
 properties — linearity in the scalars (MSM(s) + MSM(t) == MSM(s + t)),
 window-partition consistency (sum of partials == full), and the adversarial
 all-equal-scalar input (every term in one bucket per window)."""
@@ -47,7 +49,19 @@ def test_msm_exact_vs_cport(ctx, big_table, logn, lds, acc_k, monkeypatch):
     n = 1 << logn
     sc = _sb(_scalars(n, logn))
     pts = cport.from_uniform(raw[: 64 * n])
-    assert ctx.msm_table(sc, tbl, n) == cport.msm(sc, pts)
+    ctx.profile(True)
+    ctx.profile_reset()
+    try:
+        got = ctx.msm_table(sc, tbl, n)
+        digits, count = ctx.profile_get("msm_digits")[1], ctx.profile_get("msm_count")[1]
+    finally:
+        ctx.profile(False)
+        ctx.profile_reset()
+    assert got == cport.msm(sc, pts)
+    # k_msm_digits and a count pass: the LDS sort; digits folded into the
+    # radix sort's first kernel and no count pass: the radix sort
+    want_front = {(14, False): "lds", (17, False): "radix", (17, True): "lds"}[(logn, lds)]
+    assert (digits > 0, count > 0) == {"lds": (True, True), "radix": (True, False)}[want_front]
 
 
 def test_msm_2p20_linearity_and_partials(ctx, big_table):
