@@ -781,10 +781,11 @@ class _CircuitDescC(C.Structure):
 
 
 class Circuit:
-    """A compiled caller-defined circuit (bpp_circuit_create; no GPU): desc is
-    a gadgets.CircuitDesc (or anything with its fields).  n_p, Q, m, digest and
-    proof_len are the compiled statement's; matrix() and eval() expose the
-    compiled rows and the host witness."""
+    """A compiled caller-defined circuit (bpp_circuit_create, or
+    bpp_circuit_create_pub when desc.n_pub; no GPU): desc is a
+    gadgets.CircuitDesc (or anything with its fields).  n_p, Q, m, n_pub,
+    digest and proof_len are the compiled statement's; matrix() and eval()
+    expose the compiled rows and the host witness."""
 
     def __init__(self, desc):
         self.lib = _lib.load()
@@ -794,8 +795,12 @@ class Circuit:
         d = _CircuitDescC(desc.m_in, desc.n_gates, desc.n_aux, desc.n_asserts, self._keep[0], self._keep[1],
                           self._keep[2], self._keep[3])
         h = C.c_void_p()
-        check(self.lib.bpp_circuit_create(C.byref(d), C.byref(h)), "bpp_circuit_create")
+        if getattr(desc, "n_pub", 0):
+            check(self.lib.bpp_circuit_create_pub(C.byref(d), desc.n_pub, C.byref(h)), "bpp_circuit_create_pub")
+        else:
+            check(self.lib.bpp_circuit_create(C.byref(d), C.byref(h)), "bpp_circuit_create")
         self.h = h
+        self.n_pub = int(self.lib.bpp_circuit_n_pub(h))
         n_p, Q, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
         dg = C.create_string_buffer(32)
         check(self.lib.bpp_circuit_info(h, C.byref(n_p), C.byref(Q), C.byref(m), dg), "bpp_circuit_info")
@@ -816,7 +821,7 @@ class Circuit:
 
     def matrix(self, which: int):
         """Triplets (q, col, val bytes) of W_L, W_R, W_O, W_V (which = 0..3) or
-        of c (which = 4: (q, 0, c[q]))."""
+        of c (which = 4: (q, 0, c[q])), or of W_U (which = 5: (q, i, val))."""
         n = C.c_size_t(0)
         rc = self.lib.bpp_circuit_matrix(self.h, which, None, None, None, C.byref(n))
         if rc not in (0, 2):
@@ -827,13 +832,20 @@ class Circuit:
         check(self.lib.bpp_circuit_matrix(self.h, which, q, col, val, C.byref(n)), "bpp_circuit_matrix")
         return [(q[i], col[i], val.raw[32 * i:32 * i + 32]) for i in range(cnt)]
 
-    def eval(self, v, aux, x: bytes):
+    def eval(self, v, aux, x: bytes, pub=None):
         """The host witness: (a_L, a_R, a_O) as lists of n_p 32-byte scalars,
-        and 1 + the first assert that does not hold (0: all hold)."""
+        and 1 + the first assert that does not hold (0: all hold).  pub: the
+        n_pub public inputs (bpp_circuit_eval_pub)."""
         vb, ab = _join(v, 32, "v"), _join(aux, 32, "aux")
         outs = [C.create_string_buffer(32 * self.n_p) for _ in range(3)]
         bad = C.c_uint32()
-        check(self.lib.bpp_circuit_eval(self.h, _buf(vb), _buf(ab), _buf(x), *outs, C.byref(bad)), "bpp_circuit_eval")
+        if pub is not None:
+            ub = _join(pub, 32, "pub")
+            check(self.lib.bpp_circuit_eval_pub(self.h, _buf(vb), _buf(ab), _buf(ub) if ub else None, _buf(x), *outs,
+                                                C.byref(bad)), "bpp_circuit_eval_pub")
+        else:
+            check(self.lib.bpp_circuit_eval(self.h, _buf(vb), _buf(ab), _buf(x), *outs, C.byref(bad)),
+                  "bpp_circuit_eval")
         return tuple([o.raw[32 * i:32 * i + 32] for i in range(self.n_p)] for o in outs) + (bad.value,)
 
 
@@ -849,14 +861,24 @@ class CircuitProver:
         self.proof_len = self.circuit.proof_len
         self.m = self.circuit.m
 
+    def _pub(self, pub, count: int):
+        """pub[p] = the n_pub public inputs of proof p (or each proof's joined)
+        -> the joined bytes of the _pub entry points."""
+        ub = b"".join(x if isinstance(x, (bytes, bytearray)) else _join(x, 32, "pub") for x in pub)
+        if len(ub) != 32 * self.circuit.n_pub * count:
+            raise ValueError("pub: expected n_pub scalars of 32 bytes per proof")
+        return _buf(ub) if ub else None
+
     def prove_batch(self, v, aux=None, seeds32: bytes | None = None, gammas=None, raw: bool = False,
-                    out: "tuple | None" = None):
+                    out: "tuple | None" = None, pub=None):
         """v[p] = the m_in committed inputs of proof p, aux[p] = its n_aux
         auxiliary values, gammas[p] = the m_in blindings of V_0..V_{m_in-1}
         (None: drawn) -- 32-byte scalars (or each proof's joined); seeds32 = 32
         bytes per proof (None: the OS CSPRNG).  out = (proofs, V) ctypes buffers
-        to write into instead of fresh ones.  Returns what
-        DeckProver.prove_batch returns; the batch's secrets are wiped."""
+        to write into instead of fresh ones.  pub[p] = the n_pub public inputs
+        of proof p (bpp_circuit_prove_batch_pub; None: the entry point without
+        them).  Returns what DeckProver.prove_batch returns; the batch's
+        secrets are wiped."""
         c = self.circuit
         count = len(v)
         row = lambda rows, what: b"".join(x if isinstance(x, (bytes, bytearray)) else _join(x, 32, what) for x in rows)
@@ -878,21 +900,30 @@ class CircuitProver:
             V = C.create_string_buffer(max(32 * self.m * count, 1))
         else:
             pf, V = out
-        check(self.ctx.lib.bpp_circuit_prove_batch(self.ctx.h, self.gens.h, c.h, count, _buf(vb), _buf(ab),
-                                                   _buf(gb) if gb is not None else None,
-                                                   _buf(seeds32) if seeds32 is not None else None,
-                                                   _buf(self.label), len(self.label), pf, V),
-              "bpp_circuit_prove_batch", self.ctx.h)
+        tail = (_buf(gb) if gb is not None else None, _buf(seeds32) if seeds32 is not None else None,
+                _buf(self.label), len(self.label), pf, V)
+        if pub is not None:
+            check(self.ctx.lib.bpp_circuit_prove_batch_pub(self.ctx.h, self.gens.h, c.h, count, _buf(vb), _buf(ab),
+                                                           self._pub(pub, count), *tail),
+                  "bpp_circuit_prove_batch_pub", self.ctx.h)
+        else:
+            check(self.ctx.lib.bpp_circuit_prove_batch(self.ctx.h, self.gens.h, c.h, count, _buf(vb), _buf(ab), *tail),
+                  "bpp_circuit_prove_batch", self.ctx.h)
         praw, vraw = pf.raw[:self.proof_len * count], V.raw[:32 * self.m * count]
         if raw:
             return praw, vraw
         return ([praw[i * self.proof_len:(i + 1) * self.proof_len] for i in range(count)],
                 [vraw[i * 32 * self.m:(i + 1) * 32 * self.m] for i in range(count)])
 
-    def verify(self, proof: bytes, V) -> bool:
+    def verify(self, proof: bytes, V, pub=None) -> bool:
+        """pub: this proof's n_pub public inputs (bpp_circuit_verify_pub)."""
         vb = _join(V, 32, "V")
-        rc = self.ctx.lib.bpp_circuit_verify(self.ctx.h, self.gens.h, self.circuit.h, _buf(self.label),
-                                             len(self.label), _buf(proof), len(proof), _buf(vb))
+        args = (self.ctx.h, self.gens.h, self.circuit.h, _buf(self.label), len(self.label), _buf(proof), len(proof),
+                _buf(vb))
+        if pub is not None:
+            rc = self.ctx.lib.bpp_circuit_verify_pub(*args, self._pub([pub], 1))
+        else:
+            rc = self.ctx.lib.bpp_circuit_verify(*args)
         if rc == 6:
             return False
         check(rc, "bpp_circuit_verify", self.ctx.h)
@@ -900,20 +931,27 @@ class CircuitProver:
 
     _batch_buffers = PermProver._batch_buffers
 
-    def verify_batch(self, proofs, Vs) -> bool:
+    def verify_batch(self, proofs, Vs, pub=None) -> bool:
         pb, vb, count = self._batch_buffers(proofs, Vs)
-        rc = self.ctx.lib.bpp_circuit_verify_batch(self.ctx.h, self.gens.h, self.circuit.h, count, _buf(self.label),
-                                                   len(self.label), _buf(pb), _buf(vb))
+        args = (self.ctx.h, self.gens.h, self.circuit.h, count, _buf(self.label), len(self.label), _buf(pb), _buf(vb))
+        if pub is not None:
+            rc = self.ctx.lib.bpp_circuit_verify_batch_pub(*args, self._pub(pub, count))
+        else:
+            rc = self.ctx.lib.bpp_circuit_verify_batch(*args)
         if rc == 6:
             return False
         check(rc, "bpp_circuit_verify_batch", self.ctx.h)
         return True
 
-    def verify_batch_each(self, proofs, Vs) -> "list[bool]":
+    def verify_batch_each(self, proofs, Vs, pub=None) -> "list[bool]":
         pb, vb, count = self._batch_buffers(proofs, Vs)
         ok = C.create_string_buffer(max(count, 1))
-        rc = self.ctx.lib.bpp_circuit_verify_batch_each(self.ctx.h, self.gens.h, self.circuit.h, count,
-                                                        _buf(self.label), len(self.label), _buf(pb), _buf(vb), ok)
+        args = (self.ctx.h, self.gens.h, self.circuit.h, count, _buf(self.label), len(self.label), _buf(pb), _buf(vb))
+        if pub is not None:
+            rc = self.ctx.lib.bpp_circuit_verify_batch_each_pub(*args, self._pub(pub, count), ok)
+        else:
+            rc = self.ctx.lib.bpp_circuit_verify_batch_each(self.ctx.h, self.gens.h, self.circuit.h, count,
+                                                            _buf(self.label), len(self.label), _buf(pb), _buf(vb), ok)
         if rc != 6:
             check(rc, "bpp_circuit_verify_batch_each", self.ctx.h)
         return [b != 0 for b in ok.raw[:count]]

@@ -110,6 +110,13 @@ SIGNATURES = {
     "bpp_circuit_verify": (i32, [vp, vp, vp, vp, sz, vp, sz, vp]),
     "bpp_circuit_verify_batch": (i32, [vp, vp, vp, sz, vp, sz, vp, vp]),
     "bpp_circuit_verify_batch_each": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, vp]),
+    "bpp_circuit_create_pub": (i32, [vp, u32, C.POINTER(vp)]),
+    "bpp_circuit_n_pub": (u32, [vp]),
+    "bpp_circuit_eval_pub": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u32)]),
+    "bpp_circuit_prove_batch_pub": (i32, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+    "bpp_circuit_verify_pub": (i32, [vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+    "bpp_circuit_verify_batch_pub": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, vp]),
+    "bpp_circuit_verify_batch_each_pub": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]),
     "bpp_perm_verify_begin": (i32, [u32, sz, vp, sz, vp, vp, vp, C.POINTER(vp)]),
     "bpp_perm_verify_begin_dev": (i32, [vp, u32, sz, vp, sz, vp, vp, vp, C.POINTER(vp)]),
     "bpp_perm_verify_terms": (i32, [vp, C.POINTER(sz)]),

@@ -1,5 +1,5 @@
 """Caller-defined circuits for bpp_circuit_* (include/bpperm.h): a builder that
-writes the description arrays, and four gadgets built on it.  Pure Python: no
+writes the description arrays, and the gadgets built on it.  Pure Python: no
 library call, no GPU.
 
     b = CircuitBuilder()
@@ -8,8 +8,8 @@ library call, no GPU.
     b.assert_zero(o)                   # v is 3 or 7
     desc = b.build()                   # -> CircuitDesc (the arrays of bpp_circuit_desc)
 
-A linear combination (LC) is built from b.input(), b.challenge, b.one, wires
-and integers with +, -, unary - and * by an integer; coefficients are mod l.
+A linear combination (LC) is built from b.input(), b.challenge, b.public()
+(a per-proof public input, bpp_circuit_create_pub), b.one, wires and integers with +, -, unary - and * by an integer; coefficients are mod l.
 A defined side may read wires of EARLIER gates only.  b.free_mul() makes a gate
 whose two sides are fed from the per-proof auxiliary values (its two aux
 indices are 2t, 2t + 1 for the t-th free gate, left then right).
@@ -22,7 +22,7 @@ from typing import Callable, Sequence
 L = 2**252 + 27742317777372353535851937790883648493
 SIDE_LC = 0xFFFFFFFF
 
-_ONE, _V, _X, _W = 0, 1, 2, 3  # variable kinds, in id order
+_ONE, _V, _X, _U, _W = 0, 1, 2, 3, 4  # variable kinds, in id order (_U: public inputs)
 
 
 class LC:
@@ -81,6 +81,8 @@ class CircuitDesc:
     lc_coef: list
     # the gadget's hint function: v (m_in ints) -> aux (n_aux ints); None when n_aux = 0
     aux_of: "Callable[[Sequence[int]], list] | None" = field(default=None, compare=False)
+    # public inputs u_0..u_{n_pub-1} (bpp_circuit_create_pub's argument, not an array of bpp_circuit_desc)
+    n_pub: int = 0
 
     def coef_bytes(self) -> bytes:
         return b"".join(self.lc_coef)
@@ -89,6 +91,7 @@ class CircuitDesc:
 class CircuitBuilder:
     def __init__(self):
         self.m_in = 0
+        self.n_pub = 0
         self.n_aux = 0
         self.sides = []    # per gate: [left, right], each an LC (defined) or an aux index (free)
         self.asserts = []
@@ -101,6 +104,15 @@ class CircuitBuilder:
 
     def inputs(self, n: int) -> list:
         return [self.input() for _ in range(n)]
+
+    def public(self) -> LC:
+        """The next public input u_i: per proof, given to prover and verifier,
+        never committed."""
+        self.n_pub += 1
+        return LC({(_U, self.n_pub - 1, 0): 1})
+
+    def publics(self, n: int) -> list:
+        return [self.public() for _ in range(n)]
 
     def _wires(self, g: int):
         return tuple(LC({(_W, g, s): 1}) for s in range(3))
@@ -126,13 +138,13 @@ class CircuitBuilder:
         self.asserts.append(LC.of(lc))
 
     def build(self, aux_of=None) -> CircuitDesc:
-        m_in, n = self.m_in, len(self.sides)
+        m_in, n, n_pub = self.m_in, len(self.sides), self.n_pub
         if not m_in or not n:
             raise ValueError("a circuit needs an input and a gate")
 
         def var_id(key):
             kind, i, s = key
-            return {_ONE: 0, _V: 1 + i, _X: 1 + m_in, _W: 2 + m_in + 3 * i + s}[kind]
+            return {_ONE: 0, _V: 1 + i, _X: 1 + m_in, _U: 2 + m_in + i, _W: 2 + m_in + n_pub + 3 * i + s}[kind]
 
         side_aux, lc_off, lc_var, lc_coef = [], [0], [], []
 
@@ -152,7 +164,7 @@ class CircuitBuilder:
                     lc_off.append(len(lc_var))
         for a in self.asserts:
             emit(a)
-        return CircuitDesc(m_in, n, self.n_aux, len(self.asserts), side_aux, lc_off, lc_var, lc_coef, aux_of)
+        return CircuitDesc(m_in, n, self.n_aux, len(self.asserts), side_aux, lc_off, lc_var, lc_coef, aux_of, n_pub)
 
 
 # --------------------------------------------------------------------- gadgets
@@ -234,6 +246,70 @@ def same_multiset(k: int) -> CircuitDesc:
         o = b.mul(v[base] - x, v[base + 1] - x)[2]
         for i in range(2, k):
             o = b.mul(o, v[base + i] - x)[2]
+        ends.append(o)
+    b.assert_zero(ends[0] - ends[1])
+    return b.build()
+
+
+# ------------------------------------------------- gadgets over public inputs
+
+def opens_to() -> CircuitDesc:
+    """V_0 opens to the public value u_0: one gate (v_0 - u_0) * 1 whose output
+    is asserted 0.  The prover shows a commitment's value without giving up its
+    blinding."""
+    b = CircuitBuilder()
+    v, u = b.input(), b.public()
+    b.assert_zero(b.mul(v - u, 1)[2])
+    return b.build()
+
+
+def member_of_public(n: int) -> CircuitDesc:
+    """v_0 is one of the n public values of this proof: prod_{i<n} (v_0 - u_i) =
+    0, n - 1 gates (one gate for n = 1 or 2).  member_of with the set given per
+    proof: one circuit and one digest for every trick."""
+    if n < 1:
+        raise ValueError("member_of_public: an empty set")
+    b = CircuitBuilder()
+    v = b.input()
+    u = b.publics(n)
+    o = b.mul(v - u[0], v - u[1] if n > 1 else 1)[2]
+    for a in u[2:]:
+        o = b.mul(o, v - a)[2]
+    b.assert_zero(o)
+    return b.build()
+
+
+def sum_equals(k: int) -> CircuitDesc:
+    """v_0 + .. + v_{k-1} = u_0, the announced total.  The statement is one
+    assert; the one gate v_0 * 1 is there because a circuit has a gate."""
+    if k < 1:
+        raise ValueError("k >= 1")
+    b = CircuitBuilder()
+    v = b.inputs(k)
+    u = b.public()
+    b.mul(v[0], 1)
+    total = LC()
+    for x in v:
+        total = total + x
+    b.assert_zero(total - u)
+    return b.build()
+
+
+def shuffle_of_public(k: int) -> CircuitDesc:
+    """V_0..V_{k-1} commit to a permutation of this proof's public deck
+    u_0..u_{k-1}: a chain prod (v_j - x), a chain prod (u_j - x), and an assert
+    on the difference of their ends.  2k - 2 gates, m_in = k, n_pub = k."""
+    if k < 2:
+        raise ValueError("k >= 2")
+    b = CircuitBuilder()
+    v = b.inputs(k)
+    u = b.publics(k)
+    x = b.challenge
+    ends = []
+    for w in (v, u):
+        o = b.mul(w[0] - x, w[1] - x)[2]
+        for i in range(2, k):
+            o = b.mul(o, w[i] - x)[2]
         ends.append(o)
     b.assert_zero(ends[0] - ends[1])
     return b.build()

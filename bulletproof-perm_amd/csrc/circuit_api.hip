@@ -1,7 +1,8 @@
 // Caller-defined circuits: the C ABI (bpp_circuit_*, include/bpperm.h) --
 // argument checks, bpp_guard and marshalling.  The compile and the host
 // witness are host/circuit.cpp; the prover is perm_prove.hip with the circuit
-// form of ShuffleIn, the verifier perm_verify.hip unchanged.
+// form of ShuffleIn, the verifier perm_verify.hip; the _pub entry points carry
+// each proof's public inputs to both.
 #include <string>
 
 #include "host/circuit.h"
@@ -17,14 +18,71 @@ struct bpp_circuit {
   perm::Circuit C;  // (C.program: the compiled program)
 };
 
+namespace {
+
+// "every public scalar of the call is canonical", and a circuit with public
+// inputs was given them: what the _pub entry points check before any device
+// work (bad: the first proof with a scalar >= l)
+int pub_check(const bpp_circuit* c, size_t count, const uint8_t* pub, size_t* bad) {
+  const uint32_t n_pub = c->C.n_pub;
+  if (!n_pub || !count) return BPP_OK;
+  if (!pub) return BPP_ERR_ARG;
+  std::vector<uint8_t> nc(count, 0);
+  par::for_each(count, [&](size_t p) {
+    Sc t;
+    for (uint32_t i = 0; i < n_pub; ++i)
+      if (!hsc::from_canonical(t, pub + (p * (size_t)n_pub + i) * 32)) nc[p] = 1;
+  });
+  for (size_t p = 0; p < count; ++p)
+    if (nc[p]) {
+      *bad = p;
+      return BPP_ERR_NONCANONICAL;
+    }
+  return BPP_OK;
+}
+
+// the entry points without `pub` take circuits without public inputs only
+int no_pub(bpp_ctx* ctx, const bpp_circuit* c) {
+  if (!c || !c->C.n_pub) return BPP_OK;
+  if (ctx) ctx->err = "the circuit has public inputs: use the _pub entry point";
+  return BPP_ERR_ARG;
+}
+
+int circuit_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* aux, const uint8_t* pub, const uint8_t x[32],
+                 uint8_t* aL, uint8_t* aR, uint8_t* aO, uint32_t* bad_assert) {
+  return bpp_guard(nullptr, [&]() -> int {
+    if (!c || !v || !x || !aL || !aR || !aO || !bad_assert) return BPP_ERR_ARG;
+    const circuit::Program& P = *c->C.program;
+    if ((!aux && P.n_aux) || (!pub && P.n_pub)) return BPP_ERR_ARG;
+    std::vector<Sc> vs(P.m_in), as(P.n_aux), us(P.n_pub), L, R, O;
+    Sc xs;
+    for (uint32_t j = 0; j < P.m_in; ++j)
+      if (!hsc::from_canonical(vs[j], v + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
+    for (uint32_t j = 0; j < P.n_aux; ++j)
+      if (!hsc::from_canonical(as[j], aux + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
+    for (uint32_t j = 0; j < P.n_pub; ++j)
+      if (!hsc::from_canonical(us[j], pub + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
+    if (!hsc::from_canonical(xs, x)) return BPP_ERR_NONCANONICAL;
+    circuit::eval(P, c->C.n_p, vs.data(), as.data(), xs, L, R, O, bad_assert, us.data());
+    memcpy(aL, L.data(), 32 * (size_t)c->C.n_p);  // (canonical Sc == its 32 bytes)
+    memcpy(aR, R.data(), 32 * (size_t)c->C.n_p);
+    memcpy(aO, O.data(), 32 * (size_t)c->C.n_p);
+    for (auto* s : {&vs, &as, &L, &R, &O}) std::fill(s->begin(), s->end(), hsc::zero());
+    return BPP_OK;
+  });
+}
+
+}  // namespace
+
 extern "C" {
 
-int bpp_circuit_create(const bpp_circuit_desc* desc, bpp_circuit** out) {
+int bpp_circuit_create_pub(const bpp_circuit_desc* desc, uint32_t n_pub, bpp_circuit** out) {
   return bpp_guard(nullptr, [&]() -> int {
     if (!desc || !out) return BPP_ERR_ARG;
     *out = nullptr;
-    const circuit::Desc d = {desc->m_in,   desc->n_gates, desc->n_aux,  desc->n_asserts,
-                             desc->side_aux, desc->lc_off,  desc->lc_var, desc->lc_coef};
+    circuit::Desc d = {desc->m_in,   desc->n_gates, desc->n_aux,  desc->n_asserts,
+                       desc->side_aux, desc->lc_off,  desc->lc_var, desc->lc_coef};
+    d.n_pub = n_pub;
     std::unique_ptr<bpp_circuit> c(new bpp_circuit());
     std::string err;
     BPP_TRY(circuit::compile(d, c->C, err));
@@ -33,7 +91,13 @@ int bpp_circuit_create(const bpp_circuit_desc* desc, bpp_circuit** out) {
   });
 }
 
+int bpp_circuit_create(const bpp_circuit_desc* desc, bpp_circuit** out) {
+  return bpp_circuit_create_pub(desc, 0, out);
+}
+
 void bpp_circuit_destroy(bpp_circuit* c) { delete c; }
+
+uint32_t bpp_circuit_n_pub(const bpp_circuit* c) { return c ? c->C.n_pub : 0; }
 
 int bpp_circuit_info(const bpp_circuit* c, uint32_t* n_p, uint32_t* Q, uint32_t* m, uint8_t digest[32]) {
   if (!c) return BPP_ERR_ARG;
@@ -48,16 +112,16 @@ size_t bpp_circuit_proof_len(const bpp_circuit* c) { return c ? perm::proof_len(
 
 int bpp_circuit_matrix(const bpp_circuit* c, uint32_t which, uint32_t* q, uint32_t* col, uint8_t* val, size_t* count) {
   return bpp_guard(nullptr, [&]() -> int {
-    if (!c || !count || which > 4) return BPP_ERR_ARG;
-    const std::vector<perm::Entry>* const W[4] = {&c->C.WL, &c->C.WR, &c->C.WO, &c->C.WV};
-    const size_t cap = *count, n = which < 4 ? W[which]->size() : c->C.c.size();
+    if (!c || !count || which > 5) return BPP_ERR_ARG;
+    const std::vector<perm::Entry>* const W[6] = {&c->C.WL, &c->C.WR, &c->C.WO, &c->C.WV, nullptr, &c->C.WU};
+    const size_t cap = *count, n = which != 4 ? W[which]->size() : c->C.c.size();
     *count = n;
     if (cap < n) return BPP_ERR_LEN;
     if (n && (!q || !col || !val)) return BPP_ERR_ARG;
     for (size_t i = 0; i < n; ++i) {
-      q[i] = which < 4 ? (*W[which])[i].q : (uint32_t)i;
-      col[i] = which < 4 ? (*W[which])[i].col : 0;
-      hsc::to_bytes(val + 32 * i, which < 4 ? (*W[which])[i].val : c->C.c[i]);
+      q[i] = which != 4 ? (*W[which])[i].q : (uint32_t)i;
+      col[i] = which != 4 ? (*W[which])[i].col : 0;
+      hsc::to_bytes(val + 32 * i, which != 4 ? (*W[which])[i].val : c->C.c[i]);
     }
     return BPP_OK;
   });
@@ -65,33 +129,23 @@ int bpp_circuit_matrix(const bpp_circuit* c, uint32_t which, uint32_t* q, uint32
 
 int bpp_circuit_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* aux, const uint8_t x[32], uint8_t* aL,
                      uint8_t* aR, uint8_t* aO, uint32_t* bad_assert) {
-  return bpp_guard(nullptr, [&]() -> int {
-    if (!c || !v || !x || !aL || !aR || !aO || !bad_assert) return BPP_ERR_ARG;
-    const circuit::Program& P = *c->C.program;
-    if (!aux && P.n_aux) return BPP_ERR_ARG;
-    std::vector<Sc> vs(P.m_in), as(P.n_aux), L, R, O;
-    Sc xs;
-    for (uint32_t j = 0; j < P.m_in; ++j)
-      if (!hsc::from_canonical(vs[j], v + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
-    for (uint32_t j = 0; j < P.n_aux; ++j)
-      if (!hsc::from_canonical(as[j], aux + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
-    if (!hsc::from_canonical(xs, x)) return BPP_ERR_NONCANONICAL;
-    circuit::eval(P, c->C.n_p, vs.data(), as.data(), xs, L, R, O, bad_assert);
-    memcpy(aL, L.data(), 32 * (size_t)c->C.n_p);  // (canonical Sc == its 32 bytes)
-    memcpy(aR, R.data(), 32 * (size_t)c->C.n_p);
-    memcpy(aO, O.data(), 32 * (size_t)c->C.n_p);
-    for (auto* s : {&vs, &as, &L, &R, &O}) std::fill(s->begin(), s->end(), hsc::zero());
-    return BPP_OK;
-  });
+  if (c && c->C.n_pub) return BPP_ERR_ARG;
+  return circuit_eval(c, v, aux, nullptr, x, aL, aR, aO, bad_assert);
 }
 
-int bpp_circuit_prove_batch(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count, const uint8_t* v,
-                            const uint8_t* aux, const uint8_t* gammas, const uint8_t* seeds32, const uint8_t* label,
-                            size_t llen, uint8_t* proofs_out, uint8_t* V_out) {
+int bpp_circuit_eval_pub(const bpp_circuit* c, const uint8_t* v, const uint8_t* aux, const uint8_t* pub,
+                         const uint8_t x[32], uint8_t* aL, uint8_t* aR, uint8_t* aO, uint32_t* bad_assert) {
+  return circuit_eval(c, v, aux, pub, x, aL, aR, aO, bad_assert);
+}
+
+int bpp_circuit_prove_batch_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count, const uint8_t* v,
+                                const uint8_t* aux, const uint8_t* pub, const uint8_t* gammas, const uint8_t* seeds32,
+                                const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out) {
   return bpp_guard(ctx, [&]() -> int {
     if (!c || (!label && llen)) return BPP_ERR_ARG;
     const uint32_t m_in = c->C.nv, n_aux = c->C.program->n_aux;
     if ((!v || (!aux && n_aux) || !proofs_out || !V_out) && count) return BPP_ERR_ARG;
+    if (!pub && c->C.n_pub && count) return BPP_ERR_ARG;
     // every scalar of the witness is checked before any device work and
     // before any output byte is written (it needs neither the context nor
     // the generators, whose null checks follow)
@@ -112,48 +166,90 @@ int bpp_circuit_prove_batch(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* 
         if (ctx) ctx->err = "circuit proof " + std::to_string(p) + ": non-canonical value, auxiliary value or blinding";
         return bad[p];
       }
+    {
+      size_t p = 0;
+      const int rc = pub_check(c, count, pub, &p);
+      if (rc == BPP_ERR_NONCANONICAL && ctx) ctx->err = "circuit proof " + std::to_string(p) + ": non-canonical public input";
+      BPP_TRY(rc);
+    }
     if (!ctx || !G) return BPP_ERR_ARG;
     if (!count) return BPP_OK;
     ShuffleIn sh = {nullptr, nullptr, gammas};
     sh.v = v;
     sh.aux = aux;
+    sh.pub = c->C.n_pub ? pub : nullptr;
     return prove_batch_entropy(ctx, G, c->C, count, seeds32, label, llen, proofs_out, V_out, &sh);
   });
 }
 
-int bpp_circuit_verify(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, const uint8_t* label, size_t llen,
-                       const uint8_t* proof, size_t proof_len, const uint8_t* V) {
+int bpp_circuit_prove_batch(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count, const uint8_t* v,
+                            const uint8_t* aux, const uint8_t* gammas, const uint8_t* seeds32, const uint8_t* label,
+                            size_t llen, uint8_t* proofs_out, uint8_t* V_out) {
+  BPP_TRY(no_pub(ctx, c));
+  return bpp_circuit_prove_batch_pub(ctx, G, c, count, v, aux, nullptr, gammas, seeds32, label, llen, proofs_out,
+                                     V_out);
+}
+
+int bpp_circuit_verify_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, const uint8_t* label, size_t llen,
+                           const uint8_t* proof, size_t proof_len, const uint8_t* V, const uint8_t* pub) {
   return bpp_guard(ctx, [&]() -> int {
     if (!ctx || !G || !c || !proof || !V || (!label && llen)) return BPP_ERR_ARG;
+    size_t bad = 0;
+    BPP_TRY(pub_check(c, 1, pub, &bad));
     if (proof_len != perm::proof_len(c->C)) return BPP_ERR_VERIFY;
     BPP_HIP(hipSetDevice(ctx->device));
-    return verify_batch(ctx, G, c->C, label, llen, 1, proof, V);
+    return verify_batch(ctx, G, c->C, label, llen, 1, proof, V, pub);
   });
 }
 
-int bpp_circuit_verify_batch(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count, const uint8_t* label,
-                             size_t llen, const uint8_t* proofs, const uint8_t* V) {
+int bpp_circuit_verify_batch_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count,
+                                 const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
+                                 const uint8_t* pub) {
   return bpp_guard(ctx, [&]() -> int {
     if (!ctx || !G || !c || ((!proofs || !V) && count) || (!label && llen)) return BPP_ERR_ARG;
     if (!count) return BPP_OK;
+    size_t bad = 0;
+    BPP_TRY(pub_check(c, count, pub, &bad));
     BPP_HIP(hipSetDevice(ctx->device));
-    return verify_batch(ctx, G, c->C, label, llen, count, proofs, V);
+    return verify_batch(ctx, G, c->C, label, llen, count, proofs, V, pub);
   });
 }
 
-int bpp_circuit_verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count,
-                                  const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
-                                  uint8_t* ok_out) {
+int bpp_circuit_verify_batch_each_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count,
+                                      const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
+                                      const uint8_t* pub, uint8_t* ok_out) {
   // (no pass is ever left behind by a call that fails)
   if (ok_out && count) memset(ok_out, 0, count);
   return bpp_guard(ctx, [&]() -> int {
     if (!ctx || !G || !c || ((!proofs || !V || !ok_out) && count) || (!label && llen)) return BPP_ERR_ARG;
     if (!count) return BPP_OK;
+    size_t bad = 0;
+    BPP_TRY(pub_check(c, count, pub, &bad));
     BPP_HIP(hipSetDevice(ctx->device));
-    const int rc = verify_batch_each(ctx, G, c->C, label, llen, count, proofs, V, ok_out);
+    const int rc = verify_batch_each(ctx, G, c->C, label, llen, count, proofs, V, ok_out, pub);
     if (rc != BPP_OK && rc != BPP_ERR_VERIFY) memset(ok_out, 0, count);
     return rc;
   });
+}
+
+int bpp_circuit_verify(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, const uint8_t* label, size_t llen,
+                       const uint8_t* proof, size_t proof_len, const uint8_t* V) {
+  BPP_TRY(no_pub(ctx, c));
+  return bpp_circuit_verify_pub(ctx, G, c, label, llen, proof, proof_len, V, nullptr);
+}
+
+int bpp_circuit_verify_batch(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count, const uint8_t* label,
+                             size_t llen, const uint8_t* proofs, const uint8_t* V) {
+  BPP_TRY(no_pub(ctx, c));
+  return bpp_circuit_verify_batch_pub(ctx, G, c, count, label, llen, proofs, V, nullptr);
+}
+
+int bpp_circuit_verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count,
+                                  const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
+                                  uint8_t* ok_out) {
+  if (ok_out && count) memset(ok_out, 0, count);
+  BPP_TRY(no_pub(ctx, c));
+  return bpp_circuit_verify_batch_each_pub(ctx, G, c, count, label, llen, proofs, V, nullptr, ok_out);
 }
 
 }  // extern "C"

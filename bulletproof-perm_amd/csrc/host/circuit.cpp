@@ -1,5 +1,6 @@
 // Caller-defined circuits -- see circuit.h.  The checker this must agree with
-// is tests/circuit_ref.py (compile_program / eval_program / circuit_digest).
+// is tests/circuit_ref.py (compile_program / eval_program / circuit_digest),
+// with public inputs tests/circuit_pub_ref.py.
 #include "circuit.h"
 
 #include <algorithm>
@@ -10,9 +11,15 @@ using hsc::Sc;
 
 void digest(const Desc& d, uint8_t out[32]) {
   merlin::Shake256 sh;
-  sh.update((const uint8_t*)"bpperm-circuit", 14);
-  const uint32_t head[4] = {d.m_in, d.n_gates, d.n_aux, d.n_asserts};  // (little-endian host)
-  sh.update((const uint8_t*)head, 16);
+  if (d.n_pub) {
+    sh.update((const uint8_t*)"bpperm-pubcircuit", 17);
+    const uint32_t head[5] = {d.m_in, d.n_pub, d.n_gates, d.n_aux, d.n_asserts};  // (little-endian host)
+    sh.update((const uint8_t*)head, 20);
+  } else {
+    sh.update((const uint8_t*)"bpperm-circuit", 14);
+    const uint32_t head[4] = {d.m_in, d.n_gates, d.n_aux, d.n_asserts};
+    sh.update((const uint8_t*)head, 16);
+  }
   const size_t nlc = 2 * (size_t)d.n_gates + d.n_asserts, T = d.lc_off[nlc];
   sh.update((const uint8_t*)d.side_aux, 8 * (size_t)d.n_gates);
   sh.update((const uint8_t*)d.lc_off, 4 * (nlc + 1));
@@ -29,6 +36,7 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
   if (!d.m_in || !d.n_gates) return fail(ERR_ARG, "no inputs or no gates");
   if (d.m_in > kMaxInputs || d.n_gates > kMaxGates || d.n_asserts > kMaxAsserts || d.n_aux > kMaxAux)
     return fail(ERR_LEN, "more inputs, gates, asserts or auxiliary values than any circuit that fits");
+  if (d.n_pub > kMaxPub) return fail(ERR_LEN, "more than 2^16 public inputs");
   if (!d.side_aux || !d.lc_off) return fail(ERR_ARG, "null side_aux or lc_off");
   const uint32_t m_in = d.m_in, n = d.n_gates, A = d.n_asserts;
   const size_t nlc = 2 * (size_t)n + A;
@@ -37,9 +45,9 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
     if (d.lc_off[i + 1] < d.lc_off[i]) return fail(ERR_ARG, "lc_off decreases at " + std::to_string(i + 1));
   const size_t T = d.lc_off[nlc];
   if (T && (!d.lc_var || !d.lc_coef)) return fail(ERR_ARG, "null lc_var or lc_coef");
-  const uint32_t nvar = 2 + m_in + 3 * n;
+  const uint32_t wbase = 2 + m_in + d.n_pub, nvar = wbase + 3 * n;  // (the first wire id)
   auto P = std::make_shared<Program>();
-  P->m_in = m_in, P->n = n, P->n_aux = d.n_aux, P->A = A;
+  P->m_in = m_in, P->n = n, P->n_aux = d.n_aux, P->A = A, P->n_pub = d.n_pub;
   P->lc_coef.resize(T);
   uint32_t defined = 0;
   std::vector<uint32_t> level(n, 0);
@@ -61,8 +69,8 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
       const uint32_t var = d.lc_var[t];
       if (var >= nvar) return fail(ERR_ARG, where + ": variable id out of range");
       if (t > d.lc_off[i] && var <= d.lc_var[t - 1]) return fail(ERR_ARG, where + ": ids not strictly increasing");
-      if (var >= 2 + m_in && side) {
-        const uint32_t h = (var - 2 - m_in) / 3;
+      if (var >= wbase && side) {
+        const uint32_t h = (var - wbase) / 3;
         if (h >= g) return fail(ERR_ARG, where + ": reads a wire of gate " + std::to_string(h));
         level[g] = std::max(level[g], level[h] + 1);
       }
@@ -80,6 +88,7 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
   C.Q = defined + A + 1;
   C.m = m_in + 1;
   C.nv = m_in;
+  C.n_pub = d.n_pub;
   if (!lds_fits(C.Q, C.n_p, n))
     return fail(ERR_LEN, "Q = " + std::to_string(C.Q) + ", n = " + std::to_string(n) + " beyond the kernels' LDS");
   P->side_aux.assign(d.side_aux, d.side_aux + 2 * (size_t)n);
@@ -99,8 +108,10 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
         C.c[q] = is_assert ? na : a;
       else if (var <= 1 + m_in)
         C.WV.push_back({q, var - 1, is_assert ? na : a});
+      else if (var < wbase)
+        C.WU.push_back({q, var - 2 - m_in, is_assert ? na : a});
       else
-        Wire[(var - 2 - m_in) % 3]->push_back({q, (var - 2 - m_in) / 3, is_assert ? a : na});
+        Wire[(var - wbase) % 3]->push_back({q, (var - wbase) / 3, is_assert ? a : na});
     }
   };
   uint32_t q = 0;
@@ -112,7 +123,7 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
       }
   for (uint32_t a = 0; a < A; ++a) emit(q++, 2 * (size_t)n + a, true);
   C.WV.push_back({q, m_in, hsc::one()});
-  for (auto* W : {&C.WL, &C.WR, &C.WO, &C.WV})
+  for (auto* W : {&C.WL, &C.WR, &C.WO, &C.WV, &C.WU})
     for (perm::Entry& e : *W) e.valR = hsc::to_mont(e.val);
 
   // the level schedule and the device image
@@ -132,7 +143,7 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
   P->dev_lc_wire = (uint32_t)dev.size();
   for (size_t i = 0; i < nlc; ++i) {
     uint32_t t = P->lc_off[i];
-    while (t < P->lc_off[i + 1] && P->lc_var[t] < 2 + m_in) ++t;
+    while (t < P->lc_off[i + 1] && P->lc_var[t] < wbase) ++t;
     dev.push_back(t);
   }
   P->dev_level_off = (uint32_t)dev.size();
@@ -161,8 +172,8 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
 }
 
 void eval(const Program& P, uint32_t n_p, const Sc* v, const Sc* aux, const Sc& x, std::vector<Sc>& aL,
-          std::vector<Sc>& aR, std::vector<Sc>& aO, uint32_t* bad_assert) {
-  const uint32_t m_in = P.m_in, n = P.n;
+          std::vector<Sc>& aR, std::vector<Sc>& aO, uint32_t* bad_assert, const Sc* pub) {
+  const uint32_t m_in = P.m_in, n = P.n, wbase = 2 + m_in + P.n_pub;
   aL.assign(n_p, hsc::zero());
   aR.assign(n_p, hsc::zero());
   aO.assign(n_p, hsc::zero());
@@ -171,8 +182,11 @@ void eval(const Program& P, uint32_t n_p, const Sc* v, const Sc* aux, const Sc& 
     Sc acc = hsc::zero();
     for (size_t t = P.lc_off[i]; t < P.lc_off[i + 1]; ++t) {
       const uint32_t var = P.lc_var[t];
-      const Sc val = var == 0 ? hsc::one() : var <= m_in ? v[var - 1] : var == 1 + m_in ? x
-                                                         : (*Wire[(var - 2 - m_in) % 3])[(var - 2 - m_in) / 3];
+      const Sc val = var == 0           ? hsc::one()
+                     : var <= m_in      ? v[var - 1]
+                     : var == 1 + m_in  ? x
+                     : var < wbase      ? pub[var - 2 - m_in]
+                                        : (*Wire[(var - wbase) % 3])[(var - wbase) / 3];
       acc = hsc::add(acc, hsc::mul(P.lc_coef[t], val));
     }
     return acc;

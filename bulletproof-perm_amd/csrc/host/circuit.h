@@ -4,18 +4,22 @@
 // Host code only; the C ABI is circuit_api.hip.
 //
 // Variables: committed inputs v_0..v_{m_in-1}; the challenge x (x_perm,
-// squeezed after V_0..V_{m_in-1} and committed as V_{m_in}); the wires l_h,
-// r_h, o_h = l_h r_h of n multiplication gates.  A gate side is DEFINED -- a
-// sparse linear combination over {1, v_j, x, wires of gates h < g} -- or FREE,
-// fed from a per-proof auxiliary value aux_t supplied before x exists.  A
-// assert rows each force a linear combination over any variable to 0.
+// squeezed after V_0..V_{m_in-1} and committed as V_{m_in}); the public inputs
+// u_0..u_{n_pub-1} (per proof, never committed: both sides are given them and
+// the transcript absorbs them before V_0); the wires l_h, r_h, o_h = l_h r_h of
+// n multiplication gates.  A gate side is DEFINED -- a sparse linear
+// combination over {1, v_j, x, u_i, wires of gates h < g} -- or FREE, fed from
+// a per-proof auxiliary value aux_t supplied before x exists.  A assert rows
+// each force a linear combination over any variable to 0.
 //
 // Rows: defined left sides by gate, defined right sides by gate, the asserts,
 // then v_{m_in} = x (c[Q-1] = -x per proof).  Defined side of gate g at row q:
 // W(q, g) = 1 in its own matrix, a wire term a -> -a in the wire's matrix, a
-// v_j / x term -> W_V = a, the constant -> c[q] = a.  Assert row: wire terms
-// +a, v / x terms -a, constant -a.  Q = defined sides + A + 1, m = m_in + 1,
-// nv = m_in, n_p = max(4, next_pow2(n)).
+// v_j / x term -> W_V = a, a u_i term -> W_U = a, the constant -> c[q] = a.
+// Assert row: wire terms +a, v / x terms -a, u_i terms -a, constant -a.  A
+// proof's constant vector is c + W_U u (W_U: Q x n_pub); nothing else of the
+// statement depends on u.  Q = defined sides + A + 1, m = m_in + 1, nv = m_in,
+// n_p = max(4, next_pow2(n)).
 #pragma once
 #include <memory>
 #include <string>
@@ -36,16 +40,20 @@ struct Desc {
   const uint32_t* lc_off;    // [2n + A + 1]
   const uint32_t* lc_var;    // [T]
   const uint8_t* lc_coef;    // [T][32]
+  uint32_t n_pub = 0;        // (bpp_circuit_create_pub's; not a field of bpp_circuit_desc)
 };
 
 // variable ids of lc_var
 inline uint32_t var_one() { return 0; }
 inline uint32_t var_v(uint32_t j) { return 1 + j; }
 inline uint32_t var_x(uint32_t m_in) { return 1 + m_in; }
-inline uint32_t var_wire(uint32_t m_in, uint32_t h, uint32_t lro) { return 2 + m_in + 3 * h + lro; }
+inline uint32_t var_pub(uint32_t m_in, uint32_t i) { return 2 + m_in + i; }
+inline uint32_t var_wire(uint32_t m_in, uint32_t h, uint32_t lro, uint32_t n_pub = 0) {
+  return 2 + m_in + n_pub + 3 * h + lro;
+}
 
 struct Program {
-  uint32_t m_in = 0, n = 0, n_aux = 0, A = 0;
+  uint32_t m_in = 0, n = 0, n_aux = 0, A = 0, n_pub = 0;
   std::vector<uint32_t> side_aux, lc_off, lc_var;
   std::vector<hsc::Sc> lc_coef;
   // gates by dependency level: level = 1 + the highest level among the gates
@@ -54,7 +62,7 @@ struct Program {
   std::vector<uint32_t> level_off, level_gate;
   // what k_witness_program reads, one upload: side_aux [2n], lc_off [2n + A + 1],
   // lc_wire [2n + A] (the first term of each combination that reads a wire: ids
-  // ascend, so the terms over {1, v_j, x} come before it), level_off [levels +
+  // ascend, so the terms over {1, v_j, x, u_i} come before it), level_off [levels +
   // 1], level_gate [n], the T terms' variable ids (| kTermOne: coefficient 1, |
   // kTermNeg: coefficient -1, no multiply), then (from a multiple of 8 words:
   // 32-byte aligned) their Montgomery coefficients [T][8]; word offsets of the
@@ -65,31 +73,33 @@ struct Program {
 };
 
 // SHAKE256("bpperm-circuit" || le32 m_in || le32 n || le32 n_aux || le32 A ||
-// side_aux || lc_off || lc_var || lc_coef)[0..32] over the arrays as given
+// side_aux || lc_off || lc_var || lc_coef)[0..32] over the arrays as given;
+// with n_pub > 0, "bpperm-pubcircuit" || le32 m_in || le32 n_pub || le32 n || ..
 void digest(const Desc& d, uint8_t out[32]);
 
 // Validates and compiles: ERR_ARG for m_in = 0 or n = 0, ids or aux indices
 // out of range, a definition reading a wire of gate h >= g, a nonempty
 // combination on a free side, unsorted or duplicate ids, a zero coefficient, a
 // non-monotone lc_off; ERR_NONCANONICAL for a coefficient >= l; ERR_LEN beyond
-// lds_fits.  C.program is the compiled program.
+// lds_fits or kMaxPub.  C.program is the compiled program.
 int compile(const Desc& d, perm::Circuit& C, std::string& err);
 
 // The host witness: a_L, a_R, a_O (n_p each, padding gates zero) from v
 // [m_in], aux [n_aux] and x; *bad_assert = 1 + the first assert that does not
-// hold, or 0.
+// hold, or 0.  pub: the n_pub public inputs (not read when n_pub = 0).
 void eval(const Program& P, uint32_t n_p, const hsc::Sc* v, const hsc::Sc* aux, const hsc::Sc& x,
-          std::vector<hsc::Sc>& aL, std::vector<hsc::Sc>& aR, std::vector<hsc::Sc>& aO, uint32_t* bad_assert);
+          std::vector<hsc::Sc>& aL, std::vector<hsc::Sc>& aR, std::vector<hsc::Sc>& aO, uint32_t* bad_assert,
+          const hsc::Sc* pub = nullptr);
 
 // k_witness_program's dynamic LDS: its fail word (32 B) and the 3n wire values;
-// staged, also the proof's m_in inputs in Montgomery form and a copy of the
+// staged, also the proof's m_in inputs and n_pub public inputs in Montgomery form and a copy of the
 // program's device image, which turns every level's dependent index and term
 // loads from global-memory round trips into LDS reads.  Staged whenever that
 // fits one workgroup's LDS, the plain form (program and inputs read from
 // global memory) beyond.
 inline size_t witness_program_lds(uint32_t n) { return (size_t)3 * n * 32 + 32; }
 inline size_t witness_program_staged_lds(const Program& P) {
-  return witness_program_lds(P.n) + (size_t)P.m_in * 32 + P.dev.size() * 4;
+  return witness_program_lds(P.n) + ((size_t)P.m_in + P.n_pub) * 32 + P.dev.size() * 4;
 }
 // "every per-proof kernel's workgroup fits its LDS": k_poly_coef and
 // k_verify_scalars (perm.h, the formulas their launches use) and
@@ -98,6 +108,7 @@ inline bool lds_fits(uint32_t Q, uint32_t n_p, uint32_t n) {
   return perm::poly_coef_lds(Q, n_p) <= perm::kLdsMax && perm::verify_scalars_lds(Q, n_p) <= perm::kLdsMax &&
          witness_program_lds(n) <= perm::kLdsMax;
 }
-constexpr uint32_t kMaxInputs = 1u << 20, kMaxGates = 1u << 16, kMaxAsserts = 1u << 16, kMaxAux = 1u << 20;
+constexpr uint32_t kMaxInputs = 1u << 20, kMaxGates = 1u << 16, kMaxAsserts = 1u << 16, kMaxAux = 1u << 20,
+                   kMaxPub = 1u << 16;
 
 }  // namespace circuit

@@ -41,6 +41,11 @@ struct Circuit {
   // witness is evaluated from, and its description's transcript digest
   std::shared_ptr<const circuit::Program> program;
   uint8_t program_digest[32] = {0};
+  // ... with public inputs (bpp_circuit_create_pub): a proof's constant vector
+  // is c + W_U u over its own n_pub public scalars u, which its transcript
+  // absorbs ("pub", 32 bytes each) right after the prefix below
+  uint32_t n_pub = 0;
+  std::vector<Entry> WU;  // (col = the public input's index)
 };
 
 Circuit build(uint32_t k);
@@ -75,6 +80,11 @@ inline const char* statement_label(const Circuit& C) { return C.deck ? "deck" : 
 inline void transcript_prefix(const Circuit& C, merlin::Transcript& tr) {
   tr.arithmetic_domain_sep(C.n_p);
   if (const char* s = statement_label(C)) tr.append(s, C.deck ? C.deck_digest : C.program_digest, 32);
+}
+// ... then one proof's own public inputs (pub: C.n_pub canonical scalars),
+// before V_0 and so before every challenge
+inline void transcript_pub(const Circuit& C, merlin::Transcript& tr, const uint8_t* pub) {
+  for (uint32_t i = 0; i < C.n_pub; ++i) tr.append("pub", pub + 32 * (size_t)i, 32);
 }
 
 // Dynamic LDS of the one-workgroup-per-proof kernels k_poly_coef and

@@ -17,6 +17,7 @@ int ipa_transcript_step_dev(bpp_ctx* ctx, uint32_t P, uint8_t* d_states, const u
 // (50 state words, pos, pos_begin); d_venc [P][nv][32] (nv = Circuit::nv); states_out
 // [P][MERLIN_DEV_STATE_BYTES] (merlin_state_import), xperm_out [P][8] words.
 int prove_v_transcript_dev(bpp_ctx* ctx, uint32_t P, uint32_t nv, const uint32_t* init, const uint32_t* d_venc,
-                           uint8_t* states_out, uint32_t* xperm_out);
+                           uint8_t* states_out, uint32_t* xperm_out, uint32_t n_pub = 0,
+                           const uint32_t* d_pub = nullptr);  // (d_pub [P][n_pub][8]: absorbed as "pub" before V_0)
 void merlin_state_export(const merlin::Transcript& t, uint8_t* out);
 void merlin_state_import(merlin::Transcript& t, const uint8_t* in);

@@ -68,10 +68,13 @@ __global__ void __launch_bounds__(64) k_ipa_transcript_step(uint32_t P, uint8_t*
 // reference's create, circuit_lib.rs:139-186, in sound form).  venc: [P][nv]
 // encodings on the device.  states_out: [P][MERLIN_DEV_STATE_BYTES],
 // xperm_out: [P][8] canonical words (both may be pinned host memory).
+// A circuit with public inputs: append_message("pub", u_i) for the proof's
+// n_pub scalars (pub [P][n_pub][8] words) before V_0, as perm::transcript_pub.
 __global__ void __launch_bounds__(64) k_prove_v_transcript(uint32_t P, uint32_t nv, const uint32_t* __restrict__ init,
                                                            const uint32_t* __restrict__ venc,
                                                            uint8_t* __restrict__ states_out,
-                                                           uint32_t* __restrict__ xperm_out) {
+                                                           uint32_t* __restrict__ xperm_out, uint32_t n_pub,
+                                                           const uint32_t* __restrict__ pub) {
   __shared__ __attribute__((aligned(16))) uint8_t st_lds[64 * LANE_ST_BYTES];
   const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P) return;  // (no LDS or shuffle shared between lanes)
@@ -82,6 +85,12 @@ __global__ void __launch_bounds__(64) k_prove_v_transcript(uint32_t P, uint32_t 
     for (int i = 0; i < 50; ++i) d[i] = init[i];
     s.pos = init[50];
     s.pos_begin = init[51];
+  }
+  for (uint32_t j = 0; j < n_pub; ++j) {
+    const uint32_t* U = pub + ((size_t)p * n_pub + j) * 8;
+    const uint4 a = reinterpret_cast<const uint4*>(U)[0], b = reinterpret_cast<const uint4*>(U)[1];
+    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    s.append32("pub", 3, w);
   }
   const uint32_t* V = venc + (size_t)p * nv * 8;
   for (uint32_t j = 0; j < nv; ++j) {
@@ -99,12 +108,12 @@ __global__ void __launch_bounds__(64) k_prove_v_transcript(uint32_t P, uint32_t 
 }
 
 int prove_v_transcript_dev(bpp_ctx* ctx, uint32_t P, uint32_t nv, const uint32_t* init, const uint32_t* d_venc,
-                           uint8_t* states_out, uint32_t* xperm_out) {
+                           uint8_t* states_out, uint32_t* xperm_out, uint32_t n_pub, const uint32_t* d_pub) {
   if (!P) return BPP_OK;
   {
     ProfScope ps(ctx, "prove_v_transcript");
     hipLaunchKernelGGL(k_prove_v_transcript, dim3((P + 63) / 64), dim3(64), 0, ctx->stream, P, nv, init, d_venc,
-                       states_out, xperm_out);
+                       states_out, xperm_out, n_pub, d_pub);
   }
   return ctx_check_launch(ctx, "k_prove_v_transcript");
 }

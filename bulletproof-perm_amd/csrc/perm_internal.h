@@ -90,14 +90,15 @@ inline void proof_points(const Proof& P, uint8_t* out) {
 
 // A caller-supplied shuffle (bpp_perm_prove_shuffle_batch, bpp_deck_prove_batch):
 // this batch's slices of the caller's arrays, validated by the entry point.
-// The circuit form (bpp_circuit_prove_batch; C.program set): v, aux and gammas,
-// no cards and no perms.
+// The circuit form (bpp_circuit_prove_batch; C.program set): v, aux, gammas and
+// (bpp_circuit_prove_batch_pub) pub, no cards and no perms.
 struct ShuffleIn {
   const uint8_t* cards;   // [P][k] canonical scalars; nullptr with the deck circuit (the deck is the circuit's)
   const uint32_t* perms;  // [P][k], each a bijection on [0, k)
   const uint8_t* gammas;  // nullptr (drawn), or [P][C.nv] canonical scalars
   const uint8_t* v = nullptr;    // [P][m_in] canonical scalars: the committed inputs
   const uint8_t* aux = nullptr;  // [P][n_aux] canonical scalars: the free gate sides' values
+  const uint8_t* pub = nullptr;  // [P][n_pub] canonical scalars: the public inputs (nullptr when n_pub = 0)
   size_t first = 0;              // this slice's first proof in the caller's batch (error messages)
 };
 
@@ -146,6 +147,9 @@ struct bpp_verify_job {
   // that slice); a whole job has rcount = count.  (The sharded path,
   // bpp_perm_verify_partial_sharded, takes one whole job per slice.)
   size_t rfirst = 0, rcount = 0;
+  // a circuit with public inputs: the batch's [count][n_pub][8] words in dctx's
+  // "vj_pub" workspace, read by the replay and by k_verify_scalars_pub
+  const uint32_t* d_pub = nullptr;
 };
 
 namespace perm_impl BPP_HIDDEN {
@@ -167,11 +171,14 @@ int verify_begin(const perm::Circuit& C, const uint8_t* label, size_t llen, size
                  size_t proof_stride, const uint8_t* V, std::unique_ptr<bpp_verify_job>& job);
 int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label, size_t llen, size_t count,
                      const uint8_t* proofs, const uint8_t* V, std::unique_ptr<bpp_verify_job>& job, size_t rfirst = 0,
-                     size_t rcount = SIZE_MAX, bool sync = true, bool each = false);
+                     size_t rcount = SIZE_MAX, bool sync = true, bool each = false, const uint8_t* pub = nullptr);
+// pub: [count][C.n_pub] canonical scalars (checked by the entry point), the
+// proofs' public inputs; not read when C.n_pub = 0
 int verify_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
-                 size_t count, const uint8_t* proofs, const uint8_t* V);
+                 size_t count, const uint8_t* proofs, const uint8_t* V, const uint8_t* pub = nullptr);
 int verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
-                      size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out);
+                      size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out,
+                      const uint8_t* pub = nullptr);
 int verify_partial(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, const uint8_t seed[32], size_t first,
                    uint32_t wb, uint32_t we, h25519::ge* out);
 int verify_partial_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, const uint8_t seed[32], size_t first,

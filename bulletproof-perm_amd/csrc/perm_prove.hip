@@ -145,6 +145,7 @@ struct ProverState {
   std::vector<Sc> vals, aL, aR, aO;
   std::vector<Sc> cards;  // a caller-supplied deck (k > 768) or a program's inputs, kept for the host witness only
   std::vector<Sc> aux;    // a program's auxiliary values, likewise
+  std::vector<Sc> pub;    // a program's public inputs, likewise
   Sc x_perm, w;
   Sc t[7];
 };
@@ -293,6 +294,7 @@ struct ProveBatch {
   uint32_t *d_gamma = nullptr, *d_s = nullptr, *d_pi = nullptr;
   uint32_t *d_v = nullptr, *d_g = nullptr, *d_gx_half = nullptr;
   const uint32_t* d_aux = nullptr;  // a program's uploaded auxiliary values [P][n_aux]
+  const uint32_t* d_pub = nullptr;  // a program's uploaded public inputs [P][n_pub]
   uint32_t *d_l = nullptr, *d_r = nullptr, *d_hf = nullptr;
   MsmPoints pts;
   std::vector<Sc> zwvg = std::vector<Sc>(P);  // <z^Q W_V, gamma> per proof (k_poly_coef)
@@ -343,15 +345,17 @@ int ProveBatch::draws_upload() {
   // (the deck circuit's cards are the call's, public: "pb_deck" below)
   // (a caller-defined circuit: its inputs v in the cards' place, then aux)
   const uint32_t n_aux = C.program ? C.program->n_aux : 0;
-  if (C.program && !(sh && sh->v && (sh->aux || !n_aux))) {
-    ctx->err = "prove_batch: a caller-defined circuit takes the caller's v and aux";
+  const uint32_t n_pub = C.n_pub;
+  if (C.program && !(sh && sh->v && (sh->aux || !n_aux) && (sh->pub || !n_pub))) {
+    ctx->err = "prove_batch: a caller-defined circuit takes the caller's v, aux and public inputs";
     return BPP_ERR_ARG;
   }
   const size_t sh_off = (rng_bytes + 31) & ~(size_t)31;
   const size_t cards_bytes = C.program ? (size_t)P * nv * 32 : sh && sh->cards ? (size_t)P * k * 32 : 0;
   const size_t aux_bytes = (size_t)P * n_aux * 32;
   const size_t gam_bytes = sh && sh->gammas ? (size_t)P * nv * 32 : 0;
-  const size_t in_bytes = sh ? sh_off + cards_bytes + aux_bytes + gam_bytes : rng_bytes;
+  const size_t pub_bytes = (size_t)P * n_pub * 32;  // (public: behind the secrets, wiped with them all the same)
+  const size_t in_bytes = sh ? sh_off + cards_bytes + aux_bytes + gam_bytes + pub_bytes : rng_bytes;
   BPP_TRY(ctx_ws(ctx, "pb_rng_in", in_bytes, &dst));
   d_pi = (uint32_t*)((uint8_t*)dst + P * tlen);
   // (one staging region: a second take could recycle the arena under the first;
@@ -382,11 +386,16 @@ int ProveBatch::draws_upload() {
         if (sh->gammas)
           memcpy(stage + sh_off + cards_bytes + aux_bytes + i * 32 * (size_t)nv, sh->gammas + i * 32 * (size_t)nv,
                  32 * (size_t)nv);
+        if (n_pub)
+          memcpy(stage + sh_off + cards_bytes + aux_bytes + gam_bytes + i * 32 * (size_t)n_pub,
+                 sh->pub + i * 32 * (size_t)n_pub, 32 * (size_t)n_pub);
         if (!dev_witness) {  // (canonical Sc == its 32 bytes)
           S[i]->cards.resize(nv);
           memcpy(S[i]->cards.data(), sh->v + i * 32 * (size_t)nv, 32 * (size_t)nv);
           S[i]->aux.resize(n_aux);
           if (n_aux) memcpy(S[i]->aux.data(), sh->aux + i * 32 * (size_t)n_aux, 32 * (size_t)n_aux);
+          S[i]->pub.resize(n_pub);
+          if (n_pub) memcpy(S[i]->pub.data(), sh->pub + i * 32 * (size_t)n_pub, 32 * (size_t)n_pub);
         }
       } else if (sh) {
         S[i]->d.pi.assign(sh->perms + i * k, sh->perms + (i + 1) * k);
@@ -399,6 +408,8 @@ int ProveBatch::draws_upload() {
         }
       }
       perm::transcript_prefix(C, S[i]->tr);
+      // (BPP_PROVE_DEV_V=1 replaces this state with the device's, which absorbs the same)
+      if (n_pub) perm::transcript_pub(C, S[i]->tr, sh->pub + i * 32 * (size_t)n_pub);
       uint64_t tm[7];
       draw_template(sd[j], tm);
       memcpy(stage + i * tlen, tm, tlen);
@@ -416,6 +427,7 @@ int ProveBatch::draws_upload() {
     // caller's blindings over the drawn gamma_0..m_in-1)
     const uint8_t* dsh = (const uint8_t*)dst + sh_off;
     d_aux = (const uint32_t*)(dsh + cards_bytes);
+    d_pub = (const uint32_t*)(dsh + cards_bytes + aux_bytes + gam_bytes);
     BPP_TRY(draws_dev(ctx, C, (uint32_t)P, (const uint64_t*)dst, seeds[0].len, per, d_gamma, d_s));
     BPP_TRY(circuit_inputs_dev(ctx, C, (uint32_t)P, (const uint32_t*)dsh,
                                gam_bytes ? (const uint32_t*)(dsh + cards_bytes + aux_bytes) : nullptr, d_gamma, d_v,
@@ -483,7 +495,8 @@ int ProveBatch::pedersen_V() {
       BPP_TRY(ctx_zc_out(ctx, "pv_states", P * MERLIN_DEV_STATE_BYTES, &hs_));
       BPP_TRY(ctx_zc_out(ctx, "pv_xperm", P * 32, &h_xp));
       h_st = (uint8_t*)hs_;
-      BPP_TRY(prove_v_transcript_dev(ctx, (uint32_t)P, this->nv, h_init, (const uint32_t*)dvenc, h_st, h_xp));
+      BPP_TRY(prove_v_transcript_dev(ctx, (uint32_t)P, this->nv, h_init, (const uint32_t*)dvenc, h_st, h_xp, C.n_pub,
+                                     d_pub));
     }
   }
   std::vector<Enc32>& V = scr.V;
@@ -527,7 +540,7 @@ int ProveBatch::pedersen_Vx_witness() {
   uint32_t* h_fail = nullptr;  // a program's failing assert per proof, written in place (ctx_zc_out)
   if (dev_witness && C.program) {
     BPP_TRY(ctx_zc_out(ctx, "wp_fail_h", P * 4, &h_fail));
-    BPP_TRY(witness_program_dev(ctx, C, (uint32_t)P, d_v, d_aux, d_vh + 8 * P, per, d_s, h_fail));
+    BPP_TRY(witness_program_dev(ctx, C, (uint32_t)P, d_v, d_aux, d_vh + 8 * P, per, d_s, h_fail, d_pub));
   } else if (dev_witness) {
     if (C.deck)
       BPP_TRY(witness_deck_dev(ctx, C, (uint32_t)P, d_v, d_vh + 8 * P, per, d_s));
@@ -548,7 +561,8 @@ int ProveBatch::pedersen_Vx_witness() {
     if (!dev_witness) {
       ProverState& st = *S[p];
       if (C.program)
-        circuit::eval(*C.program, n_p, st.cards.data(), st.aux.data(), st.x_perm, st.aL, st.aR, st.aO, &bad[p]);
+        circuit::eval(*C.program, n_p, st.cards.data(), st.aux.data(), st.x_perm, st.aL, st.aR, st.aO, &bad[p],
+                      st.pub.data());
       else if (C.deck)
         perm::witness_deck(C, st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
       else if (sh)
@@ -753,7 +767,9 @@ namespace perm_impl BPP_HIDDEN {
 // m_in values (k_circuit_inputs), the witness is the program interpreted by
 // k_witness_program or circuit::eval -- an assert that does not hold ends the
 // batch there with BPP_ERR_ARG -- and the transcripts start from the program's
-// digest; the steps after V_{m_in} are the same.
+// digest and, with public inputs (sh->pub), the proof's own public scalars,
+// which k_witness_program reads as one more input kind; the steps after
+// V_{m_in} are the same.
 int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
                 const uint8_t* label, size_t llen, std::vector<Proof>& Ps, const ShuffleIn* sh) {
   const size_t P = seeds.size();
@@ -823,6 +839,7 @@ int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, con
           if (C.program) {
             shs.v = sh->v + b * 32 * (size_t)C.nv;
             shs.aux = sh->aux ? sh->aux + b * 32 * (size_t)C.program->n_aux : nullptr;
+            shs.pub = sh->pub ? sh->pub + b * 32 * (size_t)C.n_pub : nullptr;
           }
           shs.first = sh->first + b;
         }

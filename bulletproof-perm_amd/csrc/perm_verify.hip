@@ -374,9 +374,12 @@ int verify_partial(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, con
 // each (verify_batch_each): the decompression also keeps one flag per proof,
 // behind its verdict word in "vj_dbad" and set by the same memset (all ones;
 // cleared where a point of the proof does not decode).
+// pub (a circuit with public inputs): the proofs' public scalars, uploaded to
+// "vj_pub" beside the proofs and V (by DMA when pinned, else staged with them)
+// for the replay and for k_verify_scalars_pub (J.d_pub).
 int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label, size_t llen, size_t count,
                      const uint8_t* proofs, const uint8_t* V, std::unique_ptr<bpp_verify_job>& job,
-                     size_t rfirst, size_t rcount, bool sync, bool each) {
+                     size_t rfirst, size_t rcount, bool sync, bool each, const uint8_t* pub) {
   job.reset(new bpp_verify_job);
   bpp_verify_job& J = *job;
   if (rcount == SIZE_MAX) rcount = count;
@@ -390,9 +393,11 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
   J.dctx = ctx;
   // (before the generation: a refused call supersedes nothing)
   if (count > (1u << 26) || rfirst > count || rcount > count - rfirst) return BPP_ERR_ARG;
+  if (C.n_pub && !pub && count) return BPP_ERR_ARG;
   J.dgen = ++ctx->vjob_gen;
   if (!count) return BPP_OK;
   const size_t plen = perm::proof_len(C), vbytes = (size_t)C.m * 32, npts = count * J.npt;
+  const size_t pub_bytes = count * (size_t)C.n_pub * 32;
   bpp_ctx* kid = nullptr;
   BPP_TRY(ctx_child(ctx, VJ_CHILD, &kid));
   if (!ctx->vj_ev_dec) BPP_HIP(hipEventCreateWithFlags(&ctx->vj_ev_dec, hipEventDisableTiming));
@@ -402,6 +407,9 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
   BPP_TRY(ctx_ws(ctx, "vj_in", count * (plen + vbytes), &d_in));
   const uint32_t* d_pf = (const uint32_t*)d_in;
   const uint32_t* d_V = (const uint32_t*)((uint8_t*)d_in + count * plen);
+  void* d_pub = nullptr;
+  if (pub_bytes) BPP_TRY(ctx_ws(ctx, "vj_pub", pub_bytes, &d_pub));
+  J.d_pub = (const uint32_t*)d_pub;
   // (+1: the pad record of the replay's groups past the batch)
   BPP_TRY(ctx_ws(ctx, "vj_rec", (count + 1) * vrec_n(C) * 32, &d_rec));
   BPP_TRY(ctx_ws(ctx, "vj_x", npts * MSM_NIELS_WORDS * 4, &d_x));
@@ -432,9 +440,19 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
       // the caller registered itself) go up by DMA from where they are;
       // pageable buffers are staged through the pinned arena first (the host
       // copy then paces the upload)
-      const bool direct = host_is_pinned(proofs, count * plen) && host_is_pinned(V, count * vbytes);
+      const bool direct = host_is_pinned(proofs, count * plen) && host_is_pinned(V, count * vbytes) &&
+                          (!pub_bytes || host_is_pinned(pub, pub_bytes));
       uint8_t* stg = nullptr;
-      if (!direct) BPP_TRY(ctx_h2d_stage(ctx, count * (plen + vbytes), &stg));
+      if (!direct) BPP_TRY(ctx_h2d_stage(ctx, count * (plen + vbytes) + pub_bytes, &stg));
+      if (pub_bytes) {  // (whole, first: the replay reads all of it, the decompression none)
+        if (direct) {
+          BPP_HIP(hipMemcpyAsync(d_pub, pub, pub_bytes, hipMemcpyHostToDevice, ctx->stream));
+        } else {
+          uint8_t* ps = stg + count * (plen + vbytes);
+          ctx_stage_copy(ps, pub, pub_bytes);
+          BPP_TRY(ctx_h2d_staged(ctx, d_pub, ps, pub_bytes));
+        }
+      }
       // (The first nchunk - 1 chunks' transcripts started on a side stream
       // once their bytes were up, beside the last chunk's upload, did not pay
       // when measured behind a switch since removed: a replay launch is a
@@ -478,7 +496,8 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
   BPP_TRY(ctx_zc_out(ctx, "vj_r", rcount * 32, &h_r));
   BPP_TRY(ctx_zc_out(ctx, "vj_bad", rcount * 4, &h_bad));
   BPP_TRY(verify_replay_dev(ctx, C, (uint32_t)rcount, h_init, d_pf + rfirst * (plen / 4),
-                            d_V + rfirst * (vbytes / 4), (uint32_t*)d_rec, h_r, h_bad));
+                            d_V + rfirst * (vbytes / 4), (uint32_t*)d_rec, h_r, h_bad,
+                            J.d_pub ? J.d_pub + rfirst * (size_t)C.n_pub * 8 : nullptr));
   if (!sync) {
     J.bad_h = h_bad;
     J.rs.clear();
@@ -607,7 +626,7 @@ int verify_partial_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J,
     uint32_t* h_seed = nullptr;
     BPP_TRY(ctx_zc_in(ctx, "vj_seed", seed, 32, &h_seed));
     BPP_TRY(verify_scalars_dev_rec(ctx, J.C, (uint32_t)count, (const uint32_t*)d_rec, h_seed, first,
-                                   (uint32_t*)d_sv));
+                                   (uint32_t*)d_sv, J.d_pub));
   }
   uint64_t* h_dbad = nullptr;  // the decompression's verdict, copied behind the MSM
   BPP_TRY(ctx_zc_out(ctx, "vj_dbad_h", 8, (uint32_t**)&h_dbad));
@@ -623,14 +642,14 @@ int verify_partial_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J,
 // with per-proof weights derived from every proof's r challenge; the
 // transcripts are replayed on the device.
 int verify_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
-                 size_t count, const uint8_t* proofs, const uint8_t* V) {
+                 size_t count, const uint8_t* proofs, const uint8_t* V, const uint8_t* pub) {
   uint8_t seed[32];  // the verifier's own randomness for the batch weights
   if (!perm::verify_seed(seed)) {
     ctx->err = "getrandom failed";
     return BPP_ERR_DEVICE;
   }
   std::unique_ptr<bpp_verify_job> job;
-  BPP_TRY(verify_begin_dev(ctx, C, label, llen, count, proofs, V, job, 0, SIZE_MAX, false));
+  BPP_TRY(verify_begin_dev(ctx, C, label, llen, count, proofs, V, job, 0, SIZE_MAX, false, false, pub));
   const uint32_t c = msm_choose_c((double)verify_terms(*job));
   h25519::ge res;
   BPP_TRY(verify_partial_dev(ctx, G, *job, seed, 0, 0, (254 + c - 1) / c, &res));
@@ -697,14 +716,14 @@ static int verify_each_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job
 // merged MSM; only when that does not pass, each proof's own MSM
 // (verify_each_dev).  ok_out [count]: 1 = proof p verifies alone.
 int verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
-                      size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out) {
+                      size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out, const uint8_t* pub) {
   uint8_t seed[32];
   if (!perm::verify_seed(seed)) {
     ctx->err = "getrandom failed";
     return BPP_ERR_DEVICE;
   }
   std::unique_ptr<bpp_verify_job> job;
-  BPP_TRY(verify_begin_dev(ctx, C, label, llen, count, proofs, V, job, 0, SIZE_MAX, false, true));
+  BPP_TRY(verify_begin_dev(ctx, C, label, llen, count, proofs, V, job, 0, SIZE_MAX, false, true, pub));
   const uint32_t c = msm_choose_c((double)verify_terms(*job));
   h25519::ge res;
   // (BPP_ERR_VERIFY: a replay verdict or an undecodable point, found after

@@ -87,6 +87,7 @@ int circuit_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const u
 // host memory, valid after the next ctx_sync) 1 + the first assert that does
 // not hold, or 0.
 int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
-                        const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail);
+                        const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail,
+                        const uint32_t* d_pub = nullptr);  // (d_pub [P][n_pub] canonical: the public inputs)
 int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals, const uint32_t* d_x,
                      uint32_t per, uint32_t* d_sc);

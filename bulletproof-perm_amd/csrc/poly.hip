@@ -493,13 +493,23 @@ __global__ void __launch_bounds__(64 * (VC_W + 1)) k_verify_consts(uint32_t coun
 // (deck [k] canonical scalars in device memory, once per call): per-lane
 // strided partial products, then a tree over the workgroup in LDS (blockDim
 // more scalars behind the reduction scratch), added to <z^Q, c> by lane 0.
-template <bool DECK>
+//
+// PUB (a circuit with public inputs, circuit.h): the proof's constant vector is
+// c + W_U u_p, so <z^Q, c_p> takes sum_e z^(q_e + 1) W_U.val_e u_{p, col_e} more.
+// Entry-parallel over the workgroup (lane t: entries t, t + blockDim, ..., of
+// the flat list wu = [n_wu][q, col] then, from a multiple of 8 words, [n_wu]
+// Montgomery values), added to the lane's own acc[1] before the block sum: no
+// barrier, no reduction and no LDS of its own, and a public input read by many
+// rows costs what its entries cost.  pub: [count][n_pub][8] words, canonical.
+template <bool DECK, bool PUB = false>
 FE_INLINE void verify_scalars_body(uint32_t* lds, uint32_t n_p, uint32_t m, uint32_t Q, uint32_t lg,
                                    const uint32_t* __restrict__ rec, const uint32_t* __restrict__ kc,
                                    const uint32_t* __restrict__ cp, const uint32_t* __restrict__ ce,
                                    const uint32_t* __restrict__ cR, uint32_t* __restrict__ gen,
                                    uint32_t* __restrict__ sc_out, uint32_t NG, uint32_t npt,
-                                   const uint32_t* __restrict__ deck, uint32_t k) {
+                                   const uint32_t* __restrict__ deck, uint32_t k,
+                                   const uint32_t* __restrict__ wu = nullptr, uint32_t n_wu = 0,
+                                   const uint32_t* __restrict__ pub = nullptr, uint32_t n_pub = 0) {
   __builtin_amdgcn_s_setprio(2);  // (ahead of the proof-point decompression beside it)
   const uint32_t NY = min(n_p, (uint32_t)POW_LO);
   uint32_t* zt = lds;                // [Q + 1] z^e, Montgomery
@@ -569,6 +579,14 @@ FE_INLINE void verify_scalars_body(uint32_t* lds, uint32_t n_p, uint32_t m, uint
     const sc c = q + 1 == Q ? ldk(VK_NXP) : sc_to_mont(sc_load(cR + 8 * q));
     acc[1] = sc_add(acc[1], sc_mont(sc_load(zp + 8 * q), c));
   }
+  if constexpr (PUB) {
+    const uint32_t* wv = wu + ((2 * n_wu + 7) & ~7u);
+    const uint32_t* up = pub + 8 * (size_t)p * n_pub;
+    for (uint32_t e = threadIdx.x; e < n_wu; e += blockDim.x) {
+      const sc au = sc_mont(sc_load(wv + 8 * (size_t)e), sc_to_mont(sc_load(up + 8 * (size_t)wu[2 * e + 1])));
+      acc[1] = sc_add(acc[1], sc_mont(sc_load(zp + 8 * wu[2 * e]), au));
+    }
+  }
   VS_T(3);
   const sc wrx2fR = ldk(VK_WRX2F);
   const size_t pb = NG + (size_t)p * npt;
@@ -634,6 +652,17 @@ __global__ void __launch_bounds__(POLY_T) __attribute__((amdgpu_waves_per_eu(VS_
     uint32_t npt, const uint32_t* __restrict__ deck, uint32_t k) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   verify_scalars_body<true>(lds, n_p, m, Q, lg, rec, kc, cp, ce, cR, gen, sc_out, NG, npt, deck, k);
+}
+
+// (dynamic LDS = k_verify_scalars')
+__global__ void __launch_bounds__(POLY_T) __attribute__((amdgpu_waves_per_eu(VS_WPE))) k_verify_scalars_pub(
+    uint32_t n_p, uint32_t m, uint32_t Q, uint32_t lg, const uint32_t* __restrict__ rec,
+    const uint32_t* __restrict__ kc, const uint32_t* __restrict__ cp, const uint32_t* __restrict__ ce,
+    const uint32_t* __restrict__ cR, uint32_t* __restrict__ gen, uint32_t* __restrict__ sc_out, uint32_t NG,
+    uint32_t npt, const uint32_t* __restrict__ wu, uint32_t n_wu, const uint32_t* __restrict__ pub, uint32_t n_pub) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  verify_scalars_body<false, true>(lds, n_p, m, Q, lg, rec, kc, cp, ce, cR, gen, sc_out, NG, npt, nullptr, 0, wu, n_wu,
+                                   pub, n_pub);
 }
 
 // sc_out[i] = sum_p gen[p][i] (one workgroup per generator column)
@@ -982,7 +1011,8 @@ int circuit_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const u
 // flagged variable ids and their 32-byte-aligned Montgomery coefficients at the
 // given word offsets).  The 3n wire values live in LDS in Montgomery form (wire
 // id 3h + {0, 1, 2} = l_h, r_h, o_h).  First every gate side, one lane each:
-// an aux load, or the part of its combination over {1, v_j, x} (a col_sum-style
+// an aux load, or the part of its combination over {1, v_j, x, u_i} (u_i: the
+// proof's public inputs, ids 2 + m_in + i, wires from 2 + m_in + n_pub; a col_sum-style
 // term loop up to lc_wire) -- no side waits for another here.  Then the gates
 // by dependency level: within a level one lane per gate adds the wire terms of
 // both sides and forms the product, then a barrier -- a definition reads wires
@@ -999,24 +1029,29 @@ int circuit_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const u
 // image and the proof's inputs (Montgomery form) are copied into LDS first and
 // every level reads them there; taken whenever they fit beside the wires
 // (circuit::witness_program_staged_lds), the plain form beyond.
-// dynamic LDS = 32 B (the fail word) + 3n x 32 B [+ m_in x 32 B + the image].
+// dynamic LDS = 32 B (the fail word) + 3n x 32 B [+ (m_in + n_pub) x 32 B + the image].
 template <bool STAGE>
 FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, uint32_t n_p, uint32_t n_aux, uint32_t A,
                                     uint32_t nlev, uint32_t per, const uint32_t* __restrict__ prog,
                                     uint32_t prog_words, uint32_t o_lc, uint32_t o_wire, uint32_t o_lev, uint32_t o_gate,
                                     uint32_t o_var, uint32_t o_coef, const uint32_t* __restrict__ vals,
                                     const uint32_t* __restrict__ aux, const uint32_t* __restrict__ xs,
-                                    uint32_t* __restrict__ sc_out, uint32_t* __restrict__ fail) {
+                                    uint32_t* __restrict__ sc_out, uint32_t* __restrict__ fail, uint32_t n_pub,
+                                    const uint32_t* __restrict__ pubs) {
   uint32_t* bad = lds;                        // 1 + the first failing assert (8 words kept for alignment)
   uint32_t* wires = lds + 8;                  // [3n] Montgomery
   uint32_t* vm = wires + 8 * 3 * (size_t)n;   // STAGE: [m_in] inputs, Montgomery
-  uint32_t* image = vm + 8 * (size_t)m_in;    // STAGE: [prog_words] the device image
+  uint32_t* um = vm + 8 * (size_t)m_in;       // STAGE: [n_pub] public inputs, Montgomery
+  uint32_t* image = um + 8 * (size_t)n_pub;   // STAGE: [prog_words] the device image
   const uint32_t p = blockIdx.x, nt = blockDim.x, t = threadIdx.x;
   const uint32_t* vp = vals + 8 * (size_t)p * m_in;
+  const uint32_t* up = pubs + 8 * (size_t)p * n_pub;  // (not read when n_pub = 0)
+  const uint32_t wbase = 2 + m_in + n_pub;            // the first wire id
   const uint32_t* pg = prog;
   if constexpr (STAGE) {
     for (uint32_t i = t; i < prog_words; i += nt) image[i] = prog[i];
     for (uint32_t j = t; j < m_in; j += nt) sc_store(vm + 8 * (size_t)j, sc_to_mont(sc_load(vp + 8 * (size_t)j)));
+    for (uint32_t j = t; j < n_pub; j += nt) sc_store(um + 8 * (size_t)j, sc_to_mont(sc_load(up + 8 * (size_t)j)));
     pg = image;
   }
   const uint32_t *side_aux = pg, *lc_off = pg + o_lc, *lc_wire = pg + o_wire, *lev_off = pg + o_lev,
@@ -1028,12 +1063,18 @@ FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, ui
     if constexpr (STAGE) return sc_load(vm + 8 * (size_t)j);
     return sc_to_mont(sc_load(vp + 8 * (size_t)j));
   };
+  auto pub_in = [&](uint32_t j) {  // u_j, Montgomery
+    if constexpr (STAGE) return sc_load(um + 8 * (size_t)j);
+    return sc_to_mont(sc_load(up + 8 * (size_t)j));
+  };
   auto terms = [&](sc acc, uint32_t b, uint32_t e_end) {  // acc + terms [b, e_end), Montgomery
     for (uint32_t e = b; e < e_end; ++e) {
       const uint32_t tv = tvar[e], var = tv & circuit::kTermVar;
       const sc val = var == 0 ? oneR
                               : var <= m_in ? input(var - 1)
-                                            : var == m_in + 1 ? xR : sc_load(wires + 8 * (size_t)(var - 2 - m_in));
+                                            : var == m_in + 1 ? xR
+                                            : var < wbase     ? pub_in(var - 2 - m_in)
+                                                              : sc_load(wires + 8 * (size_t)(var - wbase));
       if (tv & circuit::kTermOne)
         acc = sc_add(acc, val);
       else if (tv & circuit::kTermNeg)
@@ -1089,10 +1130,11 @@ FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, ui
   uint32_t m_in, uint32_t n, uint32_t n_p, uint32_t n_aux, uint32_t A, uint32_t nlev, uint32_t per,                  \
       const uint32_t *__restrict__ prog, uint32_t prog_words, uint32_t o_lc, uint32_t o_wire, uint32_t o_lev,       \
       uint32_t o_gate, uint32_t o_var, uint32_t o_coef, const uint32_t *__restrict__ vals, const uint32_t *__restrict__ aux,         \
-      const uint32_t *__restrict__ xs, uint32_t *__restrict__ sc_out, uint32_t *__restrict__ fail
+      const uint32_t *__restrict__ xs, uint32_t *__restrict__ sc_out, uint32_t *__restrict__ fail, uint32_t n_pub,   \
+      const uint32_t *__restrict__ pubs
 #define WITNESS_PROGRAM_PASS \
   m_in, n, n_p, n_aux, A, nlev, per, prog, prog_words, o_lc, o_wire, o_lev, o_gate, o_var, o_coef, vals, aux, xs, \
-      sc_out, fail
+      sc_out, fail, n_pub, pubs
 __global__ void __launch_bounds__(256) k_witness_program(WITNESS_PROGRAM_ARGS) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   witness_program_body<true>(lds, WITNESS_PROGRAM_PASS);
@@ -1104,9 +1146,11 @@ __global__ void __launch_bounds__(256) k_witness_program_global(WITNESS_PROGRAM_
 }
 
 int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
-                        const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail) {
+                        const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail,
+                        const uint32_t* d_pub) {
   if (!P) return BPP_OK;
   const circuit::Program& G = *C.program;
+  if (G.n_pub && !d_pub) return BPP_ERR_ARG;
   const bool stage = circuit::witness_program_staged_lds(G) <= perm::kLdsMax;
   const size_t lds = stage ? circuit::witness_program_staged_lds(G) : circuit::witness_program_lds(G.n);
   if (lds > perm::kLdsMax) {
@@ -1124,7 +1168,7 @@ int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const 
     hipLaunchKernelGGL(stage ? k_witness_program : k_witness_program_global, dim3(P), dim3(nt), lds, ctx->stream,
                        G.m_in, G.n, C.n_p, G.n_aux, G.A, (uint32_t)G.level_off.size() - 1, per,
                        (const uint32_t*)d_prog, (uint32_t)G.dev.size(), G.dev_lc_off, G.dev_lc_wire, G.dev_level_off,
-                       G.dev_level_gate, G.dev_vars, G.dev_coefs, d_vals, d_aux, d_x, d_sc, fail);
+                       G.dev_level_gate, G.dev_vars, G.dev_coefs, d_vals, d_aux, d_x, d_sc, fail, G.n_pub, d_pub);
   }
   return ctx_check_launch(ctx, stage ? "k_witness_program" : "k_witness_program_global");
 }
@@ -1338,7 +1382,8 @@ int verify_scalars_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, con
 }
 
 int verify_scalars_dev_rec(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_rec,
-                           const uint32_t* seed, uint64_t first, uint32_t* d_sc) {
+                           const uint32_t* seed, uint64_t first, uint32_t* d_sc, const uint32_t* d_pub) {
+  if (C.n_pub && !d_pub) return BPP_ERR_ARG;
   std::vector<uint32_t> cp, ce;
   build_csr(C, cp, ce, true);
   std::vector<uint32_t> cw((size_t)C.Q * 8);
@@ -1362,6 +1407,19 @@ int verify_scalars_dev_rec(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count,
     BPP_TRY(ctx_ws(ctx, "vs_deck", (size_t)C.k * 32, &d_deck));
     BPP_TRY(ctx_h2d_const(ctx, "vs_deck", d_deck, C.cards.data(), (size_t)C.k * 32));
   }
+  void* d_wu = nullptr;
+  const uint32_t n_wu = (uint32_t)C.WU.size();
+  if (C.n_pub) {  // W_U as the flat entry list of k_verify_scalars_pub: the circuit, same every batch
+    std::vector<uint32_t> wu((((size_t)2 * n_wu + 7) & ~(size_t)7) + (size_t)8 * n_wu, 0);
+    uint32_t* wv = wu.data() + (((size_t)2 * n_wu + 7) & ~(size_t)7);
+    for (uint32_t e = 0; e < n_wu; ++e) {
+      wu[2 * e] = C.WU[e].q;
+      wu[2 * e + 1] = C.WU[e].col;
+      memcpy(wv + 8 * (size_t)e, C.WU[e].valR.v, 32);
+    }
+    BPP_TRY(ctx_ws(ctx, "vs_wu", wu.size() * 4 + 32, &d_wu));
+    BPP_TRY(ctx_h2d_const(ctx, "vs_wu", d_wu, wu.data(), wu.size() * 4));
+  }
   {
     ProfScope ps(ctx, "verify_scalars");
     hipLaunchKernelGGL(k_verify_consts, dim3((count + VC_P - 1) / VC_P), dim3(64 * (VC_W + 1)), 0, ctx->stream, count,
@@ -1370,6 +1428,10 @@ int verify_scalars_dev_rec(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count,
       hipLaunchKernelGGL(k_verify_scalars_deck, dim3(count), dim3(nt), lds + (size_t)nt * 32, ctx->stream, C.n_p, C.m,
                          C.Q, C.lg, d_rec, (const uint32_t*)d_kc, (const uint32_t*)d_cp, (const uint32_t*)d_ce,
                          (const uint32_t*)d_c, (uint32_t*)d_gen, d_sc, NG, npt, (const uint32_t*)d_deck, C.k);
+    else if (C.n_pub)
+      hipLaunchKernelGGL(k_verify_scalars_pub, dim3(count), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, C.lg, d_rec,
+                         (const uint32_t*)d_kc, (const uint32_t*)d_cp, (const uint32_t*)d_ce, (const uint32_t*)d_c,
+                         (uint32_t*)d_gen, d_sc, NG, npt, (const uint32_t*)d_wu, n_wu, d_pub, C.n_pub);
     else
       hipLaunchKernelGGL(k_verify_scalars, dim3(count), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, C.lg, d_rec,
                          (const uint32_t*)d_kc, (const uint32_t*)d_cp, (const uint32_t*)d_ce, (const uint32_t*)d_c,

@@ -36,8 +36,11 @@ inline uint32_t vpts_n(const perm::Circuit& C) { return C.m + 8 + 2 * C.lg; }
 // the t-check weight challenges) and bad ([count] u32, nonzero where a point
 // is the identity encoding, a scalar is not canonical or a challenge is
 // zero).  r_out and bad may be pinned host memory (written in place).
+// d_pub (C.n_pub > 0): [count][n_pub][8] words, each proof's public inputs,
+// absorbed as "pub" messages before its V_0.
 int verify_replay_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_init,
-                      const uint32_t* d_proofs, const uint32_t* d_V, uint32_t* d_rec, uint32_t* r_out, uint32_t* bad);
+                      const uint32_t* d_proofs, const uint32_t* d_V, uint32_t* d_rec, uint32_t* r_out, uint32_t* bad,
+                      const uint32_t* d_pub = nullptr);
 // Decompresses the proof points of proofs [p0, p1) (p1 = ~0u: count) of the
 // uploaded proofs / V into d_tbl ([count * vpts_n] Niels rows in MSM order);
 // *d_bad = the smallest index of an undecodable encoding (set to ~0 by the
@@ -58,9 +61,10 @@ int verify_sum_blocks_dev(bpp_ctx* ctx, uint32_t nb, uint32_t n, const uint32_t*
                           uint32_t* d_out);
 // k_verify_consts (each proof's weight perm::batch_weight(seed, first + p,
 // r_p) and its constants) + k_verify_scalars + k_verify_merge over device
-// records (poly.hip).  seed: 8 words, may be pinned host memory.
+// records (poly.hip).  seed: 8 words, may be pinned host memory.  d_pub
+// (C.n_pub > 0, k_verify_scalars_pub): [count][n_pub][8] words, canonical.
 int verify_scalars_dev_rec(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_rec,
-                           const uint32_t* seed, uint64_t first, uint32_t* d_sc);
+                           const uint32_t* seed, uint64_t first, uint32_t* d_sc, const uint32_t* d_pub = nullptr);
 // Per-proof verdicts (bpp_perm_verify_batch_each).  Term lists of proofs [p0,
 // p0 + M) for the multi-MSM engine: d_scal / d_idx [M][NG + npt] (generator
 // scalars d_gen[p][NG] on generator slots of a set of gn generators, then the

@@ -64,14 +64,18 @@ FE_INLINE bool w8_zero(const uint32_t w[8]) {
 // (Circuit::nv: 2k, or the deck circuit's k), m = nv + 1.  (The transcript in two launches -- its V part as
 // soon as the V bytes landed, the rest from the saved sponges -- was measured
 // behind a switch since removed and lost: profiles/r05_verify_ab.txt.)
-template <bool STAGED>
+// PUB (a circuit with public inputs): the proof's n_pub scalars (pub
+// [total][n_pub][8] words, p0 = 0) are absorbed as "pub" messages before V_0;
+// STAGED copies them into LDS behind the group's V bytes.
+template <bool STAGED, bool PUB = false>
 __global__ void __launch_bounds__(64) k_verify_replay_g(uint32_t p0, uint32_t p1, uint32_t total, uint32_t nv,
                                                         uint32_t lg, uint32_t n_p, const uint32_t* __restrict__ init,
                                                         const uint32_t* __restrict__ proofs, uint32_t pw,
                                                         const uint32_t* __restrict__ V, uint32_t* __restrict__ ch,
-                                                        uint32_t* __restrict__ okw) {
+                                                        uint32_t* __restrict__ okw, uint32_t n_pub = 0,
+                                                        const uint32_t* __restrict__ pub = nullptr) {
   __shared__ __attribute__((aligned(16))) uint8_t sp[RG_GROUPS * RG_GS];
-  extern __shared__ __attribute__((aligned(16))) uint32_t stage[];  // STAGED: [8][pw + 8 m]
+  extern __shared__ __attribute__((aligned(16))) uint32_t stage[];  // STAGED: [8][pw + 8 m (+ 8 n_pub)]
   // the replay is a latency chain and the proof-point decompression runs
   // beside it on the same SIMDs: win the issue arbitration
   __builtin_amdgcn_s_setprio(3);
@@ -93,18 +97,25 @@ __global__ void __launch_bounds__(64) k_verify_replay_g(uint32_t p0, uint32_t p1
   }
   const uint32_t* PV = nullptr;
   const uint32_t* PP = nullptr;
+  const uint32_t* PU = nullptr;
   if (STAGED) {
-    const uint32_t vw = 8 * m;
-    uint32_t* sg = stage + (size_t)g * (pw + vw);
+    const uint32_t vw = 8 * m, uw = PUB ? 8 * n_pub : 0;
+    uint32_t* sg = stage + (size_t)g * (pw + vw + uw);
     const uint4* sp4 = reinterpret_cast<const uint4*>(proofs + (size_t)p * pw);
     for (uint32_t i = gl; i < pw / 4; i += GRP_LANES) reinterpret_cast<uint4*>(sg)[i] = sp4[i];
     const uint4* sv4 = reinterpret_cast<const uint4*>(V + (size_t)p * m * 8);
     for (uint32_t i = gl; i < vw / 4; i += GRP_LANES) reinterpret_cast<uint4*>(sg + pw)[i] = sv4[i];
     PP = sg;
     PV = sg + pw;
+    if constexpr (PUB) {
+      const uint4* su4 = reinterpret_cast<const uint4*>(pub + (size_t)p * n_pub * 8);
+      for (uint32_t i = gl; i < uw / 4; i += GRP_LANES) reinterpret_cast<uint4*>(sg + pw + vw)[i] = su4[i];
+      PU = sg + pw + vw;
+    }
   } else {
     PP = proofs + (size_t)p * pw;
     PV = V + (size_t)p * m * 8;
+    if constexpr (PUB) PU = pub + (size_t)p * n_pub * 8;
   }
   GRP_FENCE();
 #if GRP_PAR_APPEND
@@ -116,6 +127,12 @@ __global__ void __launch_bounds__(64) k_verify_replay_g(uint32_t p0, uint32_t p1
   uint32_t* CH = ch + (size_t)(live ? p : total) * nch * 16;
   uint32_t w[8];
   bool ok = true;
+  if constexpr (PUB) {
+    for (uint32_t j = 0; j < n_pub; ++j) {
+      ld8(PU + 8 * j, w);
+      APPEND32("pub", 3, w, PU + 8 * j);
+    }
+  }
   for (uint32_t j = 0; j < nv; ++j) {
     ld8(PV + 8 * j, w);
     APPEND32("V", 1, w, PV + 8 * j);
@@ -291,7 +308,8 @@ void verify_init_state(const perm::Circuit& C, const uint8_t* label, size_t llen
 }
 
 int verify_replay_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_init,
-                      const uint32_t* d_proofs, const uint32_t* d_V, uint32_t* d_rec, uint32_t* r_out, uint32_t* bad) {
+                      const uint32_t* d_proofs, const uint32_t* d_V, uint32_t* d_rec, uint32_t* r_out, uint32_t* bad,
+                      const uint32_t* d_pub) {
   if (!count) return BPP_OK;
   const uint32_t pw = (uint32_t)(perm::proof_len(C) / 4);
   const uint32_t nch = 6 + C.lg;
@@ -301,8 +319,20 @@ int verify_replay_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, cons
   {
     ProfScope ps(ctx, "verify_replay_dev");
     // the proof and V bytes of the block's groups, staged in LDS while they fit
-    const size_t stage = (size_t)RG_GROUPS * (pw + 8 * (size_t)C.m) * 4;
-    if (stage <= 48 * 1024)
+    const size_t stage = (size_t)RG_GROUPS * (pw + 8 * ((size_t)C.m + C.n_pub)) * 4;
+    if (C.n_pub) {
+      // the public-input instantiations: the same staging rule over the
+      // group's proof, V and public words together
+      if (!d_pub) return BPP_ERR_ARG;
+      if (stage <= 48 * 1024)
+        hipLaunchKernelGGL((k_verify_replay_g<true, true>), dim3(grid_for(count, RG_GROUPS)), dim3(64), stage,
+                           ctx->stream, 0u, count, count, C.nv, C.lg, C.n_p, d_init, d_proofs, pw, d_V, (uint32_t*)d_ch,
+                           (uint32_t*)d_ok, C.n_pub, d_pub);
+      else
+        hipLaunchKernelGGL((k_verify_replay_g<false, true>), dim3(grid_for(count, RG_GROUPS)), dim3(64), 0, ctx->stream,
+                           0u, count, count, C.nv, C.lg, C.n_p, d_init, d_proofs, pw, d_V, (uint32_t*)d_ch,
+                           (uint32_t*)d_ok, C.n_pub, d_pub);
+    } else if (stage <= 48 * 1024)
       hipLaunchKernelGGL(k_verify_replay_g<true>, dim3(grid_for(count, RG_GROUPS)), dim3(64), stage, ctx->stream, 0u,
                          count, count, C.nv, C.lg, C.n_p, d_init, d_proofs, pw, d_V, (uint32_t*)d_ch, (uint32_t*)d_ok);
     else

@@ -468,7 +468,8 @@ int bpp_deck_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size
  * constant -a.  Q = defined sides + n_asserts + 1, m = m_in + 1, n_p = max(4,
  * next_pow2(n_gates)) <= bpp_gens_len(g), proof bytes 32 (13 + 2 log2 n_p).
  * The two-half circuit written this way compiles to bpp_perm_*'s matrices; the
- * deck circuit cannot be written (its constant depends on x).
+ * deck circuit cannot be written without public inputs (its constant depends
+ * on x and on the deck; with them see bpp_circuit_create_pub below).
  * Inside one combination the variable ids are strictly increasing and every
  * coefficient is canonical and nonzero, so one description has one digest:
  * SHAKE256("bpperm-circuit" || le32 m_in || le32 n_gates || le32 n_aux ||
@@ -540,6 +541,65 @@ int bpp_circuit_verify_batch(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit*
 int bpp_circuit_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit* c, size_t count,
                                   const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
                                   uint8_t* ok_out);
+
+/* ------------------------- caller-defined circuits with public inputs */
+/* Public inputs u_0..u_{n_pub-1} are canonical 32-byte scalars given per proof
+ * to the prover and to the verifier and never committed: "the card I play is
+ * one of THESE cards", "V_3 opens to THIS card", "my hand sums to THIS total",
+ * "V_0..V_{k-1} commit to a permutation of THIS table's deck" -- one compiled
+ * circuit, one digest and one merged batch MSM for proofs whose public data all
+ * differ.  bpp_circuit_desc is unchanged; n_pub is bpp_circuit_create_pub's own
+ * argument, and the variable ids of lc_var become
+ *   0 = one; 1+j = v_j; 1+m_in = x; 2+m_in+i = u_i;
+ *   2+m_in+n_pub+3h+{0,1,2} = l_h, r_h, o_h
+ * (ids still ascend: constants, inputs, x, public inputs, wires).  A term a u_i
+ * may stand in any defined side and in any assert, not on a free side.  It
+ * compiles to a sparse matrix W_U (Q x n_pub): +a at (q, i) for a defined side
+ * at row q, -a for an assert row -- the signs the constant of the same
+ * combination takes -- and proof p's constant vector is c + W_U u_p; nothing
+ * else of the statement depends on u.
+ * bpp_circuit_create(desc) equals bpp_circuit_create_pub(desc, 0, ..): same
+ * matrices, digest and bytes.  With n_pub > 0 the digest is
+ * SHAKE256("bpperm-pubcircuit" || le32 m_in || le32 n_pub || le32 n_gates ||
+ * le32 n_aux || le32 n_asserts || side_aux || lc_off || lc_var ||
+ * lc_coef)[0..32], and the transcript absorbs append_message("pub", u_i), 32
+ * bytes each, i < n_pub, right after append_message("circuit", digest): before
+ * V_0, x_perm and every other challenge, which binds the proof to them.
+ * n_pub <= 2^16 (BPP_ERR_LEN beyond); the other bounds are unchanged.  Proof
+ * format and bpp_circuit_proof_len are unchanged.
+ * The entry points above without `pub` return BPP_ERR_ARG for a circuit with
+ * n_pub > 0 (bpp_circuit_eval, _prove_batch, _verify, _verify_batch,
+ * _verify_batch_each); the _pub ones take every circuit (pub is not read when
+ * n_pub = 0). */
+int bpp_circuit_create_pub(const bpp_circuit_desc* desc, uint32_t n_pub, bpp_circuit** out);
+uint32_t bpp_circuit_n_pub(const bpp_circuit* c);
+/* bpp_circuit_matrix(c, 5, ..) returns W_U as (q, i, val) triplets. */
+/* bpp_circuit_eval with pub (n_pub x 32 B, canonical; NULL when n_pub = 0). */
+int bpp_circuit_eval_pub(const bpp_circuit* c, const uint8_t* v, const uint8_t* aux, const uint8_t* pub,
+                         const uint8_t x[32], uint8_t* aL, uint8_t* aR, uint8_t* aO, uint32_t* bad_assert);
+/* bpp_circuit_prove_batch with pub: count x n_pub x 32 B, proof-major (NULL
+ * when n_pub = 0; BPP_ERR_ARG if NULL with n_pub > 0).  Every pub scalar is
+ * checked canonical before any device work (BPP_ERR_NONCANONICAL).  pub rides
+ * the same upload as v and aux.  An assert that does not hold -- over the
+ * public inputs too -- is BPP_ERR_ARG naming the proof and the assert, before
+ * any output byte. */
+int bpp_circuit_prove_batch_pub(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit* c, size_t count, const uint8_t* v,
+                                const uint8_t* aux, const uint8_t* pub, const uint8_t* gammas, const uint8_t* seeds32,
+                                const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out);
+/* The three verifiers with pub (count x n_pub x 32 B; one proof's for
+ * bpp_circuit_verify_pub) after V: the same ok_out contract, count == 0
+ * behaviour and order of checks; a NULL pub with n_pub > 0 is BPP_ERR_ARG, a
+ * pub scalar >= l BPP_ERR_NONCANONICAL (ok_out all zero).  A proof verifies
+ * only under the public inputs it was made for.  pub in pinned host memory
+ * (bpp_host_alloc) goes up by DMA, as proofs and V do. */
+int bpp_circuit_verify_pub(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit* c, const uint8_t* label, size_t llen,
+                           const uint8_t* proof, size_t proof_len, const uint8_t* V, const uint8_t* pub);
+int bpp_circuit_verify_batch_pub(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit* c, size_t count,
+                                 const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
+                                 const uint8_t* pub);
+int bpp_circuit_verify_batch_each_pub(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit* c, size_t count,
+                                      const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
+                                      const uint8_t* pub, uint8_t* ok_out);
 
 /* Batch verification split for several GPUs (north_star: "the single large
  * verifier MSM partitions its bucket windows across GPUs"; reference verify
