@@ -1,7 +1,7 @@
 // Caller-defined circuits: the C ABI (bpp_circuit_*, include/bpperm.h) --
 // argument checks, bpp_guard and marshalling.  The compile and the host
-// witness are host/circuit.cpp; the prover is perm_prove.hip with the circuit
-// form of ShuffleIn, the verifier perm_verify.hip; the _pub entry points carry
+// witness are host/circuit.cpp; the prover is perm_prove.hip with the circuit's
+// rows of ProveInputs, the verifier perm_verify.hip; the _pub entry points carry
 // each proof's public inputs to both.
 #include <string>
 
@@ -27,18 +27,10 @@ int pub_check(const bpp_circuit* c, size_t count, const uint8_t* pub, size_t* ba
   const uint32_t n_pub = c->C.n_pub;
   if (!n_pub || !count) return BPP_OK;
   if (!pub) return BPP_ERR_ARG;
-  std::vector<uint8_t> nc(count, 0);
-  par::for_each(count, [&](size_t p) {
-    Sc t;
-    for (uint32_t i = 0; i < n_pub; ++i)
-      if (!hsc::from_canonical(t, pub + (p * (size_t)n_pub + i) * 32)) nc[p] = 1;
-  });
-  for (size_t p = 0; p < count; ++p)
-    if (nc[p]) {
-      *bad = p;
-      return BPP_ERR_NONCANONICAL;
-    }
-  return BPP_OK;
+  std::vector<int> nc(count, BPP_OK);
+  check_canonical(pub, n_pub, count, nc);
+  *bad = first_bad(nc);
+  return *bad == SIZE_MAX ? BPP_OK : BPP_ERR_NONCANONICAL;
 }
 
 // the entry points without `pub` take circuits without public inputs only
@@ -150,22 +142,13 @@ int bpp_circuit_prove_batch_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circu
     // before any output byte is written (it needs neither the context nor
     // the generators, whose null checks follow)
     std::vector<int> bad(count, BPP_OK);
-    par::for_each(count, [&](size_t p) {
-      Sc t;
-      for (uint32_t i = 0; i < m_in; ++i)
-        if (!hsc::from_canonical(t, v + (p * (size_t)m_in + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
-      for (uint32_t i = 0; i < n_aux; ++i)
-        if (!hsc::from_canonical(t, aux + (p * (size_t)n_aux + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
-      if (gammas)
-        for (uint32_t i = 0; i < m_in; ++i)
-          if (!hsc::from_canonical(t, gammas + (p * (size_t)m_in + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
-      t = hsc::zero();
-    });
-    for (size_t p = 0; p < count; ++p)
-      if (bad[p] != BPP_OK) {
-        if (ctx) ctx->err = "circuit proof " + std::to_string(p) + ": non-canonical value, auxiliary value or blinding";
-        return bad[p];
-      }
+    check_canonical(v, m_in, count, bad);
+    check_canonical(aux, n_aux, count, bad);
+    check_canonical(gammas, m_in, count, bad);
+    if (const size_t p = first_bad(bad); p != SIZE_MAX) {
+      if (ctx) ctx->err = "circuit proof " + std::to_string(p) + ": non-canonical value, auxiliary value or blinding";
+      return bad[p];
+    }
     {
       size_t p = 0;
       const int rc = pub_check(c, count, pub, &p);
@@ -174,11 +157,12 @@ int bpp_circuit_prove_batch_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circu
     }
     if (!ctx || !G) return BPP_ERR_ARG;
     if (!count) return BPP_OK;
-    ShuffleIn sh = {nullptr, nullptr, gammas};
-    sh.v = v;
-    sh.aux = aux;
-    sh.pub = c->C.n_pub ? pub : nullptr;
-    return prove_batch_entropy(ctx, G, c->C, count, seeds32, label, llen, proofs_out, V_out, &sh);
+    ProveInputs in;
+    in.values = {v, m_in};
+    in.aux = {n_aux ? aux : nullptr, n_aux};
+    in.gammas = {gammas, m_in};
+    in.pub = {c->C.n_pub ? pub : nullptr, c->C.n_pub};
+    return prove_batch_entropy(ctx, G, c->C, count, seeds32, label, llen, proofs_out, V_out, &in);
   });
 }
 
@@ -192,44 +176,25 @@ int bpp_circuit_prove_batch(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* 
 
 int bpp_circuit_verify_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, const uint8_t* label, size_t llen,
                            const uint8_t* proof, size_t proof_len, const uint8_t* V, const uint8_t* pub) {
-  return bpp_guard(ctx, [&]() -> int {
-    if (!ctx || !G || !c || !proof || !V || (!label && llen)) return BPP_ERR_ARG;
-    size_t bad = 0;
-    BPP_TRY(pub_check(c, 1, pub, &bad));
-    if (proof_len != perm::proof_len(c->C)) return BPP_ERR_VERIFY;
-    BPP_HIP(hipSetDevice(ctx->device));
-    return verify_batch(ctx, G, c->C, label, llen, 1, proof, V, pub);
-  });
+  size_t bad = 0;
+  return verify_entry({ctx, G, label, llen, 1, proof, V, pub}, c != nullptr, proof_len == bpp_circuit_proof_len(c),
+                      [&] { return pub_check(c, 1, pub, &bad); }, [&]() -> const perm::Circuit& { return c->C; });
 }
 
 int bpp_circuit_verify_batch_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count,
                                  const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
                                  const uint8_t* pub) {
-  return bpp_guard(ctx, [&]() -> int {
-    if (!ctx || !G || !c || ((!proofs || !V) && count) || (!label && llen)) return BPP_ERR_ARG;
-    if (!count) return BPP_OK;
-    size_t bad = 0;
-    BPP_TRY(pub_check(c, count, pub, &bad));
-    BPP_HIP(hipSetDevice(ctx->device));
-    return verify_batch(ctx, G, c->C, label, llen, count, proofs, V, pub);
-  });
+  size_t bad = 0;
+  return verify_entry({ctx, G, label, llen, count, proofs, V, pub}, c != nullptr, true,
+                      [&] { return pub_check(c, count, pub, &bad); }, [&]() -> const perm::Circuit& { return c->C; });
 }
 
 int bpp_circuit_verify_batch_each_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, size_t count,
                                       const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
                                       const uint8_t* pub, uint8_t* ok_out) {
-  // (no pass is ever left behind by a call that fails)
-  if (ok_out && count) memset(ok_out, 0, count);
-  return bpp_guard(ctx, [&]() -> int {
-    if (!ctx || !G || !c || ((!proofs || !V || !ok_out) && count) || (!label && llen)) return BPP_ERR_ARG;
-    if (!count) return BPP_OK;
-    size_t bad = 0;
-    BPP_TRY(pub_check(c, count, pub, &bad));
-    BPP_HIP(hipSetDevice(ctx->device));
-    const int rc = verify_batch_each(ctx, G, c->C, label, llen, count, proofs, V, ok_out, pub);
-    if (rc != BPP_OK && rc != BPP_ERR_VERIFY) memset(ok_out, 0, count);
-    return rc;
-  });
+  size_t bad = 0;
+  return verify_entry({ctx, G, label, llen, count, proofs, V, pub, true, ok_out}, c != nullptr, true,
+                      [&] { return pub_check(c, count, pub, &bad); }, [&]() -> const perm::Circuit& { return c->C; });
 }
 
 int bpp_circuit_verify(bpp_ctx* ctx, const bpp_gens* G, const bpp_circuit* c, const uint8_t* label, size_t llen,

@@ -100,6 +100,28 @@ inline size_t poly_coef_lds(uint32_t Q, uint32_t n_p) {
 inline size_t verify_scalars_lds(uint32_t Q, uint32_t n_p) {
   return ((size_t)Q + 1 + 2 * (n_p < kPolyLanes ? n_p : kPolyLanes)) * 32 + (kPolyLanes / 64) * 2 * 32;
 }
+// The chain witness kernels (poly.hip chain_prefix_products; k_witness and
+// k_witness_cards: 2 chains of k, k_witness_deck: 1): the prefix products
+// [chains][k] and two scan buffers [chains][lanes] of 32-byte scalars.  256
+// lanes while that fits; the two-chain kernels then go on at 128, and the
+// device witness ends (the host's begins) past chain_witness_dev_max.
+constexpr uint32_t chain_witness_min_lanes(uint32_t chains) { return chains == 2 ? 128 : 256; }
+constexpr size_t chain_witness_lds(uint32_t chains, uint32_t k, uint32_t lanes) {
+  return ((size_t)chains * k + 2 * (size_t)chains * lanes) * 32;
+}
+constexpr uint32_t chain_witness_lanes(uint32_t chains, uint32_t k) {
+  return chain_witness_lds(chains, k, 256) <= kLdsMax ? 256 : chain_witness_min_lanes(chains);
+}
+constexpr size_t chain_witness_lds(uint32_t chains, uint32_t k) {
+  return chain_witness_lds(chains, k, chain_witness_lanes(chains, k));
+}
+constexpr uint32_t chain_witness_dev_max(uint32_t chains) {
+  return (uint32_t)(kLdsMax / 32 - 2 * chains * chain_witness_min_lanes(chains)) / chains;
+}
+static_assert(chain_witness_dev_max(2) == 768 && chain_witness_lanes(2, 512) == 256 && chain_witness_lanes(2, 513) == 128 &&
+                  chain_witness_dev_max(1) == 1536 && chain_witness_lds(1, 1536) == kLdsMax &&
+                  chain_witness_lds(2, 768) == kLdsMax,
+              "the witness paths' sizes");
 
 // v = [1..k, pi(1..k), x]; gate values (sound create_a)
 void witness(const Circuit& C, const std::vector<uint32_t>& pi, const hsc::Sc& x, std::vector<hsc::Sc>& v,

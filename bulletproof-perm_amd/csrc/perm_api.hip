@@ -58,39 +58,26 @@ int bpp_perm_prove_shuffle_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, si
     if (((!cards || !perms || !proofs_out || !V_out) && count) || (!label && llen) || !k_in_range(k))
       return BPP_ERR_ARG;
     // the whole witness is checked before any device work and before any
-    // output byte is written (it needs neither the context nor the
-    // generators, whose null checks follow): every perm a bijection on
-    // [0, k), every card and supplied blinding a canonical scalar
+    // output byte is written: every perm a bijection on [0, k), every card
+    // and supplied blinding a canonical scalar
     std::vector<int> bad(count, BPP_OK);
-    par::for_each(count, [&](size_t p) {
-      std::vector<uint8_t> seen(k, 0);
-      const uint32_t* pm = perms + p * (size_t)k;
-      for (uint32_t i = 0; i < k; ++i) {
-        if (pm[i] >= k || seen[pm[i]]) {
-          bad[p] = BPP_ERR_ARG;
-          return;
-        }
-        seen[pm[i]] = 1;
-      }
-      Sc t;
-      for (uint32_t i = 0; i < k; ++i)
-        if (!hsc::from_canonical(t, cards + (p * (size_t)k + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
-      if (gammas)
-        for (uint32_t i = 0; i < 2 * k; ++i)
-          if (!hsc::from_canonical(t, gammas + (p * 2 * (size_t)k + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
-      t = hsc::zero();
-    });
-    for (size_t p = 0; p < count; ++p)
-      if (bad[p] != BPP_OK) {
-        if (ctx)
-          ctx->err = bad[p] == BPP_ERR_ARG ? "shuffle " + std::to_string(p) + ": perm is not a bijection on [0, k)"
-                                           : "shuffle " + std::to_string(p) + ": non-canonical card or blinding";
-        return bad[p];
-      }
+    check_perms(perms, count, k, bad);
+    check_canonical(cards, k, count, bad);
+    check_canonical(gammas, 2 * (size_t)k, count, bad);
+    if (const size_t p = first_bad(bad); p != SIZE_MAX) {
+      if (ctx)
+        ctx->err = bad[p] == BPP_ERR_ARG ? "shuffle " + std::to_string(p) + ": perm is not a bijection on [0, k)"
+                                         : "shuffle " + std::to_string(p) + ": non-canonical card or blinding";
+      return bad[p];
+    }
     if (!ctx || !G) return BPP_ERR_ARG;
     if (!count) return BPP_OK;
-    const ShuffleIn sh = {cards, perms, gammas};
-    return prove_batch_entropy(ctx, G, perm::build(k), count, seeds32, label, llen, proofs_out, V_out, &sh);
+    ProveInputs in;
+    in.perms = perms;
+    in.n_perm = k;
+    in.values = {cards, k};
+    in.gammas = {gammas, 2 * k};
+    return prove_batch_entropy(ctx, G, perm::build(k), count, seeds32, label, llen, proofs_out, V_out, &in);
   });
 }
 
@@ -121,80 +108,47 @@ int bpp_deck_prove_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t cou
   return bpp_guard(ctx, [&]() -> int {
     if (((!perms || !proofs_out || !V_out) && count) || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
     // the whole witness is checked before any device work and before any
-    // output byte is written (bpp_perm_prove_shuffle_batch's checks, in its
-    // order): every perm a bijection on [0, k), every deck card and supplied
-    // blinding a canonical scalar
+    // output byte is written: every perm a bijection on [0, k), then every
+    // deck card, then every supplied blinding a canonical scalar
     std::vector<int> bad(count, BPP_OK);
-    par::for_each(count, [&](size_t p) {
-      std::vector<uint8_t> seen(k, 0);
-      const uint32_t* pm = perms + p * (size_t)k;
-      for (uint32_t i = 0; i < k; ++i) {
-        if (pm[i] >= k || seen[pm[i]]) {
-          bad[p] = BPP_ERR_ARG;
-          return;
-        }
-        seen[pm[i]] = 1;
-      }
-      Sc t;
-      if (gammas)
-        for (uint32_t i = 0; i < k; ++i)
-          if (!hsc::from_canonical(t, gammas + (p * (size_t)k + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
-      t = hsc::zero();
-    });
-    for (size_t p = 0; p < count; ++p)
-      if (bad[p] == BPP_ERR_ARG) {
-        if (ctx) ctx->err = "deck proof " + std::to_string(p) + ": perm is not a bijection on [0, k)";
-        return BPP_ERR_ARG;
-      }
+    check_perms(perms, count, k, bad);
+    check_canonical(gammas, k, count, bad);
+    if (const size_t p = first_bad(bad, BPP_ERR_ARG); p != SIZE_MAX) {
+      if (ctx) ctx->err = "deck proof " + std::to_string(p) + ": perm is not a bijection on [0, k)";
+      return BPP_ERR_ARG;
+    }
     BPP_TRY(deck_canonical(ctx, k, deck));
-    for (size_t p = 0; p < count; ++p)
-      if (bad[p] != BPP_OK) {
-        if (ctx) ctx->err = "deck proof " + std::to_string(p) + ": non-canonical blinding";
-        return bad[p];
-      }
+    if (const size_t p = first_bad(bad); p != SIZE_MAX) {
+      if (ctx) ctx->err = "deck proof " + std::to_string(p) + ": non-canonical blinding";
+      return bad[p];
+    }
     if (!ctx || !G) return BPP_ERR_ARG;
     if (!count) return BPP_OK;
-    const ShuffleIn sh = {nullptr, perms, gammas};
-    return prove_batch_entropy(ctx, G, perm::build_deck(k, deck), count, seeds32, label, llen, proofs_out, V_out, &sh);
+    ProveInputs in;
+    in.perms = perms;
+    in.n_perm = k;
+    in.gammas = {gammas, k};
+    return prove_batch_entropy(ctx, G, perm::build_deck(k, deck), count, seeds32, label, llen, proofs_out, V_out, &in);
   });
 }
 
 int bpp_deck_verify(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, const uint8_t* deck, const uint8_t* label,
                     size_t llen, const uint8_t* proof, size_t proof_len, const uint8_t* V) {
-  return bpp_guard(ctx, [&]() -> int {
-    if (!ctx || !G || !proof || !V || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
-    BPP_TRY(deck_canonical(ctx, k, deck));
-    if (proof_len != bpp_deck_proof_len(k)) return BPP_ERR_VERIFY;
-    BPP_HIP(hipSetDevice(ctx->device));
-    return verify_batch(ctx, G, perm::build_deck(k, deck), label, llen, 1, proof, V);
-  });
+  return verify_entry({ctx, G, label, llen, 1, proof, V}, k_in_range(k), proof_len == bpp_deck_proof_len(k),
+                      [&] { return deck_canonical(ctx, k, deck); }, [&] { return perm::build_deck(k, deck); });
 }
 
 int bpp_deck_verify_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* deck,
                           const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V) {
-  return bpp_guard(ctx, [&]() -> int {
-    if (!ctx || !G || ((!proofs || !V) && count) || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
-    BPP_TRY(deck_canonical(ctx, k, deck));
-    if (!count) return BPP_OK;
-    BPP_HIP(hipSetDevice(ctx->device));
-    return verify_batch(ctx, G, perm::build_deck(k, deck), label, llen, count, proofs, V);
-  });
+  return verify_entry({ctx, G, label, llen, count, proofs, V}, k_in_range(k), true,
+                      [&] { return deck_canonical(ctx, k, deck); }, [&] { return perm::build_deck(k, deck); });
 }
 
 int bpp_deck_verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* deck,
                                const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
                                uint8_t* ok_out) {
-  // (no pass is ever left behind by a call that fails)
-  if (ok_out && count) memset(ok_out, 0, count);
-  return bpp_guard(ctx, [&]() -> int {
-    if (!ctx || !G || ((!proofs || !V || !ok_out) && count) || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
-    BPP_TRY(deck_canonical(ctx, k, deck));
-    if (!count) return BPP_OK;
-    BPP_HIP(hipSetDevice(ctx->device));
-    const int rc = verify_batch_each(ctx, G, perm::build_deck(k, deck), label, llen, count, proofs, V, ok_out);
-    if (rc != BPP_OK && rc != BPP_ERR_VERIFY) memset(ok_out, 0, count);
-    return rc;
-  });
+  return verify_entry({ctx, G, label, llen, count, proofs, V, nullptr, true, ok_out}, k_in_range(k), true,
+                      [&] { return deck_canonical(ctx, k, deck); }, [&] { return perm::build_deck(k, deck); });
 }
 
 int bpp_debug_secret_residue(bpp_ctx* ctx, uint64_t* nonzero_bytes) {
@@ -209,42 +163,20 @@ int bpp_debug_secret_residue(bpp_ctx* ctx, uint64_t* nonzero_bytes) {
 
 int bpp_perm_verify(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, const uint8_t* label, size_t llen,
                     const uint8_t* proof, size_t proof_len, const uint8_t* V) {
-  return bpp_guard(ctx, [&]() -> int {
-    if (!ctx || !G || !proof || !V || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
-    if (proof_len != perm::proof_len(k)) return BPP_ERR_VERIFY;
-    BPP_HIP(hipSetDevice(ctx->device));
-    const perm::Circuit C = perm::build(k);
-    return verify_batch(ctx, G, C, label, llen, 1, proof, V);
-  });
+  return verify_entry({ctx, G, label, llen, 1, proof, V}, k_in_range(k), proof_len == bpp_perm_proof_len(k), no_refusal,
+                      [&] { return perm::build(k); });
 }
 
 int bpp_perm_verify_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* label, size_t llen,
                           const uint8_t* proofs, const uint8_t* V) {
-  return bpp_guard(ctx, [&]() -> int {
-    if (!ctx || !G || ((!proofs || !V) && count) || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
-    if (!count) return BPP_OK;
-    // (the context's own spin: the verifier's waits already spin where they
-    // sit on the critical path (ctx_sync_latency), and syncs that spin 300 us
-    // before sleeping measured within noise, profiles/r06_sync_spin_ab.txt)
-    BPP_HIP(hipSetDevice(ctx->device));
-    const perm::Circuit C = perm::build(k);
-    return verify_batch(ctx, G, C, label, llen, count, proofs, V);
-  });
+  return verify_entry({ctx, G, label, llen, count, proofs, V}, k_in_range(k), true, no_refusal,
+                      [&] { return perm::build(k); });
 }
 
 int bpp_perm_verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_t count, const uint8_t* label,
                                size_t llen, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out) {
-  // (no pass is ever left behind by a call that fails)
-  if (ok_out && count) memset(ok_out, 0, count);
-  return bpp_guard(ctx, [&]() -> int {
-    if (!ctx || !G || ((!proofs || !V || !ok_out) && count) || (!label && llen) || !k_in_range(k)) return BPP_ERR_ARG;
-    if (!count) return BPP_OK;
-    BPP_HIP(hipSetDevice(ctx->device));
-    const perm::Circuit C = perm::build(k);
-    const int rc = verify_batch_each(ctx, G, C, label, llen, count, proofs, V, ok_out);
-    if (rc != BPP_OK && rc != BPP_ERR_VERIFY) memset(ok_out, 0, count);
-    return rc;
-  });
+  return verify_entry({ctx, G, label, llen, count, proofs, V, nullptr, true, ok_out}, k_in_range(k), true, no_refusal,
+                      [&] { return perm::build(k); });
 }
 
 int bpp_perm_verify_begin(uint32_t k, size_t count, const uint8_t* label, size_t llen, const uint8_t* proofs,

@@ -88,18 +88,76 @@ inline void proof_points(const Proof& P, uint8_t* out) {
   for (auto& r : P.ipa.R) add(r);
 }
 
-// A caller-supplied shuffle (bpp_perm_prove_shuffle_batch, bpp_deck_prove_batch):
-// this batch's slices of the caller's arrays, validated by the entry point.
-// The circuit form (bpp_circuit_prove_batch; C.program set): v, aux, gammas and
-// (bpp_circuit_prove_batch_pub) pub, no cards and no perms.
-struct ShuffleIn {
-  const uint8_t* cards;   // [P][k] canonical scalars; nullptr with the deck circuit (the deck is the circuit's)
-  const uint32_t* perms;  // [P][k], each a bijection on [0, k)
-  const uint8_t* gammas;  // nullptr (drawn), or [P][C.nv] canonical scalars
-  const uint8_t* v = nullptr;    // [P][m_in] canonical scalars: the committed inputs
-  const uint8_t* aux = nullptr;  // [P][n_aux] canonical scalars: the free gate sides' values
-  const uint8_t* pub = nullptr;  // [P][n_pub] canonical scalars: the public inputs (nullptr when n_pub = 0)
-  size_t first = 0;              // this slice's first proof in the caller's batch (error messages)
+// A caller's array of canonical scalars, [P][per] x 32 bytes (p = nullptr: none).
+struct ScalarRows {
+  const uint8_t* p = nullptr;
+  uint32_t per = 0;
+  const uint8_t* at(size_t i) const { return p + i * 32 * (size_t)per; }
+  size_t bytes(size_t P) const { return p ? P * 32 * (size_t)per : 0; }
+};
+
+// The witness a caller hands the prover in place of the seed's own: this
+// batch's rows of the caller's arrays, validated by the entry point.
+//   statement                        perms  values      aux    gammas  pub
+//   two-half shuffle (perm::build)   [k]    k cards     -      2k      -
+//   deck (perm::build_deck)          [k]    - (C.cards) -      k       -
+//   circuit (C.program)              -      m_in (v)    n_aux  m_in    n_pub
+// gammas: the blindings of V_0..V_{nv-1}, drawn when there are none.
+struct ProveInputs {
+  const uint32_t* perms = nullptr;  // [P][n_perm], each a bijection on [0, n_perm)
+  uint32_t n_perm = 0;
+  ScalarRows values, aux, gammas, pub;
+  size_t first = 0;  // the batch's first proof in the caller's call (error messages)
+
+  // the same from the batch's proof b on
+  ProveInputs slice(size_t b) const {
+    ProveInputs s = *this;
+    if (perms) s.perms += b * (size_t)n_perm;
+    for (ScalarRows* r : {&s.values, &s.aux, &s.gammas, &s.pub})
+      if (r->p) r->p = r->at(b);
+    s.first += b;
+    return s;
+  }
+};
+
+// One batch's staged upload ("pb_rng_in", one copy): the draw templates [P][7]
+// u64 and pi [P][k] u32, then -- with inputs, 32-byte aligned: the kernels read
+// them with 16-byte loads -- values, aux, gammas and pub (public, wiped with the
+// secrets all the same).  Offsets in bytes, computed here once.
+struct StageLayout {
+  struct Rows {
+    ScalarRows src;  // the caller's
+    size_t off = 0, bytes = 0;
+    void stage(uint8_t* base, size_t i) const {  // proof i's row into the staging buffer
+      if (src.p) memcpy(base + off + i * 32 * (size_t)src.per, src.at(i), 32 * (size_t)src.per);
+    }
+    const uint32_t* dev(const void* base) const {  // the uploaded rows
+      return src.p ? (const uint32_t*)((const uint8_t*)base + off) : nullptr;
+    }
+  };
+  size_t tmpl = 0, tmpl_bytes, pi, pi_bytes, pad, pad_bytes;
+  Rows values, aux, gammas, pub;
+  size_t bytes;
+  StageLayout(size_t P, uint32_t k, const ProveInputs* in) {
+    tmpl_bytes = P * 7 * sizeof(uint64_t);
+    pi = tmpl_bytes;
+    pi_bytes = P * 4 * (size_t)k;
+    pad = bytes = pi + pi_bytes;
+    if (in) bytes = (bytes + 31) & ~(size_t)31;
+    pad_bytes = bytes - pad;
+    auto place = [&](Rows& r, const ScalarRows& src) {
+      r.src = src;
+      r.off = bytes;
+      r.bytes = src.bytes(P);
+      bytes += r.bytes;
+    };
+    if (in) {
+      place(values, in->values);
+      place(aux, in->aux);
+      place(gammas, in->gammas);
+      place(pub, in->pub);
+    }
+  }
 };
 
 // One proof's Fiat-Shamir challenges (verify_replay).
@@ -156,13 +214,13 @@ namespace perm_impl BPP_HIDDEN {
 
 // --- prover (perm_prove.hip)
 int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
-                const uint8_t* label, size_t llen, std::vector<Proof>& Ps, const ShuffleIn* sh = nullptr);
+                const uint8_t* label, size_t llen, std::vector<Proof>& Ps, const ProveInputs* in = nullptr);
 int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
                     const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out, bool wipe = false,
-                    const ShuffleIn* sh = nullptr);
+                    const ProveInputs* in = nullptr);
 int prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, size_t count, const uint8_t* seeds32,
                         const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out,
-                        const ShuffleIn* sh = nullptr);
+                        const ProveInputs* in = nullptr);
 int prove_wipe(bpp_ctx* ctx);
 int secret_residue(bpp_ctx* ctx, uint64_t* nz);
 
@@ -192,5 +250,86 @@ int verify_slice_points_dev(bpp_ctx* ctx, const bpp_verify_job& J, void* d_out);
 size_t verify_terms(const bpp_verify_job& J);
 int verify_terms_weighted(const bpp_verify_job& J, const uint8_t seed[32], size_t first, std::vector<Sc>& sc,
                           std::vector<uint8_t>& enc);
+
+// --- argument checks the C ABI's entry points share (perm_api.hip,
+// circuit_api.hip).  They look at the caller's arrays alone, so the provers run
+// them before the context's and the generators' null checks.
+
+// bad[p] = BPP_ERR_ARG where perms[p] ([count][k]) is no bijection on [0, k)
+inline void check_perms(const uint32_t* perms, size_t count, uint32_t k, std::vector<int>& bad) {
+  par::for_each(count, [&](size_t p) {
+    std::vector<uint8_t> seen(k, 0);
+    const uint32_t* pm = perms + p * (size_t)k;
+    for (uint32_t i = 0; i < k; ++i) {
+      if (pm[i] >= k || seen[pm[i]]) {
+        bad[p] = BPP_ERR_ARG;
+        return;
+      }
+      seen[pm[i]] = 1;
+    }
+  });
+}
+
+// bad[p] = BPP_ERR_NONCANONICAL where one of proof p's scalars (ptr
+// [count][per_proof] x 32 bytes; nullptr: none to check) is >= l; a proof
+// already refused keeps its code and is not read
+inline void check_canonical(const uint8_t* ptr, size_t per_proof, size_t count, std::vector<int>& bad) {
+  if (!ptr) return;
+  par::for_each(count, [&](size_t p) {
+    if (bad[p] != BPP_OK) return;
+    Sc t;
+    for (size_t i = 0; i < per_proof; ++i)
+      if (!hsc::from_canonical(t, ptr + (p * per_proof + i) * 32)) bad[p] = BPP_ERR_NONCANONICAL;
+    t = hsc::zero();
+  });
+}
+
+// the first proof refused with `code` (0: with any), or SIZE_MAX
+inline size_t first_bad(const std::vector<int>& bad, int code = 0) {
+  for (size_t p = 0; p < bad.size(); ++p)
+    if (code ? bad[p] == code : bad[p] != BPP_OK) return p;
+  return SIZE_MAX;
+}
+
+// One call of bpp_*_verify (count = 1), _verify_batch or _verify_batch_each
+// (each: ok_out [count], where no pass is ever left behind by a call that fails).
+struct VerifyCall {
+  bpp_ctx* ctx;
+  const bpp_gens* G;
+  const uint8_t* label;
+  size_t llen, count;
+  const uint8_t *proofs, *V;
+  const uint8_t* pub = nullptr;  // [count][n_pub] (verify_batch)
+  bool each = false;
+  uint8_t* ok_out = nullptr;
+};
+
+// What every such entry point does, in the order its refusals win: the
+// arguments (stmt_ok: the statement's own, "k is in range" or "the circuit is
+// not null"), the statement's refusals (pre(): a non-canonical deck card or
+// public input), an empty batch, a single proof of the wrong length (len_ok),
+// the device; then the verifier on the circuit that build() returns.
+template <class Pre, class Build>
+int verify_entry(const VerifyCall& a, bool stmt_ok, bool len_ok, Pre&& pre, Build&& build) {
+  if (a.each && a.ok_out && a.count) memset(a.ok_out, 0, a.count);
+  bpp_ctx* const ctx = a.ctx;  // (BPP_HIP names it)
+  return bpp_guard(ctx, [&]() -> int {
+    if (!ctx || !a.G || ((!a.proofs || !a.V || (a.each && !a.ok_out)) && a.count) || (!a.label && a.llen) || !stmt_ok)
+      return BPP_ERR_ARG;
+    BPP_TRY(pre());
+    if (!a.count) return BPP_OK;
+    if (!len_ok) return BPP_ERR_VERIFY;
+    // (the context's own spin: the verifier's waits already spin where they
+    // sit on the critical path (ctx_sync_latency), and syncs that spin 300 us
+    // before sleeping measured within noise, profiles/r06_sync_spin_ab.txt)
+    BPP_HIP(hipSetDevice(ctx->device));
+    const perm::Circuit& C = build();
+    if (!a.each) return verify_batch(a.ctx, a.G, C, a.label, a.llen, a.count, a.proofs, a.V, a.pub);
+    const int rc = verify_batch_each(a.ctx, a.G, C, a.label, a.llen, a.count, a.proofs, a.V, a.ok_out, a.pub);
+    if (rc != BPP_OK && rc != BPP_ERR_VERIFY) memset(a.ok_out, 0, a.count);
+    return rc;
+  });
+}
+inline int no_refusal() { return BPP_OK; }
 
 }  // namespace perm_impl

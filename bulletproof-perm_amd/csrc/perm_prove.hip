@@ -24,7 +24,7 @@
 #include "poly.h"
 #include "verify_dev.h"
 
-using namespace perm_impl;  // (Proof, ShuffleIn, Sc)
+using namespace perm_impl;  // (Proof, ProveInputs, Sc)
 
 namespace {
 
@@ -270,7 +270,7 @@ struct ProveBatch {
   const uint8_t* const label;
   const size_t llen;
   std::vector<Proof>& Ps;
-  const ShuffleIn* const sh;  // a caller's shuffle: read by draws_upload and Vx_witness only
+  const ProveInputs* const in;  // a caller's witness (nullptr: the seed's own)
   const size_t P = seeds.size();
   const uint32_t k = C.k, n_p = C.n_p, m = C.m;
   const uint32_t nv = C.nv;          // V commitments before x_perm (2k; the deck circuit's k)
@@ -283,7 +283,7 @@ struct ProveBatch {
   // (circuit::lds_fits); BPP_CIRCUIT_HOST_WITNESS=1: its host witness
   const bool dev_witness = C.program ? !circuit_host_witness()
                            : C.deck  ? k <= DECK_WITNESS_DEV_MAX && !deck_host_witness()
-                                     : (2 * (size_t)k + 512) * 32 <= 64 * 1024;
+                                     : k <= perm::chain_witness_dev_max(2);
   // (a plain reference: pool workers must reach THIS thread's states, a
   // thread_local named inside their lambdas would be their own)
   std::vector<std::unique_ptr<ProverState>>& S = prover_states_tl();
@@ -300,8 +300,8 @@ struct ProveBatch {
   std::vector<Sc> zwvg = std::vector<Sc>(P);  // <z^Q W_V, gamma> per proof (k_poly_coef)
 
   ProveBatch(bpp_ctx* ctx_, const bpp_gens* G_, const perm::Circuit& C_, const std::vector<perm::Seed>& seeds_,
-             const uint8_t* label_, size_t llen_, std::vector<Proof>& Ps_, const ShuffleIn* sh_)
-      : ctx(ctx_), G(G_), C(C_), seeds(seeds_), label(label_), llen(llen_), Ps(Ps_), sh(sh_) {
+             const uint8_t* label_, size_t llen_, std::vector<Proof>& Ps_, const ProveInputs* in_)
+      : ctx(ctx_), G(G_), C(C_), seeds(seeds_), label(label_), llen(llen_), Ps(Ps_), in(in_) {
     while (S.size() < P) S.emplace_back(new ProverState());
     par::for_each(P, [&](size_t p) { S[p]->tr = merlin::Transcript(label, llen); });
     for (size_t p = 0; p < P; ++p) trs[p] = &S[p]->tr;
@@ -330,41 +330,31 @@ const uint8_t* sc_bytes(const Sc& s) { return reinterpret_cast<const uint8_t*>(s
 int ProveBatch::draws_upload() {
   HostScope hs(ctx, "pb_rng");
   void* dst = nullptr;
-  const size_t tlen = 7 * sizeof(uint64_t);  // draw template per proof
   for (const perm::Seed& sd : seeds)
     if (sd.len != seeds[0].len) {
       ctx->err = "prove_batch: seeds of different lengths in one batch";
       return BPP_ERR_ARG;
     }
-  BPP_TRY(ctx_ws(ctx, "pb_gamma", (size_t)P * m * 32, (void**)&d_gamma));
-  BPP_TRY(ctx_ws(ctx, "mt_s", (size_t)P * per * 32 + 32, (void**)&d_s));
-  // templates then pi, one device buffer filled by one copy; a caller's
-  // shuffle appends its cards and V blindings (32-byte aligned: the kernels
-  // read them with 16-byte loads) to the same buffer and the same copy
-  const size_t rng_bytes = P * tlen + (size_t)P * k * 4;
-  // (the deck circuit's cards are the call's, public: "pb_deck" below)
-  // (a caller-defined circuit: its inputs v in the cards' place, then aux)
-  const uint32_t n_aux = C.program ? C.program->n_aux : 0;
-  const uint32_t n_pub = C.n_pub;
-  if (C.program && !(sh && sh->v && (sh->aux || !n_aux) && (sh->pub || !n_pub))) {
+  if (C.program && !(in && in->values.p && (in->aux.p || !C.program->n_aux) && (in->pub.p || !C.n_pub))) {
     ctx->err = "prove_batch: a caller-defined circuit takes the caller's v, aux and public inputs";
     return BPP_ERR_ARG;
   }
-  const size_t sh_off = (rng_bytes + 31) & ~(size_t)31;
-  const size_t cards_bytes = C.program ? (size_t)P * nv * 32 : sh && sh->cards ? (size_t)P * k * 32 : 0;
-  const size_t aux_bytes = (size_t)P * n_aux * 32;
-  const size_t gam_bytes = sh && sh->gammas ? (size_t)P * nv * 32 : 0;
-  const size_t pub_bytes = (size_t)P * n_pub * 32;  // (public: behind the secrets, wiped with them all the same)
-  const size_t in_bytes = sh ? sh_off + cards_bytes + aux_bytes + gam_bytes + pub_bytes : rng_bytes;
-  BPP_TRY(ctx_ws(ctx, "pb_rng_in", in_bytes, &dst));
-  d_pi = (uint32_t*)((uint8_t*)dst + P * tlen);
+  if (C.deck && !in) {
+    ctx->err = "prove_batch: the deck circuit takes a caller's perms";
+    return BPP_ERR_ARG;
+  }
+  BPP_TRY(ctx_ws(ctx, "pb_gamma", (size_t)P * m * 32, (void**)&d_gamma));
+  BPP_TRY(ctx_ws(ctx, "mt_s", (size_t)P * per * 32 + 32, (void**)&d_s));
+  // one device buffer filled by one copy (the deck circuit's cards are the
+  // call's, public: "pb_deck" below)
+  const StageLayout L(P, k, in);
+  BPP_TRY(ctx_ws(ctx, "pb_rng_in", L.bytes, &dst));
   // (one staging region: a second take could recycle the arena under the first;
   // read in place instead, by k_draws through LDS, measured within noise)
   uint8_t* stage = nullptr;
-  BPP_TRY(ctx_h2d_stage(ctx, in_bytes, &stage));
-  ctx_secret_span(ctx, stage, in_bytes);  // (prove_wipe)
-  if (sh) memset(stage + rng_bytes, 0, sh_off - rng_bytes);
-  uint8_t* pis = stage + P * tlen;
+  BPP_TRY(ctx_h2d_stage(ctx, L.bytes, &stage));
+  ctx_secret_span(ctx, stage, L.bytes);  // (prove_wipe)
+  memset(stage + L.pad, 0, L.pad_bytes);  // (the alignment gap is uploaded too)
   par::for_each((P + 7) / 8, [&](size_t gi) {
     perm::Seed sd[8];
     perm::RandomDraws* d[8];
@@ -374,97 +364,62 @@ int ProveBatch::draws_upload() {
       sd[j] = seeds[std::min(8 * gi + j, P - 1)];
       d[j] = real ? &S[8 * gi + j]->d : &spare;
     }
-    perm::draw_prover_host_x8(C, sd, d, !sh);
+    perm::draw_prover_host_x8(C, sd, d, !in);
     for (size_t j = 0; j < 8 && 8 * gi + j < P; ++j) {
       const size_t i = 8 * gi + j;
-      if (C.program) {
-        S[i]->d.pi.clear();
-        memcpy(stage + sh_off + i * 32 * (size_t)nv, sh->v + i * 32 * (size_t)nv, 32 * (size_t)nv);
-        if (n_aux)
-          memcpy(stage + sh_off + cards_bytes + i * 32 * (size_t)n_aux, sh->aux + i * 32 * (size_t)n_aux,
-                 32 * (size_t)n_aux);
-        if (sh->gammas)
-          memcpy(stage + sh_off + cards_bytes + aux_bytes + i * 32 * (size_t)nv, sh->gammas + i * 32 * (size_t)nv,
-                 32 * (size_t)nv);
-        if (n_pub)
-          memcpy(stage + sh_off + cards_bytes + aux_bytes + gam_bytes + i * 32 * (size_t)n_pub,
-                 sh->pub + i * 32 * (size_t)n_pub, 32 * (size_t)n_pub);
-        if (!dev_witness) {  // (canonical Sc == its 32 bytes)
-          S[i]->cards.resize(nv);
-          memcpy(S[i]->cards.data(), sh->v + i * 32 * (size_t)nv, 32 * (size_t)nv);
-          S[i]->aux.resize(n_aux);
-          if (n_aux) memcpy(S[i]->aux.data(), sh->aux + i * 32 * (size_t)n_aux, 32 * (size_t)n_aux);
-          S[i]->pub.resize(n_pub);
-          if (n_pub) memcpy(S[i]->pub.data(), sh->pub + i * 32 * (size_t)n_pub, 32 * (size_t)n_pub);
-        }
-      } else if (sh) {
-        S[i]->d.pi.assign(sh->perms + i * k, sh->perms + (i + 1) * k);
-        if (sh->cards) memcpy(stage + sh_off + i * 32 * (size_t)k, sh->cards + i * 32 * (size_t)k, 32 * (size_t)k);
-        if (sh->gammas)
-          memcpy(stage + sh_off + cards_bytes + i * 32 * (size_t)nv, sh->gammas + i * 32 * (size_t)nv, 32 * (size_t)nv);
-        if (!dev_witness && sh->cards) {  // (canonical Sc == its 32 bytes)
-          S[i]->cards.resize(k);
-          memcpy(S[i]->cards.data(), sh->cards + i * 32 * (size_t)k, 32 * (size_t)k);
+      ProverState& st = *S[i];
+      if (in) {
+        st.d.pi.clear();
+        if (in->perms) st.d.pi.assign(in->perms + i * k, in->perms + (i + 1) * k);
+        for (const StageLayout::Rows* r : {&L.values, &L.aux, &L.gammas, &L.pub}) r->stage(stage, i);
+        if (!dev_witness) {  // the host witness's own copies (canonical Sc == its 32 bytes)
+          auto keep = [&](std::vector<Sc>& v, const ScalarRows& src) {
+            v.resize(src.p ? src.per : 0);
+            if (src.p) memcpy(v.data(), src.at(i), 32 * (size_t)src.per);
+          };
+          keep(st.cards, in->values);
+          keep(st.aux, in->aux);
+          keep(st.pub, in->pub);
         }
       }
-      perm::transcript_prefix(C, S[i]->tr);
+      perm::transcript_prefix(C, st.tr);
       // (BPP_PROVE_DEV_V=1 replaces this state with the device's, which absorbs the same)
-      if (n_pub) perm::transcript_pub(C, S[i]->tr, sh->pub + i * 32 * (size_t)n_pub);
+      if (C.n_pub) perm::transcript_pub(C, st.tr, in->pub.at(i));
       uint64_t tm[7];
       draw_template(sd[j], tm);
-      memcpy(stage + i * tlen, tm, tlen);
-      if (k) memcpy(pis + i * 4 * (size_t)k, S[i]->d.pi.data(), 4 * (size_t)k);
+      memcpy(stage + L.tmpl + i * sizeof tm, tm, sizeof tm);
+      if (k) memcpy(stage + L.pi + i * 4 * (size_t)k, st.d.pi.data(), 4 * (size_t)k);
     }
   });
-  BPP_TRY(ctx_h2d_staged(ctx, dst, stage, in_bytes));  // (pis follows the templates)
-  // (the V commitments' inputs in the same launch: values 1..k and pi + 1,
-  // gamma copies and gamma_2k / 2, into the V phase's workspaces)
+  BPP_TRY(ctx_h2d_staged(ctx, dst, stage, L.bytes));
+  const uint8_t* base = (const uint8_t*)dst;
+  d_pi = (uint32_t*)(base + L.pi);
   BPP_TRY(ctx_ws(ctx, "pv_v", (size_t)P * nv * 32, (void**)&d_v));
   BPP_TRY(ctx_ws(ctx, "pv_g", (size_t)P * nv * 32, (void**)&d_g));
   BPP_TRY(ctx_ws(ctx, "pv_gx", (size_t)P * 32, (void**)&d_gx_half));  // gamma_nv / 2 for V_nv
-  if (C.program) {
-    // the draws alone, then the V inputs from the uploaded values (and the
-    // caller's blindings over the drawn gamma_0..m_in-1)
-    const uint8_t* dsh = (const uint8_t*)dst + sh_off;
-    d_aux = (const uint32_t*)(dsh + cards_bytes);
-    d_pub = (const uint32_t*)(dsh + cards_bytes + aux_bytes + gam_bytes);
-    BPP_TRY(draws_dev(ctx, C, (uint32_t)P, (const uint64_t*)dst, seeds[0].len, per, d_gamma, d_s));
-    BPP_TRY(circuit_inputs_dev(ctx, C, (uint32_t)P, (const uint32_t*)dsh,
-                               gam_bytes ? (const uint32_t*)(dsh + cards_bytes + aux_bytes) : nullptr, d_gamma, d_v,
-                               d_g, d_gx_half));
-  } else if (C.deck) {
-    // the draws alone, then the V inputs deck[perm] from the call's deck (and
-    // the caller's blindings over the drawn gamma_0..k-1)
-    if (!sh) {
-      ctx->err = "prove_batch: the deck circuit takes a caller's perms";
-      return BPP_ERR_ARG;
-    }
+  const uint64_t* d_tmpl = (const uint64_t*)(base + L.tmpl);
+  // the seed's own witness: the V commitments' inputs (values 1..k and pi + 1,
+  // gamma copies and gamma_2k / 2) in the draws' launch
+  if (!in) return draws_dev(ctx, C, (uint32_t)P, d_tmpl, seeds[0].len, per, d_gamma, d_s, d_pi, d_v, d_g, d_gx_half);
+  // a caller's: the draws alone, then the V inputs from the uploaded rows (and
+  // the caller's blindings over the drawn gamma_0..nv-1)
+  d_aux = L.aux.dev(dst);
+  d_pub = L.pub.dev(dst);
+  const uint32_t* d_src = L.values.dev(dst);
+  if (C.deck) {
     void* d_deck = nullptr;
     BPP_TRY(ctx_ws(ctx, "pb_deck", (size_t)k * 32, &d_deck));
     BPP_TRY(ctx_h2d_const(ctx, "pb_deck", d_deck, C.cards.data(), (size_t)k * 32));
-    const uint8_t* dsh = (const uint8_t*)dst + sh_off;
-    BPP_TRY(draws_dev(ctx, C, (uint32_t)P, (const uint64_t*)dst, seeds[0].len, per, d_gamma, d_s));
-    BPP_TRY(deck_inputs_dev(ctx, C, (uint32_t)P, (const uint32_t*)d_deck, d_pi,
-                            gam_bytes ? (const uint32_t*)dsh : nullptr, d_gamma, d_v, d_g, d_gx_half));
-  } else if (sh) {
-    // the draws alone, then the V inputs from the uploaded cards and perms
-    // (and the caller's blindings over the drawn gamma_0..2k-1)
-    const uint8_t* dsh = (const uint8_t*)dst + sh_off;
-    BPP_TRY(draws_dev(ctx, C, (uint32_t)P, (const uint64_t*)dst, seeds[0].len, per, d_gamma, d_s));
-    BPP_TRY(shuffle_inputs_dev(ctx, C, (uint32_t)P, (const uint32_t*)dsh, d_pi,
-                               gam_bytes ? (const uint32_t*)(dsh + cards_bytes) : nullptr, d_gamma, d_v, d_g,
-                               d_gx_half));
-  } else {
-    BPP_TRY(draws_dev(ctx, C, (uint32_t)P, (const uint64_t*)dst, seeds[0].len, per, d_gamma, d_s, d_pi, d_v, d_g,
-                      d_gx_half));
+    d_src = (const uint32_t*)d_deck;
   }
-  return BPP_OK;
+  BPP_TRY(draws_dev(ctx, C, (uint32_t)P, d_tmpl, seeds[0].len, per, d_gamma, d_s));
+  return v_inputs_dev(ctx, C, (uint32_t)P, d_src, in->values.per, in->perms ? d_pi : nullptr, nv - in->n_perm,
+                      L.gammas.dev(dst), d_gamma, d_v, d_g, d_gx_half);
 }
 
 // V_0..V_{nv-1} of every proof (nv = 2k, or the deck circuit's k): one
 // fixed-base launch over device inputs (values 1..k, pi + 1 and gamma, written
-// by k_draws; a caller's, by k_shuffle_inputs / k_deck_inputs), encodings back
-// to the host
+// by k_draws; a caller's, by k_v_inputs), encodings back to the host
 int ProveBatch::pedersen_V() {
   HostScope hs(ctx, "pb_pedersen_V");
   const size_t nv = (size_t)P * this->nv;  // (all proofs')
@@ -485,7 +440,7 @@ int ProveBatch::pedersen_V() {
     // cards are secret full-width scalars: no bound, every digit position
     // walked whatever the value, as for gamma)
     BPP_TRY(pedersen_dev(ctx, G, d_v, d_g, nv, dev_v ? (uint32_t*)dvenc : denc, nullptr,
-                         sh ? 0 : (uint64_t)k + 1));
+                         in ? 0 : (uint64_t)k + 1));
     if (dev_v) {
       BPP_HIP(hipMemcpyAsync(denc, dvenc, nv * 32, hipMemcpyDeviceToHost, ctx->stream));
       uint32_t init[52], *h_init = nullptr;
@@ -545,7 +500,7 @@ int ProveBatch::pedersen_Vx_witness() {
     if (C.deck)
       BPP_TRY(witness_deck_dev(ctx, C, (uint32_t)P, d_v, d_vh + 8 * P, per, d_s));
     else
-      BPP_TRY(witness_dev(ctx, C, (uint32_t)P, d_pi, d_vh + 8 * P, per, d_s, sh ? d_v : nullptr));
+      BPP_TRY(witness_dev(ctx, C, (uint32_t)P, d_pi, d_vh + 8 * P, per, d_s, in ? d_v : nullptr));
   }
   uint32_t* h_p3 = nullptr;  // written in place by the kernel (ctx_zc_out)
   BPP_TRY(ctx_zc_out(ctx, "pv_p3_h", P * P3_BYTES, &h_p3));
@@ -565,7 +520,7 @@ int ProveBatch::pedersen_Vx_witness() {
                       st.pub.data());
       else if (C.deck)
         perm::witness_deck(C, st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
-      else if (sh)
+      else if (in)
         perm::witness(C, st.cards.data(), st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
       else
         perm::witness(C, st.d.pi, st.x_perm, st.vals, st.aL, st.aR, st.aO);
@@ -573,7 +528,7 @@ int ProveBatch::pedersen_Vx_witness() {
   });
   for (size_t p = 0; p < P; ++p)
     if (bad[p]) {
-      ctx->err = "circuit proof " + std::to_string((sh ? sh->first : 0) + p) + ": assert " +
+      ctx->err = "circuit proof " + std::to_string((in ? in->first : 0) + p) + ": assert " +
                  std::to_string(bad[p] - 1) + " does not hold";
       return BPP_ERR_ARG;
     }
@@ -753,25 +708,18 @@ namespace perm_impl BPP_HIDDEN {
 // round) is ONE launch sequence for the whole batch, and the per-proof host
 // work between them (transcripts, challenges, polynomial coefficients) runs
 // on a thread pool.  Outputs are identical to proving one at a time.
-// With sh, the witness is the caller's (cards, perms, optionally the V
-// blindings) instead of the seed's: no pi stream is read, the uploaded cards
-// and perms feed k_shuffle_inputs and k_witness_cards, and the V commitments
-// take full-width values; every other step is the same launch sequence.
-// With the deck circuit (perm::build_deck; sh carries perms and optional
-// blindings, no cards) the V phase commits deck[perm] over C.nv = k
-// commitments (k_deck_inputs), the witness is the one chain of k_witness_deck
-// or perm::witness_deck, and the transcripts start from the deck digest
-// (perm::transcript_prefix); the steps after V_k are the same.
-// With a caller-defined circuit (circuit::compile; sh carries v, aux and
-// optional blindings, no cards and no perms) the V phase commits the caller's
-// m_in values (k_circuit_inputs), the witness is the program interpreted by
-// k_witness_program or circuit::eval -- an assert that does not hold ends the
-// batch there with BPP_ERR_ARG -- and the transcripts start from the program's
-// digest and, with public inputs (sh->pub), the proof's own public scalars,
-// which k_witness_program reads as one more input kind; the steps after
-// V_{m_in} are the same.
+// The statement is C's and the witness the seed's or, with `in`, the caller's
+// (no pi stream is read then, and the V commitments take full-width values);
+// every step but these is the same launch sequence:
+//   statement         transcript starts  V inputs (nv)                    witness
+//   two-half, seeded  k                  k_draws: 1..k, pi + 1 (2k)       k_witness / perm::witness
+//   two-half, `in`    k                  k_v_inputs: cards, cards[perm]   k_witness_cards / perm::witness
+//   deck              deck digest        k_v_inputs: deck[perm] (k)       k_witness_deck / perm::witness_deck
+//   circuit           program digest,    k_v_inputs: v (m_in)             k_witness_program / circuit::eval;
+//                     then in->pub                                        an assert that does not hold ends
+//                                                                         the batch with BPP_ERR_ARG
 int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
-                const uint8_t* label, size_t llen, std::vector<Proof>& Ps, const ShuffleIn* sh) {
+                const uint8_t* label, size_t llen, std::vector<Proof>& Ps, const ProveInputs* in) {
   const size_t P = seeds.size();
   Ps.resize(P);
   if (!P) return BPP_OK;
@@ -780,7 +728,7 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
   // flight) keeps the sleeping wait that frees the host cores
   constexpr size_t spin_batch = 128;  // the largest batch that spins
   SyncSpin spin(ctx, P <= spin_batch ? 300u : ctx->sync_spin_us);
-  ProveBatch b(ctx, G, C, seeds, label, llen, Ps, sh);
+  ProveBatch b(ctx, G, C, seeds, label, llen, Ps, in);
   BPP_TRY(b.draws_upload());
   BPP_TRY(b.pedersen_V());
   BPP_TRY(b.pedersen_Vx_witness());
@@ -794,10 +742,9 @@ int prove_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const s
 // context inside its sub-batch thread (whose prover states are its own)
 int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const std::vector<perm::Seed>& seeds,
                     const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out, bool wipe,
-                    const ShuffleIn* sh) {
+                    const ProveInputs* in) {
   const size_t count = seeds.size();
   if (!count) return BPP_OK;
-  const uint32_t k = C.k;
   BPP_TRY(gens_cover(ctx, G, C.n_p));
   BPP_HIP(hipSetDevice(ctx->device));
   const size_t pl = perm::proof_len(C);
@@ -815,7 +762,7 @@ int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, con
     BPP_TRY(gens_points(ctx, G, &warm));
   }
   if (S <= 1) {
-    BPP_TRY(prove_batch(ctx, G, C, seeds, label, llen, Ps, sh));
+    BPP_TRY(prove_batch(ctx, G, C, seeds, label, llen, Ps, in));
   } else {
     std::vector<bpp_ctx*> kids(S);
     for (size_t s = 0; s < S; ++s) BPP_TRY(ctx_child(ctx, s, &kids[s]));
@@ -832,18 +779,8 @@ int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, con
         }
         std::vector<Proof> sub;
         std::vector<perm::Seed> part(seeds.begin() + b, seeds.begin() + e);
-        ShuffleIn shs;  // this sub-batch's slices of the caller's witness
-        if (sh) {
-          shs = {sh->cards ? sh->cards + b * 32 * (size_t)k : nullptr, sh->perms ? sh->perms + b * (size_t)k : nullptr,
-                 sh->gammas ? sh->gammas + b * 32 * (size_t)C.nv : nullptr};
-          if (C.program) {
-            shs.v = sh->v + b * 32 * (size_t)C.nv;
-            shs.aux = sh->aux ? sh->aux + b * 32 * (size_t)C.program->n_aux : nullptr;
-            shs.pub = sh->pub ? sh->pub + b * 32 * (size_t)C.n_pub : nullptr;
-          }
-          shs.first = sh->first + b;
-        }
-        rcs[s] = prove_batch(kc, G, C, part, label, llen, sub, sh ? &shs : nullptr);
+        const ProveInputs sub_in = in ? in->slice(b) : ProveInputs();  // this sub-batch's rows
+        rcs[s] = prove_batch(kc, G, C, part, label, llen, sub, in ? &sub_in : nullptr);
         if (rcs[s] == BPP_OK)
           for (size_t i = b; i < e; ++i) Ps[i] = std::move(sub[i - b]);
         if (wipe) {
@@ -876,7 +813,7 @@ int prove_batch_api(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, con
 // stack and heap, where bpp_debug_secret_residue does not look -- and ctx's
 // own wipe.
 int prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, size_t count, const uint8_t* seeds32,
-                        const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out, const ShuffleIn* sh) {
+                        const uint8_t* label, size_t llen, uint8_t* proofs_out, uint8_t* V_out, const ProveInputs* in) {
   std::vector<uint8_t> ent;
   if (!seeds32 && count) {
     ent.resize(32 * count);
@@ -888,7 +825,7 @@ int prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C,
   }
   std::vector<perm::Seed> sd(count);
   for (size_t i = 0; i < count; ++i) sd[i] = perm::Seed::bytes32(seeds32 + 32 * i);
-  const int rc = prove_batch_api(ctx, G, C, sd, label, llen, proofs_out, V_out, true, sh);
+  const int rc = prove_batch_api(ctx, G, C, sd, label, llen, proofs_out, V_out, true, in);
   if (!ent.empty()) memset(ent.data(), 0, ent.size());
   for (perm::Seed& x : sd) memset(x.b, 0, sizeof x.b);
   const int wrc = prove_wipe(ctx);

@@ -42,15 +42,19 @@ int draws_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint64_t* 
               uint32_t* d_v = nullptr, uint32_t* d_g = nullptr, uint32_t* d_gx_half = nullptr);
 void draw_template(const perm::Seed& seed, uint64_t tmpl[7]);
 
-
-// The V commitment inputs of a caller-supplied shuffle (k_shuffle_inputs),
-// after draws_dev without d_v on the same stream: d_v [P][2k] = cards then
-// cards[perm] (d_cards [P][k] canonical scalars, d_perm [P][k] u32 < k), d_g
-// [P][2k] = the drawn gamma_0..2k-1 or, when d_gammas ([P][2k]) is non-null,
-// the caller's, which then replace d_gamma's too; d_gx_half [P] = gamma_2k / 2.
-int shuffle_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_cards,
-                       const uint32_t* d_perm, const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v,
-                       uint32_t* d_g, uint32_t* d_gx_half);
+// The V commitment inputs from a caller's values (k_v_inputs), after draws_dev
+// without d_v on the same stream: d_v [P][nv] = d_src[p * src_stride + index(j)]
+// (canonical scalars; src_stride 0: one array shared by the call's proofs),
+// with index(j) = j for the first n_id entries and d_perm[p][j - n_id] ([P][nv -
+// n_id] u32, each a bijection) after them, or j throughout without a d_perm;
+// d_g [P][nv] = the drawn gamma_0..nv-1 or, when d_gammas ([P][nv]) is non-null,
+// the caller's, which then replace d_gamma's ([P][nv + 1]) too; d_gx_half [P]
+// = gamma_nv / 2.  (Two-half shuffle: cards, stride k, perms, n_id = k; deck
+// circuit: the call's deck, stride 0, perms, n_id = 0; caller-defined circuit:
+// v, stride m_in, no perm.)
+int v_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_src, uint32_t src_stride,
+                 const uint32_t* d_perm, uint32_t n_id, const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v,
+                 uint32_t* d_g, uint32_t* d_gx_half);
 
 // The witness a_L, a_R, a_O of every proof (x = x_perm [P] canonical, pi
 // [P][k]) into their slots of d_sc.  With d_vals ([P][2k] canonical, d_v
@@ -59,28 +63,15 @@ int shuffle_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const u
 int witness_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_pi, const uint32_t* d_x,
                 uint32_t per, uint32_t* d_sc, const uint32_t* d_vals = nullptr);
 
-// The deck circuit (perm.h build_deck).  deck_inputs_dev (k_deck_inputs), after
-// draws_dev without d_v on the same stream: d_v [P][k] = deck[perm] (d_deck [k]
-// canonical scalars, the call's; d_perm [P][k] u32 < k), d_g [P][k] = the drawn
-// gamma_0..k-1 or, when d_gammas ([P][k]) is non-null, the caller's, which then
-// replace d_gamma's ([P][k + 1]) too; d_gx_half [P] = gamma_k / 2.
-int deck_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_deck, const uint32_t* d_perm,
-                    const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v, uint32_t* d_g, uint32_t* d_gx_half);
-// witness_deck_dev (k_witness_deck): a_L, a_R, a_O of the one chain over d_vals
-// (d_v above) into their slots of d_sc, for k <= DECK_WITNESS_DEV_MAX -- the
-// kernel's own LDS budget, (k + 2 x 256) x 32 B <= 64 KB; the host witness
+// The deck circuit (perm.h build_deck).  witness_deck_dev (k_witness_deck):
+// a_L, a_R, a_O of the one chain over d_vals ([P][k], d_v above) into their
+// slots of d_sc, for k <= DECK_WITNESS_DEV_MAX; the host witness
 // (perm::witness_deck) beyond.
-#define DECK_WITNESS_DEV_MAX 1536u
+constexpr uint32_t DECK_WITNESS_DEV_MAX = perm::chain_witness_dev_max(1);
+int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals, const uint32_t* d_x,
+                     uint32_t per, uint32_t* d_sc);
 
-// A caller-defined circuit (host/circuit.h).  circuit_inputs_dev
-// (k_circuit_inputs), after draws_dev without d_v on the same stream: d_v
-// [P][m_in] = the caller's values (d_vals [P][m_in] canonical), d_g [P][m_in] =
-// the drawn gamma_0..m_in-1 or, when d_gammas ([P][m_in]) is non-null, the
-// caller's, which then replace d_gamma's ([P][m_in + 1]) too; d_gx_half [P] =
-// gamma_m_in / 2.
-int circuit_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
-                       const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v, uint32_t* d_g,
-                       uint32_t* d_gx_half);
+// A caller-defined circuit (host/circuit.h).
 // witness_program_dev (k_witness_program): every proof's workgroup interprets
 // C.program over its own values (d_vals [P][m_in], d_aux [P][n_aux], d_x [P],
 // canonical): a_L, a_R, a_O into their slots of d_sc, and into fail[p] (pinned
@@ -89,5 +80,3 @@ int circuit_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const u
 int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
                         const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail,
                         const uint32_t* d_pub = nullptr);  // (d_pub [P][n_pub] canonical: the public inputs)
-int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals, const uint32_t* d_x,
-                     uint32_t per, uint32_t* d_sc);

@@ -737,56 +737,36 @@ __global__ void __launch_bounds__(256) k_draws(uint32_t P, uint32_t m, uint32_t 
   sc_store(sc_out + 8 * ((size_t)p * per + pos), x);
 }
 
-// The sound create_a witness of one proof per workgroup (host restatement
-// host/perm_circuit.cpp witness, weights.rs:63-113 fixed as SURVEY Q3):
-// with d_A[i] = (i + 1) - x and d_B[i] = (pi_i + 1) - x (i < k) and their
-// inclusive prefix products A, B, gates g < k - 1 are (A[g], d_A[g+1],
-// A[g+1]), gates k-1+g' (g' < k-1) are (B[g'], d_B[g'+1], B[g'+1]), gate
-// 2k-2 is (B[k-1], -1, -B[k-1]) and gate 2k-1 is (A[k-1] - B[k-1], 1, same);
-// padding gates are zero.  a_L, a_R, a_O go straight into the A_I/A_O/S
-// scalar array.  Prefix products: per-lane chunks, then a Hillis-Steele scan
-// of the chunk products in LDS.  dynamic LDS = (2 k + 4 blockDim) x 32 B.
-//
-// CARDS (bpp_perm_prove_shuffle_batch): both chains' values are the caller's
-// cards, read from vals ([P][2k] canonical, the V commitments' inputs that
-// k_shuffle_inputs wrote: cards then cards[perm]) instead of synthesised from
-// pi; the values stay in global memory, the LDS budget is the same.
-template <bool CARDS>
-FE_INLINE void witness_body(uint32_t* lds, uint32_t k, uint32_t n_p, uint32_t per, const uint32_t* __restrict__ pi,
-                            const uint32_t* __restrict__ vals, const uint32_t* __restrict__ xs,
-                            uint32_t* __restrict__ sc_out) {
-  uint32_t* pref = lds;           // [2][k] prefix products (A then B): Montgomery, then canonical
-  uint32_t* scan = lds + 16 * k;  // [2 buffers][2][blockDim] chunk products
-  const uint32_t p = blockIdx.x, nt = blockDim.x, t = threadIdx.x;
-  const sc x = sc_load(xs + 8 * (size_t)p);
-  sc one = sc_zero();
-  one.v[0] = 1;
+// The inclusive prefix products of NC chains of k elements each, one proof
+// per workgroup: pref = lds [NC][k] holds them canonical on return (after a
+// barrier).  dd(c, i) is element i of chain c, canonical.  Per-lane chunks
+// (lane t owns elements [i0, i1) of every chain; nch lanes own any; the rest
+// an empty range), then a Hillis-Steele scan of the chunk products in the
+// ping-pong buffers [2][NC][blockDim] behind pref, then each chunk times the
+// product of the chunks before it.  dynamic LDS = perm::chain_witness_lds.
+template <uint32_t NC, class Fetch>
+FE_INLINE void chain_prefix_products(uint32_t* lds, uint32_t k, const sc& one, const Fetch& dd) {
+  uint32_t* pref = lds;
+  uint32_t* scan = lds + 8 * NC * k;
+  const uint32_t nt = blockDim.x, t = threadIdx.x;
   const sc oneR = sc_to_mont(one);
-  // lane t owns elements [i0, i1) of both chains; nch lanes own any
-  const uint32_t C = (k + nt - 1) / nt, nch = (k + C - 1) / C, i0 = t * C, i1 = min(i0 + C, k);
-  auto dd = [&](uint32_t c, uint32_t i) {  // v_i - x: v = i + 1 (A) or pi(i) + 1 (B); or the cards
-    sc v = sc_zero();
-    if constexpr (CARDS)
-      v = sc_load(vals + 8 * ((size_t)p * 2 * k + c * k + i));
-    else
-      v.v[0] = c == 0 ? i + 1 : pi[(size_t)p * k + i] + 1;
-    return sc_sub(v, x);
-  };
-  sc run[2] = {oneR, oneR};
+  const uint32_t C = (k + nt - 1) / nt, nch = (k + C - 1) / C, i0 = min(t * C, k), i1 = min(i0 + C, k);
+  sc run[NC];
+  _Pragma("unroll") for (uint32_t c = 0; c < NC; ++c) run[c] = oneR;
   for (uint32_t i = i0; i < i1; ++i)
-    _Pragma("unroll") for (uint32_t c = 0; c < 2; ++c) {
+    _Pragma("unroll") for (uint32_t c = 0; c < NC; ++c) {
       run[c] = sc_mont(run[c], sc_to_mont(dd(c, i)));
       sc_store(pref + 8 * (c * k + i), run[c]);
     }
   // inclusive Hillis-Steele scan of the chunk products, ping-pong buffers
   uint32_t cur = 0;
-  _Pragma("unroll") for (uint32_t c = 0; c < 2; ++c) sc_store(scan + 8 * (c * nt + t), run[c]);
+  _Pragma("unroll") for (uint32_t c = 0; c < NC; ++c) sc_store(scan + 8 * (c * nt + t), run[c]);
   __syncthreads();
   for (uint32_t d = 1; d < nch; d <<= 1) {
-    const uint32_t* src = scan + 16 * nt * cur;
-    uint32_t* dst = scan + 16 * nt * (cur ^ 1);
+    const uint32_t* src = scan + 8 * NC * nt * cur;
+    uint32_t* dst = scan + 8 * NC * nt * (cur ^ 1);
     if (t < nch)
-      _Pragma("unroll") for (uint32_t c = 0; c < 2; ++c) {
+      _Pragma("unroll") for (uint32_t c = 0; c < NC; ++c) {
         sc a = sc_load(src + 8 * (c * nt + t));
         if (t >= d) a = sc_mont(sc_load(src + 8 * (c * nt + t - d)), a);
         sc_store(dst + 8 * (c * nt + t), a);
@@ -797,13 +777,52 @@ FE_INLINE void witness_body(uint32_t* lds, uint32_t k, uint32_t n_p, uint32_t pe
   // canonical prefixes: mont(e, P) for the canonical product e of the
   // earlier chunks and Montgomery P is e P canonical (one multiply each)
   if (t < nch)
-    _Pragma("unroll") for (uint32_t c = 0; c < 2; ++c) {
-      const sc e = t > 0 ? sc_from_mont(sc_load(scan + 16 * nt * cur + 8 * (c * nt + t - 1))) : one;
+    _Pragma("unroll") for (uint32_t c = 0; c < NC; ++c) {
+      const sc e = t > 0 ? sc_from_mont(sc_load(scan + 8 * NC * nt * cur + 8 * (c * nt + t - 1))) : one;
       for (uint32_t i = i0; i < i1; ++i) sc_store(pref + 8 * (c * k + i), sc_mont(e, sc_load(pref + 8 * (c * k + i))));
     }
   __syncthreads();
+}
+
+// gate g's a_L, a_R, a_O into their slots of the proof's A_I/A_O/S scalars o
+FE_INLINE void witness_gate_store(uint32_t* o, uint32_t n_p, uint32_t g, const sc& aL, const sc& aR, const sc& aO) {
+  sc_store(o + 8 * (1 + g), aL);
+  sc_store(o + 8 * (1 + n_p + g), aR);
+  sc_store(o + 8 * (2 + 2 * n_p + g), aO);
+}
+
+// The sound create_a witness of one proof per workgroup (host restatement
+// host/perm_circuit.cpp witness, weights.rs:63-113 fixed as SURVEY Q3):
+// with d_A[i] = (i + 1) - x and d_B[i] = (pi_i + 1) - x (i < k) and their
+// inclusive prefix products A, B (chain_prefix_products<2>), gates g < k - 1
+// are (A[g], d_A[g+1], A[g+1]), gates k-1+g' (g' < k-1) are (B[g'], d_B[g'+1],
+// B[g'+1]), gate 2k-2 is (B[k-1], -1, -B[k-1]) and gate 2k-1 is (A[k-1] -
+// B[k-1], 1, same); padding gates are zero.  a_L, a_R, a_O go straight into
+// the A_I/A_O/S scalar array.
+//
+// CARDS (bpp_perm_prove_shuffle_batch): both chains' values are the caller's
+// cards, read from vals ([P][2k] canonical, the V commitments' inputs that
+// k_v_inputs wrote: cards then cards[perm]) instead of synthesised from pi;
+// the values stay in global memory, the LDS budget is the same.
+template <bool CARDS>
+FE_INLINE void witness_body(uint32_t* lds, uint32_t k, uint32_t n_p, uint32_t per, const uint32_t* __restrict__ pi,
+                            const uint32_t* __restrict__ vals, const uint32_t* __restrict__ xs,
+                            uint32_t* __restrict__ sc_out) {
+  const uint32_t p = blockIdx.x, nt = blockDim.x, t = threadIdx.x;
+  const sc x = sc_load(xs + 8 * (size_t)p);
+  sc one = sc_zero();
+  one.v[0] = 1;
+  auto dd = [&](uint32_t c, uint32_t i) {  // v_i - x: v = i + 1 (A) or pi(i) + 1 (B); or the cards
+    sc v = sc_zero();
+    if constexpr (CARDS)
+      v = sc_load(vals + 8 * ((size_t)p * 2 * k + c * k + i));
+    else
+      v.v[0] = c == 0 ? i + 1 : pi[(size_t)p * k + i] + 1;
+    return sc_sub(v, x);
+  };
+  chain_prefix_products<2>(lds, k, one, dd);
   uint32_t* o = sc_out + 8 * (size_t)p * per;
-  auto pr = [&](uint32_t c, uint32_t i) { return sc_load(pref + 8 * (c * k + i)); };
+  auto pr = [&](uint32_t c, uint32_t i) { return sc_load(lds + 8 * (c * k + i)); };
   for (uint32_t g = t; g < n_p; g += nt) {
     sc aL = sc_zero(), aR = sc_zero(), aO = sc_zero();
     if (g + 1 < k) {
@@ -824,9 +843,7 @@ FE_INLINE void witness_body(uint32_t* lds, uint32_t k, uint32_t n_p, uint32_t pe
       aR = one;
       aO = aL;
     }
-    sc_store(o + 8 * (1 + g), aL);
-    sc_store(o + 8 * (1 + n_p + g), aR);
-    sc_store(o + 8 * (2 + 2 * n_p + g), aO);
+    witness_gate_store(o, n_p, g, aL, aR, aO);
   }
 }
 
@@ -846,92 +863,64 @@ __global__ void __launch_bounds__(256) k_witness_cards(uint32_t k, uint32_t n_p,
 // The deck circuit's witness (perm.h build_deck; host restatement
 // witness_deck), one proof per workgroup, ONE chain: with d[i] = vals[p][i] -
 // x (vals [P][k] canonical: the values the V phase commits, deck[perm], written
-// by k_deck_inputs) and their inclusive prefix products A, gate g < k - 1 is
-// (A[g], d[g+1], A[g+1]); padding gates are zero.  The prefix-product scan of
-// witness_body: per-lane chunks, then a Hillis-Steele scan of the chunk
-// products in LDS.  dynamic LDS = (k + 2 blockDim) x 32 B -- half the
-// two-chain kernel's -- so at 256 lanes the device witness reaches k <= 1536
-// ((1536 + 512) x 32 B = 64 KB; DECK_WITNESS_DEV_MAX); the host witness beyond.
+// by k_v_inputs) and their inclusive prefix products A
+// (chain_prefix_products<1>), gate g < k - 1 is (A[g], d[g+1], A[g+1]); padding
+// gates are zero.  Half the two-chain kernels' LDS, so the device witness
+// reaches twice their k (perm::chain_witness_dev_max); the host witness beyond.
 __global__ void __launch_bounds__(256) k_witness_deck(uint32_t k, uint32_t n_p, uint32_t per,
                                                      const uint32_t* __restrict__ vals,
                                                      const uint32_t* __restrict__ xs, uint32_t* __restrict__ sc_out) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  uint32_t* pref = lds;          // [k] prefix products: Montgomery, then canonical
-  uint32_t* scan = lds + 8 * k;  // [2 buffers][blockDim] chunk products
   const uint32_t p = blockIdx.x, nt = blockDim.x, t = threadIdx.x;
   const sc x = sc_load(xs + 8 * (size_t)p);
   sc one = sc_zero();
   one.v[0] = 1;
-  const sc oneR = sc_to_mont(one);
   const uint32_t* vp = vals + 8 * (size_t)p * k;
-  auto dd = [&](uint32_t i) { return sc_sub(sc_load(vp + 8 * (size_t)i), x); };
-  // lane t owns elements [i0, i1); nch lanes own any
-  const uint32_t C = (k + nt - 1) / nt, nch = (k + C - 1) / C, i0 = min(t * C, k), i1 = min(i0 + C, k);
-  sc run = oneR;
-  for (uint32_t i = i0; i < i1; ++i) {
-    run = sc_mont(run, sc_to_mont(dd(i)));
-    sc_store(pref + 8 * i, run);
-  }
-  uint32_t cur = 0;
-  sc_store(scan + 8 * t, run);
-  __syncthreads();
-  for (uint32_t d = 1; d < nch; d <<= 1) {
-    const uint32_t* src = scan + 8 * nt * cur;
-    uint32_t* dst = scan + 8 * nt * (cur ^ 1);
-    if (t < nch) {
-      sc a = sc_load(src + 8 * t);
-      if (t >= d) a = sc_mont(sc_load(src + 8 * (t - d)), a);
-      sc_store(dst + 8 * t, a);
-    }
-    cur ^= 1;
-    __syncthreads();
-  }
-  // canonical prefixes: mont(e, P) for the canonical product e of the earlier
-  // chunks and Montgomery P is e P canonical
-  if (t < nch) {
-    const sc e = t > 0 ? sc_from_mont(sc_load(scan + 8 * nt * cur + 8 * (t - 1))) : one;
-    for (uint32_t i = i0; i < i1; ++i) sc_store(pref + 8 * i, sc_mont(e, sc_load(pref + 8 * i)));
-  }
-  __syncthreads();
+  auto dd = [&](uint32_t, uint32_t i) { return sc_sub(sc_load(vp + 8 * (size_t)i), x); };
+  chain_prefix_products<1>(lds, k, one, dd);
   uint32_t* o = sc_out + 8 * (size_t)p * per;
   for (uint32_t g = t; g < n_p; g += nt) {
     sc aL = sc_zero(), aR = sc_zero(), aO = sc_zero();
     if (g + 1 < k) {
-      aL = sc_load(pref + 8 * g);
-      aR = dd(g + 1);
-      aO = sc_load(pref + 8 * (g + 1));
+      aL = sc_load(lds + 8 * g);
+      aR = dd(0, g + 1);
+      aO = sc_load(lds + 8 * (g + 1));
     }
-    sc_store(o + 8 * (1 + g), aL);
-    sc_store(o + 8 * (1 + n_p + g), aR);
-    sc_store(o + 8 * (2 + 2 * n_p + g), aO);
+    witness_gate_store(o, n_p, g, aL, aR, aO);
   }
 }
 
-// The V phase's inputs of a deck proof (bpp_deck_prove_batch), one lane per
-// commitment input (P x m lanes, m = k + 1, after k_draws with v = nullptr on
-// the same stream): v[p][i] = deck[perm[p][i]] (i < k; the deck [k] is the
-// call's, shared by its proofs; perm is a bijection on [0, k), checked by the
-// entry point before any device work -- the index is clamped all the same),
-// g[p][i] = the blinding of V_i: the drawn gamma[p][i], or the caller's
-// gammas[p][i] ([P][k]), which then also replaces gamma[p][i] (k_poly_coef
-// reads it for tau_x); gx_half[p] = gamma_k / 2 (always drawn).
-__global__ void __launch_bounds__(256) k_deck_inputs(uint32_t P, uint32_t k, const uint32_t* __restrict__ deck,
-                                                    const uint32_t* __restrict__ perm,
-                                                    const uint32_t* __restrict__ gammas,
-                                                    uint32_t* __restrict__ gamma, uint32_t* __restrict__ v,
-                                                    uint32_t* __restrict__ g, uint32_t* __restrict__ gx_half) {
-  const uint32_t m = k + 1;
+// The V phase's inputs from a caller's values, one lane per commitment input
+// (P x m lanes, m = nv + 1, after k_draws with v = nullptr on the same stream):
+// v[p][j] = src[p * src_stride + index(j)] for j < nv, with index(j) = j for the
+// n_id leading identity entries and perm[p][j - n_id] after them (perm [P][nv -
+// n_id], each a bijection checked by the entry point before any device work --
+// the index is clamped all the same; perm = nullptr: the identity).
+//   two-half shuffle  src = cards [P][k], stride k, perm, n_id = k: cards, cards[perm]
+//   deck circuit      src = the call's deck [k], stride 0, perm, n_id = 0: deck[perm]
+//   circuit           src = the caller's v [P][m_in], stride m_in, no perm
+// g[p][j] = the blinding of V_j: the drawn gamma[p][j], or the caller's
+// gammas[p][j] ([P][nv]), which then also replaces gamma[p][j] (k_poly_coef
+// reads it for tau_x); gx_half[p] = gamma_nv / 2 (always drawn; V_nv is
+// committed with halved scalars).  src, gammas, gamma [P][m]: canonical.
+__global__ void __launch_bounds__(256) k_v_inputs(uint32_t P, uint32_t nv, uint32_t n_id,
+                                                 const uint32_t* __restrict__ src, uint32_t src_stride,
+                                                 const uint32_t* __restrict__ perm,
+                                                 const uint32_t* __restrict__ gammas, uint32_t* __restrict__ gamma,
+                                                 uint32_t* __restrict__ v, uint32_t* __restrict__ g,
+                                                 uint32_t* __restrict__ gx_half) {
+  const uint32_t m = nv + 1, np = nv - n_id;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)P * m) return;
   const uint32_t p = (uint32_t)(t / m), j = (uint32_t)(t % m);
   uint32_t* gm = gamma + 8 * ((size_t)p * m + j);
-  if (j == k) {
+  if (j == nv) {
     sc_store(gx_half + 8 * (size_t)p, sc_half(sc_load(gm)));
     return;
   }
-  const uint32_t src = min(perm[(size_t)p * k + j], k - 1);
-  const size_t o = 8 * ((size_t)p * k + j);
-  sc_store(v + o, sc_load(deck + 8 * (size_t)src));
+  const uint32_t idx = j < n_id || !perm ? j : min(perm[(size_t)p * np + (j - n_id)], np - 1);
+  const size_t o = 8 * ((size_t)p * nv + j);
+  sc_store(v + o, sc_load(src + 8 * ((size_t)p * src_stride + idx)));
   sc x;
   if (gammas) {
     x = sc_load(gammas + o);
@@ -942,13 +931,14 @@ __global__ void __launch_bounds__(256) k_deck_inputs(uint32_t P, uint32_t k, con
   sc_store(g + o, x);
 }
 
-int deck_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_deck, const uint32_t* d_perm,
-                    const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v, uint32_t* d_g, uint32_t* d_gx_half) {
+int v_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_src, uint32_t src_stride,
+                 const uint32_t* d_perm, uint32_t n_id, const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v,
+                 uint32_t* d_g, uint32_t* d_gx_half) {
   if (!P) return BPP_OK;
   const size_t nt = (size_t)P * C.m;
-  hipLaunchKernelGGL(k_deck_inputs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, P, C.k, d_deck,
-                     d_perm, d_gammas, d_gamma, d_v, d_g, d_gx_half);
-  return ctx_check_launch(ctx, "k_deck_inputs");
+  hipLaunchKernelGGL(k_v_inputs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, P, C.nv, n_id, d_src,
+                     src_stride, d_perm, d_gammas, d_gamma, d_v, d_g, d_gx_half);
+  return ctx_check_launch(ctx, "k_v_inputs");
 }
 
 int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals, const uint32_t* d_x,
@@ -958,50 +948,9 @@ int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uin
     ctx->err = "witness_deck_dev: k beyond the kernel's LDS budget";
     return BPP_ERR_LEN;
   }
-  const size_t lds = ((size_t)C.k + 2 * 256) * 32;
-  hipLaunchKernelGGL(k_witness_deck, dim3(P), dim3(256), lds, ctx->stream, C.k, C.n_p, per, d_vals, d_x, d_sc);
+  hipLaunchKernelGGL(k_witness_deck, dim3(P), dim3(perm::chain_witness_lanes(1, C.k)),
+                     perm::chain_witness_lds(1, C.k), ctx->stream, C.k, C.n_p, per, d_vals, d_x, d_sc);
   return ctx_check_launch(ctx, "k_witness_deck");
-}
-
-// The V phase's inputs of a caller-defined circuit (bpp_circuit_prove_batch),
-// one lane per commitment input (P x m lanes, m = m_in + 1, after k_draws with
-// v = nullptr on the same stream): v[p][j] = vals[p][j] (j < m_in), g[p][j] =
-// the blinding of V_j: the drawn gamma[p][j], or the caller's gammas[p][j]
-// ([P][m_in]), which then also replaces gamma[p][j] (k_poly_coef reads it for
-// tau_x); gx_half[p] = gamma_m_in / 2 (always drawn).
-__global__ void __launch_bounds__(256) k_circuit_inputs(uint32_t P, uint32_t m_in, const uint32_t* __restrict__ vals,
-                                                       const uint32_t* __restrict__ gammas,
-                                                       uint32_t* __restrict__ gamma, uint32_t* __restrict__ v,
-                                                       uint32_t* __restrict__ g, uint32_t* __restrict__ gx_half) {
-  const uint32_t m = m_in + 1;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (size_t)P * m) return;
-  const uint32_t p = (uint32_t)(t / m), j = (uint32_t)(t % m);
-  uint32_t* gm = gamma + 8 * ((size_t)p * m + j);
-  if (j == m_in) {
-    sc_store(gx_half + 8 * (size_t)p, sc_half(sc_load(gm)));
-    return;
-  }
-  const size_t o = 8 * ((size_t)p * m_in + j);
-  sc_store(v + o, sc_load(vals + o));
-  sc x;
-  if (gammas) {
-    x = sc_load(gammas + o);
-    sc_store(gm, x);
-  } else {
-    x = sc_load(gm);
-  }
-  sc_store(g + o, x);
-}
-
-int circuit_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
-                       const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v, uint32_t* d_g,
-                       uint32_t* d_gx_half) {
-  if (!P) return BPP_OK;
-  const size_t nt = (size_t)P * C.m;
-  hipLaunchKernelGGL(k_circuit_inputs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, P, C.nv, d_vals,
-                     d_gammas, d_gamma, d_v, d_g, d_gx_half);
-  return ctx_check_launch(ctx, "k_circuit_inputs");
 }
 
 // The witness of a caller-defined circuit (host/circuit.h; host restatement
@@ -1173,58 +1122,11 @@ int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const 
   return ctx_check_launch(ctx, stage ? "k_witness_program" : "k_witness_program_global");
 }
 
-// The V phase's inputs of a caller-supplied shuffle, one lane per commitment
-// input (P x m lanes, after k_draws with v = nullptr on the same stream):
-// v[p][i] = cards[p][i], v[p][k + i] = cards[p][perm[p][i]] (i < k; perm is a
-// bijection on [0, k), checked by the entry point before any device work --
-// the index is clamped all the same), g[p][j] = the blinding of V_j: the
-// drawn gamma[p][j], or the caller's gammas[p][j], which then also replaces
-// gamma[p][j] (k_poly_coef reads it for tau_x); gx_half[p] = gamma_2k / 2
-// (always drawn).  cards [P][k], gammas [P][2k], gamma [P][m]: canonical.
-__global__ void __launch_bounds__(256) k_shuffle_inputs(uint32_t P, uint32_t k, uint32_t m,
-                                                       const uint32_t* __restrict__ cards,
-                                                       const uint32_t* __restrict__ perm,
-                                                       const uint32_t* __restrict__ gammas,
-                                                       uint32_t* __restrict__ gamma, uint32_t* __restrict__ v,
-                                                       uint32_t* __restrict__ g, uint32_t* __restrict__ gx_half) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (size_t)P * m) return;
-  const uint32_t p = (uint32_t)(t / m), j = (uint32_t)(t % m);
-  uint32_t* gm = gamma + 8 * ((size_t)p * m + j);
-  if (j == 2 * k) {
-    sc_store(gx_half + 8 * (size_t)p, sc_half(sc_load(gm)));
-    return;
-  }
-  const uint32_t src = j < k ? j : min(perm[(size_t)p * k + (j - k)], k - 1);
-  const size_t o = 8 * ((size_t)p * 2 * k + j);
-  sc_store(v + o, sc_load(cards + 8 * ((size_t)p * k + src)));
-  sc x;
-  if (gammas) {
-    x = sc_load(gammas + o);
-    sc_store(gm, x);
-  } else {
-    x = sc_load(gm);
-  }
-  sc_store(g + o, x);
-}
-
-int shuffle_inputs_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_cards,
-                       const uint32_t* d_perm, const uint32_t* d_gammas, uint32_t* d_gamma, uint32_t* d_v,
-                       uint32_t* d_g, uint32_t* d_gx_half) {
-  if (!P) return BPP_OK;
-  const size_t nt = (size_t)P * C.m;
-  hipLaunchKernelGGL(k_shuffle_inputs, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, P, C.k, C.m,
-                     d_cards, d_perm, d_gammas, d_gamma, d_v, d_g, d_gx_half);
-  return ctx_check_launch(ctx, "k_shuffle_inputs");
-}
-
 int witness_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_pi, const uint32_t* d_x,
                 uint32_t per, uint32_t* d_sc, const uint32_t* d_vals) {
   if (!P) return BPP_OK;
-  // (256 lanes while the prefixes and both scan buffers fit 64 KB, else 128:
-  // perm_prove.hip's dev_witness bound (2 k + 512) x 32 B)
-  const unsigned nt = (2 * (size_t)C.k + 4 * 256) * 32 <= 64 * 1024 ? 256 : 128;
-  const size_t lds = (2 * (size_t)C.k + 4 * nt) * 32;
+  const unsigned nt = perm::chain_witness_lanes(2, C.k);
+  const size_t lds = perm::chain_witness_lds(2, C.k);
   if (d_vals) {
     {
       ProfScope ps(ctx, "witness_cards");

@@ -3,7 +3,8 @@ statement it restates: two_half_shuffle(52) through bpp_circuit_prove_batch /
 bpp_circuit_verify_batch against bpp_perm_prove_shuffle_batch /
 bpp_perm_verify_batch at 52 cards -- the same statement, n_p and m, so the only
 differences are the interpreted witness (k_witness_program for k_witness_cards),
-the input kernel and the "circuit" digest in the transcript.
+k_v_inputs' arguments (v as it stands, for cards and cards[perm]) and the
+"circuit" digest in the transcript.
 
     python tools/circuit_cost.py [--windows 5] [--out profiles/circuit_cost_ab.json]
 
