@@ -24,7 +24,7 @@ from ._lib import BppError, check
 MSM_INFLIGHT = 4  # BPP_MSM_INFLIGHT (include/bpperm.h)
 
 __all__ = ["Context", "PointTable", "BppError", "vartime_multiscalar_mul", "default_context", "VerifyJob",
-           "partials_is_identity", "Circuit", "CircuitProver"]
+           "partials_is_identity", "Circuit", "CircuitProver", "verify_groups"]
 
 
 def _buf(b: bytes):
@@ -861,12 +861,16 @@ class CircuitProver:
         self.proof_len = self.circuit.proof_len
         self.m = self.circuit.m
 
-    def _pub(self, pub, count: int):
+    def _pub_bytes(self, pub, count: int) -> bytes:
         """pub[p] = the n_pub public inputs of proof p (or each proof's joined)
         -> the joined bytes of the _pub entry points."""
         ub = b"".join(x if isinstance(x, (bytes, bytearray)) else _join(x, 32, "pub") for x in pub)
         if len(ub) != 32 * self.circuit.n_pub * count:
             raise ValueError("pub: expected n_pub scalars of 32 bytes per proof")
+        return ub
+
+    def _pub(self, pub, count: int):
+        ub = self._pub_bytes(pub, count)
         return _buf(ub) if ub else None
 
     def prove_batch(self, v, aux=None, seeds32: bytes | None = None, gammas=None, raw: bool = False,
@@ -955,6 +959,67 @@ class CircuitProver:
         if rc != 6:
             check(rc, "bpp_circuit_verify_batch_each", self.ctx.h)
         return [b != 0 for b in ok.raw[:count]]
+
+
+VERIFY_GROUPS_MAX = 16  # BPP_VERIFY_GROUPS_MAX (include/bpperm.h)
+
+
+class _VerifyGroupC(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("k", C.c_uint32), ("deck", C.c_char_p), ("circuit", C.c_void_p),
+                ("label", C.c_char_p), ("label_len", C.c_size_t), ("count", C.c_size_t), ("proofs", C.c_char_p),
+                ("V", C.c_char_p), ("pub", C.c_char_p)]
+
+
+def verify_groups(gens: Gens, groups, each: bool = False, ctx: "Context | None" = None):
+    """Proofs of different statements verified in one call with one MSM
+    (bpp_verify_groups, bpp_verify_groups_each).  groups: a sequence of
+    (prover, proofs, Vs) or (prover, proofs, Vs, pub), prover a PermProver,
+    DeckProver or CircuitProver -- it supplies the statement and the label --
+    and proofs / Vs in the two forms its verify_batch takes; pub as
+    CircuitProver.verify_batch takes it.  Returns True if every proof
+    verifies; with each=True one list of per-proof verdicts per group, what
+    prover.verify(proof, V[, pub]) returns for each."""
+    ctx = ctx or gens.ctx
+    arr = (_VerifyGroupC * max(len(groups), 1))()
+    keep = []  # the buffers the structs point into, alive across the call
+    counts = []
+    for i, grp in enumerate(groups):
+        prover, proofs, Vs = grp[0], grp[1], grp[2]
+        pub = grp[3] if len(grp) > 3 else None
+        pb, vb, count = prover._batch_buffers(proofs, Vs)
+        g = arr[i]
+        g.label, g.label_len, g.count = prover.label or None, len(prover.label), count
+        g.proofs, g.V = pb or None, vb or None
+        if isinstance(prover, CircuitProver):
+            g.kind, g.circuit = 2, prover.circuit.h
+            if pub is not None:
+                ub = prover._pub_bytes(pub, count)
+                g.pub = ub or None
+                keep.append(ub)
+        elif isinstance(prover, DeckProver):
+            g.kind, g.k, g.deck = 1, prover.k, prover.deck
+        elif isinstance(prover, PermProver):
+            g.kind, g.k = 0, prover.k
+        else:
+            raise TypeError("verify_groups: prover must be a PermProver, DeckProver or CircuitProver")
+        keep += [prover, pb, vb]
+        counts.append(count)
+    if not each:
+        rc = ctx.lib.bpp_verify_groups(ctx.h, gens.h, arr, len(groups))
+        if rc == 6:
+            return False
+        check(rc, "bpp_verify_groups", ctx.h)
+        return True
+    total = sum(counts)
+    ok = C.create_string_buffer(max(total, 1))
+    rc = ctx.lib.bpp_verify_groups_each(ctx.h, gens.h, arr, len(groups), ok)
+    if rc != 6:
+        check(rc, "bpp_verify_groups_each", ctx.h)
+    flags, out, o = ok.raw, [], 0
+    for n in counts:
+        out.append([b != 0 for b in flags[o:o + n]])
+        o += n
+    return out
 
 
 class VerifyJob:

@@ -117,6 +117,8 @@ SIGNATURES = {
     "bpp_circuit_verify_pub": (i32, [vp, vp, vp, vp, sz, vp, sz, vp, vp]),
     "bpp_circuit_verify_batch_pub": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, vp]),
     "bpp_circuit_verify_batch_each_pub": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]),
+    "bpp_verify_groups": (i32, [vp, vp, vp, sz]),
+    "bpp_verify_groups_each": (i32, [vp, vp, vp, sz, vp]),
     "bpp_perm_verify_begin": (i32, [u32, sz, vp, sz, vp, vp, vp, C.POINTER(vp)]),
     "bpp_perm_verify_begin_dev": (i32, [vp, u32, sz, vp, sz, vp, vp, vp, C.POINTER(vp)]),
     "bpp_perm_verify_terms": (i32, [vp, C.POINTER(sz)]),

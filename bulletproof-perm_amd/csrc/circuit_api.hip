@@ -14,24 +14,7 @@ static_assert(circuit::OK == BPP_OK && circuit::ERR_ARG == BPP_ERR_ARG && circui
                   circuit::ERR_NONCANONICAL == BPP_ERR_NONCANONICAL && circuit::SIDE_LC == BPP_SIDE_LC,
               "host/circuit.h restates these");
 
-struct bpp_circuit {
-  perm::Circuit C;  // (C.program: the compiled program)
-};
-
 namespace {
-
-// "every public scalar of the call is canonical", and a circuit with public
-// inputs was given them: what the _pub entry points check before any device
-// work (bad: the first proof with a scalar >= l)
-int pub_check(const bpp_circuit* c, size_t count, const uint8_t* pub, size_t* bad) {
-  const uint32_t n_pub = c->C.n_pub;
-  if (!n_pub || !count) return BPP_OK;
-  if (!pub) return BPP_ERR_ARG;
-  std::vector<int> nc(count, BPP_OK);
-  check_canonical(pub, n_pub, count, nc);
-  *bad = first_bad(nc);
-  return *bad == SIZE_MAX ? BPP_OK : BPP_ERR_NONCANONICAL;
-}
 
 // the entry points without `pub` take circuits without public inputs only
 int no_pub(bpp_ctx* ctx, const bpp_circuit* c) {

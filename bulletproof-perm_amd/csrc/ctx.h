@@ -94,6 +94,15 @@ struct bpp_ctx {
   // one event per upload chunk (verify_begin_dev: each chunk's points are
   // decompressed as soon as its copy lands)
   std::vector<hipEvent_t> vj_ev_chunk;
+  // the child the decompression runs on: VJ_CHILD, behind the MSM slots'
+  // children; 0 on a group context, which has no other child
+  size_t vj_child = BPP_MSM_INFLIGHT;
+  // bpp_verify_groups: one context per group of a mixed batch (own stream,
+  // "vj_*" / "vs_*" / "pv_s" workspaces and decompression child), created on
+  // first use (ctx_group) and kept; vg_ev (on a group context) = the group's
+  // scalars and points are ready, waited for by the parent's stream
+  std::vector<bpp_ctx*> groups;
+  hipEvent_t vg_ev = nullptr;
   // bpp_msm_submit_host: the uploaded scalars of this (child) context's MSM,
   // copied on the parent's upload streams (up_stream, created on first use;
   // one per chunk of the copy) and signalled to this context's stream by
@@ -234,6 +243,17 @@ struct SyncSpin {
 };
 // i-th child context of ctx (created on first use, destroyed with ctx).
 int ctx_child(bpp_ctx* ctx, size_t i, bpp_ctx** out);
+// i-th group context of ctx (bpp_verify_groups; created on first use,
+// destroyed with ctx): a list of its own, so that the MSM slots' children
+// are not created for it, and a group context's only child is the one its
+// decompression runs on (vj_child = 0).
+int ctx_group(bpp_ctx* ctx, size_t i, bpp_ctx** out);
+// "everything queued on ctx's stream is known to have completed" (another
+// stream that waited for it was synchronised): what ctx_sync clears, no wait
+inline void ctx_mark_idle(bpp_ctx* ctx) {
+  ctx->zc_live.clear();
+  ctx->stage_used = 0;
+}
 
 // Profiling brackets around a launch on ctx->stream.
 struct ProfScope {

@@ -345,6 +345,22 @@ int ctx_child(bpp_ctx* ctx, size_t i, bpp_ctx** out) {
   return BPP_OK;
 }
 
+int ctx_group(bpp_ctx* ctx, size_t i, bpp_ctx** out) {
+  while (ctx->groups.size() <= i) {
+    bpp_ctx* c = nullptr;
+    const int rc = bpp_ctx_create(ctx->device, &c);
+    if (rc) {
+      ctx->err = "creating a group context failed";
+      return rc;
+    }
+    c->vj_child = 0;
+    c->prof = ctx->prof;
+    ctx->groups.push_back(c);
+  }
+  *out = ctx->groups[i];
+  return BPP_OK;
+}
+
 int ctx_check_launch(bpp_ctx* ctx, const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -380,7 +396,9 @@ ProfScope::~ProfScope() {
 
 static void prof_resolve(bpp_ctx* ctx) {
   // stages that ran on child streams count under the parent
-  for (bpp_ctx* c : ctx->children) {
+  std::vector<bpp_ctx*> kids = ctx->children;
+  kids.insert(kids.end(), ctx->groups.begin(), ctx->groups.end());
+  for (bpp_ctx* c : kids) {
     prof_resolve(c);
     for (auto& kv : c->prof_acc) {
       auto& acc = ctx->prof_acc[kv.first];
@@ -491,6 +509,7 @@ int bpp_ctx_create(int device, bpp_ctx** out) {
 void bpp_ctx_destroy(bpp_ctx* ctx) {
   if (!ctx) return;
   for (bpp_ctx* c : ctx->children) bpp_ctx_destroy(c);
+  for (bpp_ctx* c : ctx->groups) bpp_ctx_destroy(c);
   hipSetDevice(ctx->device);
   hipStreamSynchronize(ctx->stream);
   for (auto& kv : ctx->ws)
@@ -516,6 +535,7 @@ void bpp_ctx_destroy(bpp_ctx* ctx) {
       hipStreamDestroy(s);
     }
   if (ctx->vj_ev_dec) hipEventDestroy(ctx->vj_ev_dec);
+  if (ctx->vg_ev) hipEventDestroy(ctx->vg_ev);
   for (auto e : ctx->vj_ev_chunk) hipEventDestroy(e);
   for (auto& sl : ctx->msm_slot)
     if (sl.done) hipEventDestroy(sl.done);
@@ -532,6 +552,7 @@ int bpp_ctx_profile(bpp_ctx* ctx, int enable) {
     if (!ctx) return BPP_ERR_ARG;
     ctx->prof = enable != 0;
     for (bpp_ctx* c : ctx->children) bpp_ctx_profile(c, enable);
+    for (bpp_ctx* c : ctx->groups) bpp_ctx_profile(c, enable);
     return BPP_OK;
   });
 }
@@ -548,7 +569,9 @@ int bpp_ctx_profile_get(bpp_ctx* ctx, const char* stage, double* ms, uint64_t* l
 }
 
 static void work_resolve(bpp_ctx* ctx) {
-  for (bpp_ctx* c : ctx->children) {
+  std::vector<bpp_ctx*> kids = ctx->children;
+  kids.insert(kids.end(), ctx->groups.begin(), ctx->groups.end());
+  for (bpp_ctx* c : kids) {
     work_resolve(c);
     for (auto& kv : c->work) ctx->work[kv.first] += kv.second;
     c->work.clear();

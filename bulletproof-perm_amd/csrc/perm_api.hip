@@ -8,9 +8,6 @@
 
 using namespace perm_impl;
 
-// "k is in range"
-static bool k_in_range(uint32_t k) { return k >= 2 && k <= (1u << 20); }
-
 extern "C" {
 
 size_t bpp_perm_proof_len(uint32_t k) { return k_in_range(k) ? perm::proof_len(k) : 0; }
@@ -83,17 +80,6 @@ int bpp_perm_prove_shuffle_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, si
 
 // --- the deck circuit (perm.h build_deck): V_0..V_{k-1} commit to a
 // permutation of the call's PUBLIC deck
-
-// "every deck card is a canonical scalar" (deck == nullptr: 1..k)
-static int deck_canonical(bpp_ctx* ctx, uint32_t k, const uint8_t* deck) {
-  Sc t;
-  for (uint32_t i = 0; deck && i < k; ++i)
-    if (!hsc::from_canonical(t, deck + 32 * (size_t)i)) {
-      if (ctx) ctx->err = "deck card " + std::to_string(i) + " is not a canonical scalar";
-      return BPP_ERR_NONCANONICAL;
-    }
-  return BPP_OK;
-}
 
 size_t bpp_deck_proof_len(uint32_t k) {
   if (!k_in_range(k)) return 0;

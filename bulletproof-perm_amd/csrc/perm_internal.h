@@ -210,6 +210,11 @@ struct bpp_verify_job {
   const uint32_t* d_pub = nullptr;
 };
 
+// A compiled caller-defined circuit (circuit_api.hip bpp_circuit_create_pub).
+struct bpp_circuit {
+  perm::Circuit C;  // (C.program: the compiled program)
+};
+
 namespace perm_impl BPP_HIDDEN {
 
 // --- prover (perm_prove.hip)
@@ -237,6 +242,17 @@ int verify_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const 
 int verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
                       size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out,
                       const uint8_t* pub = nullptr);
+// One group of a mixed batch (bpp_verify_groups): count proofs of statement C
+// (kept by the caller for the call) under one label, with the arrays
+// verify_batch takes.
+struct VerifyGroup {
+  const perm::Circuit* C;
+  const uint8_t* label;
+  size_t llen, count;
+  const uint8_t *proofs, *V, *pub;
+};
+// ok_out: nullptr, or [sum of counts] per-proof verdicts in group order
+int verify_groups(bpp_ctx* ctx, const bpp_gens* G, const VerifyGroup* groups, size_t n, uint8_t* ok_out);
 int verify_partial(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, const uint8_t seed[32], size_t first,
                    uint32_t wb, uint32_t we, h25519::ge* out);
 int verify_partial_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, const uint8_t seed[32], size_t first,
@@ -289,6 +305,36 @@ inline size_t first_bad(const std::vector<int>& bad, int code = 0) {
   for (size_t p = 0; p < bad.size(); ++p)
     if (code ? bad[p] == code : bad[p] != BPP_OK) return p;
   return SIZE_MAX;
+}
+
+// --- the statements' own refusals, shared by the per-kind entry points and
+// bpp_verify_groups
+
+// "k is in range"
+inline bool k_in_range(uint32_t k) { return k >= 2 && k <= (1u << 20); }
+
+// "every deck card is a canonical scalar" (deck == nullptr: 1..k)
+inline int deck_canonical(bpp_ctx* ctx, uint32_t k, const uint8_t* deck) {
+  Sc t;
+  for (uint32_t i = 0; deck && i < k; ++i)
+    if (!hsc::from_canonical(t, deck + 32 * (size_t)i)) {
+      if (ctx) ctx->err = "deck card " + std::to_string(i) + " is not a canonical scalar";
+      return BPP_ERR_NONCANONICAL;
+    }
+  return BPP_OK;
+}
+
+// "every public scalar of the call is canonical", and a circuit with public
+// inputs was given them: what the _pub entry points check before any device
+// work (bad: the first proof with a scalar >= l)
+inline int pub_check(const bpp_circuit* c, size_t count, const uint8_t* pub, size_t* bad) {
+  const uint32_t n_pub = c->C.n_pub;
+  if (!n_pub || !count) return BPP_OK;
+  if (!pub) return BPP_ERR_ARG;
+  std::vector<int> nc(count, BPP_OK);
+  check_canonical(pub, n_pub, count, nc);
+  *bad = first_bad(nc);
+  return *bad == SIZE_MAX ? BPP_OK : BPP_ERR_NONCANONICAL;
 }
 
 // One call of bpp_*_verify (count = 1), _verify_batch or _verify_batch_each

@@ -399,7 +399,7 @@ int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label,
   const size_t plen = perm::proof_len(C), vbytes = (size_t)C.m * 32, npts = count * J.npt;
   const size_t pub_bytes = count * (size_t)C.n_pub * 32;
   bpp_ctx* kid = nullptr;
-  BPP_TRY(ctx_child(ctx, VJ_CHILD, &kid));
+  BPP_TRY(ctx_child(ctx, ctx->vj_child, &kid));
   if (!ctx->vj_ev_dec) BPP_HIP(hipEventCreateWithFlags(&ctx->vj_ev_dec, hipEventDisableTiming));
   // (the previous job's decompression may still read "vj_in")
   if (ctx->vj_dec_pending) BPP_HIP(hipStreamWaitEvent(ctx->stream, ctx->vj_ev_dec, 0));
@@ -542,7 +542,7 @@ int verify_slice_points_dev(bpp_ctx* ctx, const bpp_verify_job& J, void* d_out) 
   // on the decompression's own (child) stream, behind the decompression:
   // an asynchronous begin's replay may still be running on ctx's stream
   bpp_ctx* kid = nullptr;
-  BPP_TRY(ctx_child(ctx, VJ_CHILD, &kid));
+  BPP_TRY(ctx_child(ctx, ctx->vj_child, &kid));
   void *d_x = nullptr, *d_dbad = nullptr;
   BPP_TRY(ctx_ws(ctx, "vj_x", J.count * J.npt * MSM_NIELS_WORDS * 4, &d_x));
   BPP_TRY(ctx_ws(ctx, "vj_dbad", 8, &d_dbad));
@@ -755,6 +755,195 @@ int verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, c
   }
   ctx->err = std::to_string(bad) + " of " + std::to_string(count) + " proofs failed, the first at index " +
              std::to_string(first);
+  return BPP_ERR_VERIFY;
+}
+
+// A mixed batch (bpp_verify_groups, _each with ok_out): n <= VG_MAX groups, each
+// `count` proofs of one statement, verified with ONE MSM.  The proof at
+// position p of group g is weighted by perm::batch_weight(seed, first_g + p,
+// r_p), first_g = the proofs before it in the call.  Every non-empty group
+// runs its job -- upload, replay, decompression, scalars -- on a group context
+// of its own (ctx_group), so the groups' latency chains overlap; ctx's stream
+// waits for one event per group, sums the groups' generator blocks into [G:
+// n_max | H: n_max | B | Bb] and gathers their proof-point scalars and points
+// behind it (k_verify_merge_groups, k_verify_gather_groups), and runs the MSM.
+// Nothing waits on the host before the MSM's own synchronisation; the replay
+// and decode verdicts of every group are read after it.  ok_out: as
+// verify_batch_each -- all ones when the batch passes, else each group's
+// verify_each_dev over what its job left on its context.
+int verify_groups(bpp_ctx* ctx, const bpp_gens* G, const VerifyGroup* groups, size_t n, uint8_t* ok_out) {
+  if (n > VG_MAX) return BPP_ERR_LEN;
+  uint32_t n_max = 0;
+  size_t total = 0, pts = 0;
+  for (size_t g = 0; g < n; ++g) {
+    if (!groups[g].count) continue;
+    const perm::Circuit& C = *groups[g].C;
+    if (groups[g].count > (1u << 26) || (C.n_pub && !groups[g].pub)) return BPP_ERR_ARG;
+    n_max = std::max(n_max, C.n_p);
+    total += groups[g].count;
+    pts += groups[g].count * vpts_n(C);
+  }
+  if (!total) return BPP_OK;
+  // (before any context's job generation moves)
+  BPP_TRY(gens_cover(ctx, G, n_max));
+  const uint32_t n0 = (uint32_t)(2 * G->n + 2);
+  const size_t NG = 2 * (size_t)n_max + 2, T = NG + pts, prec = (size_t)MSM_NIELS_WORDS * 4;
+  if (total > (1u << 26) || n0 + pts >= 0x80000000ull) return BPP_ERR_LEN;  // (an engine entry is index | sign << 31)
+  uint8_t seed[32];
+  if (!perm::verify_seed(seed)) {
+    ctx->err = "getrandom failed";
+    return BPP_ERR_DEVICE;
+  }
+  struct Run {
+    bpp_ctx* gctx = nullptr;
+    std::unique_ptr<bpp_verify_job> job;
+    size_t first = 0;
+    const uint64_t* h_dbad = nullptr;
+  };
+  Run run[VG_MAX];
+  size_t started = 0;  // group contexts with work queued
+  // "a failed call leaves no kernel reading the caller's buffers": every
+  // group context that has work queued is drained, then ctx
+  auto drain = [&]() {
+    for (size_t s = 0; s < started; ++s) {
+      bpp_ctx* gc = run[s].gctx;
+      if (!gc->children.empty()) (void)hipStreamSynchronize(gc->children[0]->stream);
+      (void)ctx_sync(gc);
+    }
+    (void)ctx_sync(ctx);
+  };
+  // a group context's refusal, reported on ctx
+  auto fail = [&](bpp_ctx* gc, int rc) {
+    if (gc && !gc->err.empty()) ctx->err = gc->err;
+    drain();
+    return rc;
+  };
+  void *d_sv = nullptr, *d_x = nullptr;
+  if (int rc = ctx_ws(ctx, "vg_s", T * 32 + 32, &d_sv)) return rc;
+  if (int rc = ctx_ws(ctx, "vg_x", pts * prec, &d_x)) return rc;
+  VerifyGroupTab tab;
+  VerifyGatherTab gt;
+  const bool each = ok_out != nullptr;
+  size_t first = 0, pt0 = 0;
+  for (size_t g = 0; g < n; ++g) {
+    const VerifyGroup& grp = groups[g];
+    if (!grp.count) continue;
+    const perm::Circuit& C = *grp.C;
+    Run& R = run[started];
+    if (int rc = ctx_group(ctx, started, &R.gctx)) return fail(nullptr, rc);
+    bpp_ctx* gc = R.gctx;
+    gc->err.clear();
+    R.first = first;
+    ++started;
+    // the group's job, asynchronous: upload, replay, decompression
+    if (int rc = verify_begin_dev(gc, C, grp.label, grp.llen, grp.count, grp.proofs, grp.V, R.job, 0, SIZE_MAX, false,
+                                  each, grp.pub))
+      return fail(gc, rc);
+    // its scalars, the layout verify_partial_dev leaves: "pv_s" = [2 n_p + 2
+    // merged | count x npt], "vs_gen" = each proof's own generator rows
+    const size_t NGg = 2 * (size_t)C.n_p + 2, npt = R.job->npt, gpts = grp.count * npt;
+    auto queue = [&]() -> int {
+      bpp_ctx* ctx = gc;  // (BPP_HIP names it)
+      void *d_rec = nullptr, *g_x = nullptr, *g_sv = nullptr, *d_dbad = nullptr;
+      BPP_TRY(ctx_ws(ctx, "vj_rec", (grp.count + 1) * vrec_n(C) * 32, &d_rec));
+      BPP_TRY(ctx_ws(ctx, "vj_x", gpts * prec, &g_x));
+      BPP_TRY(ctx_ws(ctx, "vj_dbad", 8, &d_dbad));
+      BPP_TRY(ctx_ws(ctx, "pv_s", (NGg + gpts) * 32 + 32, &g_sv));
+      {
+        HostScope hs(ctx, "verify_terms");
+        uint32_t* h_seed = nullptr;
+        BPP_TRY(ctx_zc_in(ctx, "vj_seed", seed, 32, &h_seed));
+        BPP_TRY(verify_scalars_dev_rec(ctx, C, (uint32_t)grp.count, (const uint32_t*)d_rec, h_seed, first,
+                                       (uint32_t*)g_sv, R.job->d_pub));
+      }
+      // behind the decompression: its verdict word, then the group's event
+      uint64_t* h_dbad = nullptr;
+      BPP_TRY(ctx_zc_out(ctx, "vj_dbad_h", 8, (uint32_t**)&h_dbad));
+      R.h_dbad = h_dbad;
+      BPP_HIP(hipStreamWaitEvent(ctx->stream, ctx->vj_ev_dec, 0));
+      BPP_HIP(hipMemcpyAsync(h_dbad, d_dbad, 8, hipMemcpyDeviceToHost, ctx->stream));
+      if (!ctx->vg_ev) BPP_HIP(hipEventCreateWithFlags(&ctx->vg_ev, hipEventDisableTiming));
+      BPP_HIP(hipEventRecord(ctx->vg_ev, ctx->stream));
+      tab.g[tab.n].blk = (const uint32_t*)g_sv;
+      tab.g[tab.n].n_p = C.n_p;
+      ++tab.n;
+      auto seg = [&](const void* src, void* dst, size_t bytes) {
+        gt.src[gt.n] = (const uint4*)src;
+        gt.dst[gt.n] = (uint4*)dst;
+        gt.pre[gt.n + 1] = gt.pre[gt.n] + bytes / 16;
+        ++gt.n;
+      };
+      seg((const uint8_t*)g_sv + NGg * 32, (uint8_t*)d_sv + (NG + pt0) * 32, gpts * 32);
+      seg(g_x, (uint8_t*)d_x + pt0 * prec, gpts * prec);
+      return BPP_OK;
+    };
+    if (int rc = queue()) return fail(gc, rc);
+    if (hipStreamWaitEvent(ctx->stream, gc->vg_ev, 0) != hipSuccess) {
+      ctx->err = "hipStreamWaitEvent on a group's event failed";
+      return fail(nullptr, BPP_ERR_DEVICE);
+    }
+    first += grp.count;
+    pt0 += gpts;
+  }
+  h25519::ge res;
+  auto merged = [&]() -> int {
+    BPP_TRY(verify_merge_groups_dev(ctx, tab, n_max, (uint32_t*)d_sv, gt));
+    // term t reads generator t of the resident set or proof point t - NG (the
+    // rule of verify_msm: no list when the set is exactly as long)
+    uint32_t* d_idx = nullptr;
+    if (G->n != n_max) {
+      std::vector<uint32_t> idx(T);
+      for (uint32_t i = 0; i < n_max; ++i) {
+        idx[i] = G->gidx(i);
+        idx[n_max + i] = G->hidx(i);
+      }
+      idx[2 * n_max] = G->bidx();
+      idx[2 * n_max + 1] = G->bbidx();
+      for (size_t j = NG; j < T; ++j) idx[j] = n0 + (uint32_t)(j - NG);
+      void* d = nullptr;
+      BPP_TRY(ctx_ws(ctx, "vg_idx", idx.size() * 4 + 4, &d));
+      BPP_TRY(ctx_h2d_const(ctx, "vg_idx", d, idx.data(), idx.size() * 4));
+      d_idx = (uint32_t*)d;
+    }
+    const uint32_t c = msm_choose_c((double)T);
+    return msm_single_dev(ctx, (const uint32_t*)d_sv, d_idx, G->d_tbl, T, c, 0, (254 + c - 1) / c, &res,
+                          (const uint32_t*)d_x, n0);
+  };
+  if (int rc = merged()) return fail(nullptr, rc);
+  // ctx's stream waited for every group's event and has been synchronised:
+  // the group contexts are idle, their pinned verdicts written
+  bool rejected = false;
+  for (size_t s = 0; s < started; ++s) {
+    ctx_mark_idle(run[s].gctx);
+    if (async_replay_verdict(ctx, *run[s].job) != BPP_OK || decode_verdict(ctx, *run[s].h_dbad) != BPP_OK)
+      rejected = true;
+  }
+  if (!rejected) {
+    uint8_t e[32];
+    h25519::encode(e, res);
+    static const uint8_t zero[32] = {0};
+    if (memcmp(e, zero, 32) == 0) {
+      if (each) memset(ok_out, 1, total);
+      return BPP_OK;
+    }
+    ctx->err = "the batch check failed";
+  }
+  if (!each) return BPP_ERR_VERIFY;
+  for (size_t s = 0; s < started; ++s)
+    if (int rc = verify_each_dev(run[s].gctx, G, *run[s].job, ok_out + run[s].first)) return fail(run[s].gctx, rc);
+  size_t bad = 0, first_bad = total;
+  for (size_t p = total; p-- > 0;)
+    if (!ok_out[p]) {
+      ++bad;
+      first_bad = p;
+    }
+  if (!bad) {
+    memset(ok_out, 0, total);
+    ctx->err = "the batch check failed but no single proof did";
+    return BPP_ERR_DEVICE;
+  }
+  ctx->err = std::to_string(bad) + " of " + std::to_string(total) + " proofs failed, the first at index " +
+             std::to_string(first_bad);
   return BPP_ERR_VERIFY;
 }
 

@@ -59,6 +59,32 @@ void verify_init_state(const perm::Circuit& C, const uint8_t* label, size_t llen
 // (the generator scalars of a gathered sliced verification).
 int verify_sum_blocks_dev(bpp_ctx* ctx, uint32_t nb, uint32_t n, const uint32_t* d_blocks, uint32_t stride,
                           uint32_t* d_out);
+// A mixed batch (bpp_verify_groups): up to VG_MAX groups of different
+// circuits.  VerifyGroupTab: group g's generator block blk ([2 n_p + 2][8]
+// words: G, H, B, Bb, the head of its context's "pv_s") and its n_p.
+// VerifyGatherTab: segments of 16-byte units, segment s = pre[s + 1] - pre[s]
+// units from src[s] to dst[s] (two per group: its proof-point scalars and its
+// decompressed points).  Both are kernel arguments: nothing is uploaded.
+#define VG_MAX BPP_VERIFY_GROUPS_MAX
+struct VerifyGroupTab {
+  uint32_t n = 0;
+  struct {
+    const uint32_t* blk;
+    uint32_t n_p;
+  } g[VG_MAX];
+};
+struct VerifyGatherTab {
+  uint32_t n = 0;
+  uint64_t pre[2 * VG_MAX + 1] = {0};
+  const uint4* src[2 * VG_MAX];
+  uint4* dst[2 * VG_MAX];
+};
+// d_out [2 n_max + 2][8] = the groups' generator scalars summed slot by slot
+// (out[i] and out[n_max + i] over the groups with i < n_p, the two bases over
+// all; mod l, canonical in and out), then the gather.  n_p <= n_max for every
+// group (BPP_ERR_ARG otherwise, before any launch).
+int verify_merge_groups_dev(bpp_ctx* ctx, const VerifyGroupTab& tab, uint32_t n_max, uint32_t* d_out,
+                            const VerifyGatherTab& gt);
 // k_verify_consts (each proof's weight perm::batch_weight(seed, first + p,
 // r_p) and its constants) + k_verify_scalars + k_verify_merge over device
 // records (poly.hip).  seed: 8 words, may be pinned host memory.  d_pub

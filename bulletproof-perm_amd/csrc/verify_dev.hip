@@ -368,6 +368,60 @@ int verify_sum_blocks_dev(bpp_ctx* ctx, uint32_t nb, uint32_t n, const uint32_t*
   return ctx_check_launch(ctx, "k_verify_sum_blocks");
 }
 
+// The generator scalars of a mixed batch (bpp_verify_groups): k_verify_sum_blocks
+// over blocks of different width.  Group g's block is [G: n_p,g | H: n_p,g | B |
+// Bb] canonical scalars; the generator chain is one sequence, so G_i and H_i of a
+// narrower circuit are the first n_p,g of the widest one's and slot i of every
+// block that has it weighs the same point.  One lane per output scalar of [G:
+// n_max | H: n_max | B | Bb]; the table rides in the kernel's arguments.
+__global__ void __launch_bounds__(64) k_verify_merge_groups(VerifyGroupTab tab, uint32_t n_max,
+                                                            uint32_t* __restrict__ out) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= 2 * n_max + 2) return;
+  // t -> (part, i): G_i, H_i, or the two bases behind them
+  const uint32_t part = t < n_max ? 0u : t < 2 * n_max ? 1u : 2u;
+  const uint32_t i = t - part * n_max;  // (part 2: 0 = B, 1 = Bb)
+  sc acc = sc_zero();
+  for (uint32_t g = 0; g < tab.n; ++g) {
+    const uint32_t n_p = tab.g[g].n_p;
+    if (part < 2 && i >= n_p) continue;
+    acc = sc_add(acc, sc_load(tab.g[g].blk + 8 * ((size_t)part * n_p + i)));
+  }
+  sc_store(out + 8 * (size_t)t, acc);
+}
+
+// Segment s's units (16 B each) [pre[s], pre[s + 1]) of the launch are copied
+// from src[s] to dst[s]: every group's proof-point scalars and Niels rows to
+// their places behind the merged generators, in ONE launch.
+__global__ void __launch_bounds__(256) k_verify_gather_groups(VerifyGatherTab tab) {
+  const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= tab.pre[tab.n]) return;
+  uint32_t lo = 0, hi = tab.n;  // segment s: pre[s] <= u < pre[s + 1]
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (tab.pre[mid] <= u) lo = mid;
+    else hi = mid;
+  }
+  tab.dst[lo][u - tab.pre[lo]] = tab.src[lo][u - tab.pre[lo]];
+}
+
+int verify_merge_groups_dev(bpp_ctx* ctx, const VerifyGroupTab& tab, uint32_t n_max, uint32_t* d_out,
+                            const VerifyGatherTab& gt) {
+  if (tab.n > VG_MAX || gt.n > 2 * VG_MAX) return BPP_ERR_ARG;
+  for (uint32_t g = 0; g < tab.n; ++g)
+    if (!tab.g[g].blk || !tab.g[g].n_p || tab.g[g].n_p > n_max) return BPP_ERR_ARG;
+  for (uint32_t s = 0; s < gt.n; ++s)
+    if (!gt.src[s] || !gt.dst[s] || gt.pre[s + 1] < gt.pre[s]) return BPP_ERR_ARG;
+  if (!tab.n || !n_max) return BPP_OK;
+  {
+    ProfScope ps(ctx, "verify_merge_groups");
+    hipLaunchKernelGGL(k_verify_merge_groups, dim3(grid_for(2 * (size_t)n_max + 2, 64)), dim3(64), 0, ctx->stream, tab,
+                       n_max, d_out);
+    if (gt.n && gt.pre[gt.n])
+      hipLaunchKernelGGL(k_verify_gather_groups, dim3(grid_for(gt.pre[gt.n], 256)), dim3(256), 0, ctx->stream, gt);
+  }
+  return ctx_check_launch(ctx, "k_verify_merge_groups/gather");
+}
 
 int verify_decompress_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_proofs,
                           const uint32_t* d_V, uint32_t* d_tbl, unsigned long long* d_bad, uint32_t p0, uint32_t p1,

@@ -601,6 +601,57 @@ int bpp_circuit_verify_batch_each_pub(bpp_ctx* ctx, const bpp_gens* g, const bpp
                                       const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
                                       const uint8_t* pub, uint8_t* ok_out);
 
+/* Mixed batches: proofs of different statements verified in one call with ONE
+ * GPU MSM.  A group is `count` proofs of one statement under one label: the
+ * two-half shuffle of k cards, the public-deck shuffle of k cards (deck as
+ * bpp_deck_verify_batch takes it), or a compiled circuit (pub as the _pub
+ * verifiers take it when the circuit's n_pub > 0, NULL otherwise).  proofs, V
+ * and pub have the layouts of that statement's _verify_batch.  Groups may
+ * differ in n_p, m and proof length, may be empty, and two groups may name the
+ * same statement; at most BPP_VERIFY_GROUPS_MAX groups per call (BPP_ERR_LEN
+ * beyond; the caller splits).
+ * One verifier seed serves the call: the proof at position p of group g is
+ * weighted by its index in the call, (the counts of the groups before g) + p.
+ * Every non-empty group's upload, replay and decompression run on a stream of
+ * its own beside the others'; the generator scalars of all groups are summed
+ * into one block of the widest circuit's width (the generator chain is one
+ * sequence: a narrower circuit uses its first n_p) and one MSM of 2 n_max + 2
+ * + sum count_g (m_g + 8 + 2 lg_g) terms decides.  g must cover n_max
+ * (BPP_ERR_LEN otherwise).
+ *   BPP_OK          every proof of every group verifies.
+ *   BPP_ERR_VERIFY  at least one does not.
+ * Refused before any device work, and with no effect on any job of ctx: what
+ * the statement's own entry points refuse -- k outside [2, 2^20], a deck card or
+ * a public input >= l (BPP_ERR_NONCANONICAL), a NULL circuit, a NULL pub with
+ * n_pub > 0 -- and a pub given with n_pub = 0, an unknown kind, NULL proofs or
+ * V with count > 0 (BPP_ERR_ARG; bpp_ctx_last_error names the group).
+ * n_groups == 0 or every count 0: BPP_OK, nothing is launched.
+ * bpp_verify_groups_each writes one verdict per proof (ok: sum of the counts
+ * bytes, in group order) under the ok_out contract of
+ * bpp_perm_verify_batch_each: a batch that passes costs what bpp_verify_groups
+ * costs; otherwise each proof's own MSM runs over what the groups' jobs left on
+ * the device, and bpp_ctx_last_error gives the count and the first failing
+ * index in the call.  The per-kind entry points on the same ctx are not
+ * affected by either call. */
+#define BPP_STMT_PERM 0    /* two-half shuffle: k                    */
+#define BPP_STMT_DECK 1    /* public-deck shuffle: k, deck (or NULL) */
+#define BPP_STMT_CIRCUIT 2 /* circuit handle; pub iff its n_pub > 0  */
+#define BPP_VERIFY_GROUPS_MAX 16
+typedef struct {
+  uint32_t kind, k;
+  const uint8_t* deck;        /* DECK: k x 32 canonical, or NULL = 1..k */
+  const bpp_circuit* circuit; /* CIRCUIT */
+  const uint8_t* label;
+  size_t label_len;
+  size_t count;      /* may be 0 */
+  const uint8_t* proofs; /* count x proof_len */
+  const uint8_t* V;      /* count x m x 32 */
+  const uint8_t* pub;    /* count x n_pub x 32, CIRCUIT with n_pub > 0 */
+} bpp_verify_group;
+int bpp_verify_groups(bpp_ctx* ctx, const bpp_gens* g, const bpp_verify_group* groups, size_t n_groups);
+int bpp_verify_groups_each(bpp_ctx* ctx, const bpp_gens* g, const bpp_verify_group* groups, size_t n_groups,
+                           uint8_t* ok);
+
 /* Batch verification split for several GPUs (north_star: "the single large
  * verifier MSM partitions its bucket windows across GPUs"; reference verify
  * circuit_lib.rs:478-585).  Host phase, no GPU: parse `count` proofs, replay
