@@ -785,17 +785,31 @@ class Circuit:
     bpp_circuit_create_pub when desc.n_pub; no GPU): desc is a
     gadgets.CircuitDesc (or anything with its fields).  n_p, Q, m, n_pub,
     digest and proof_len are the compiled statement's; matrix() and eval()
-    expose the compiled rows and the host witness."""
+    expose the compiled rows and the host witness.  large=True
+    (bpp_circuit_create_ex, BPP_CIRCUIT_LARGE) accepts circuits beyond the
+    one-workgroup LDS bounds (682 gates, Q = 1507); tiled=True
+    (BPP_CIRCUIT_TILED, implies large) uses the large-circuit kernels even where
+    the narrow ones fit.  Neither is part of the statement: digest, matrices and
+    proof bytes are the same."""
 
-    def __init__(self, desc):
+    LARGE, TILED = 1, 2  # BPP_CIRCUIT_LARGE, BPP_CIRCUIT_TILED
+
+    def __init__(self, desc, large: bool = False, tiled: bool = False, flags: "int | None" = None):
+        """flags: the raw flag word in place of large / tiled (tests)."""
         self.lib = _lib.load()
         self.desc = desc
+        if flags is None:
+            flags = (self.LARGE if large else 0) | (self.TILED if tiled else 0)
+        self.flags = flags
         u32a = lambda xs: (C.c_uint32 * max(len(xs), 1))(*xs)
         self._keep = (u32a(desc.side_aux), u32a(desc.lc_off), u32a(desc.lc_var), b"".join(desc.lc_coef))
         d = _CircuitDescC(desc.m_in, desc.n_gates, desc.n_aux, desc.n_asserts, self._keep[0], self._keep[1],
                           self._keep[2], self._keep[3])
         h = C.c_void_p()
-        if getattr(desc, "n_pub", 0):
+        if flags:
+            check(self.lib.bpp_circuit_create_ex(C.byref(d), getattr(desc, "n_pub", 0), flags, C.byref(h)),
+                  "bpp_circuit_create_ex")
+        elif getattr(desc, "n_pub", 0):
             check(self.lib.bpp_circuit_create_pub(C.byref(d), desc.n_pub, C.byref(h)), "bpp_circuit_create_pub")
         else:
             check(self.lib.bpp_circuit_create(C.byref(d), C.byref(h)), "bpp_circuit_create")

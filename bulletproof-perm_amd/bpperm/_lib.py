@@ -111,6 +111,7 @@ SIGNATURES = {
     "bpp_circuit_verify_batch": (i32, [vp, vp, vp, sz, vp, sz, vp, vp]),
     "bpp_circuit_verify_batch_each": (i32, [vp, vp, vp, sz, vp, sz, vp, vp, vp]),
     "bpp_circuit_create_pub": (i32, [vp, u32, C.POINTER(vp)]),
+    "bpp_circuit_create_ex": (i32, [vp, u32, u32, C.POINTER(vp)]),
     "bpp_circuit_n_pub": (u32, [vp]),
     "bpp_circuit_eval_pub": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u32)]),
     "bpp_circuit_prove_batch_pub": (i32, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp]),

@@ -232,6 +232,39 @@ def in_range(nbits: int) -> CircuitDesc:
     return b.build(aux_of)
 
 
+def in_range_many(count: int, nbits: int) -> CircuitDesc:
+    """v_0..v_{count-1} are each below 2^nbits, in one proof: in_range's bit
+    gates for every value (count * nbits gates with both sides free, each with
+    its asserts o = 0 and l + r - 1 = 0) and one weighted-sum assert per value.
+    aux_of(v) gives the 2 count nbits hints, value-major.  16 values of 64 bits
+    are 1024 gates: a large circuit (Circuit(desc, large=True))."""
+    if count < 1:
+        raise ValueError("count >= 1")
+    if not 1 <= nbits <= 252:
+        raise ValueError("1 <= nbits <= 252")
+    b = CircuitBuilder()
+    vs = b.inputs(count)
+    for v in vs:
+        total = LC()
+        for i in range(nbits):
+            l, r, o = b.free_mul()
+            b.assert_zero(o)
+            b.assert_zero(l + r - 1)
+            total = total + l * (1 << i)
+        b.assert_zero(total - v)
+
+    def aux_of(vals):
+        out = []
+        for j in range(count):
+            x = int(vals[j]) % L
+            for i in range(nbits):
+                bit = (x >> i) & 1
+                out += [bit, 1 - bit]
+        return out
+
+    return b.build(aux_of)
+
+
 def same_multiset(k: int) -> CircuitDesc:
     """Two hidden hands v_0..v_{k-1} and v_k..v_{2k-1} hold the same multiset:
     prod (v_i - x) over each hand, 2k - 2 gates, one assert on the difference

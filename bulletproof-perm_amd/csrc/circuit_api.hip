@@ -11,7 +11,8 @@
 using namespace perm_impl;
 
 static_assert(circuit::OK == BPP_OK && circuit::ERR_ARG == BPP_ERR_ARG && circuit::ERR_LEN == BPP_ERR_LEN &&
-                  circuit::ERR_NONCANONICAL == BPP_ERR_NONCANONICAL && circuit::SIDE_LC == BPP_SIDE_LC,
+                  circuit::ERR_NONCANONICAL == BPP_ERR_NONCANONICAL && circuit::SIDE_LC == BPP_SIDE_LC &&
+                  circuit::kLarge == BPP_CIRCUIT_LARGE && circuit::kTiled == BPP_CIRCUIT_TILED,
               "host/circuit.h restates these");
 
 namespace {
@@ -51,19 +52,24 @@ int circuit_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* aux, con
 
 extern "C" {
 
-int bpp_circuit_create_pub(const bpp_circuit_desc* desc, uint32_t n_pub, bpp_circuit** out) {
+int bpp_circuit_create_ex(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags, bpp_circuit** out) {
   return bpp_guard(nullptr, [&]() -> int {
     if (!desc || !out) return BPP_ERR_ARG;
     *out = nullptr;
     circuit::Desc d = {desc->m_in,   desc->n_gates, desc->n_aux,  desc->n_asserts,
                        desc->side_aux, desc->lc_off,  desc->lc_var, desc->lc_coef};
     d.n_pub = n_pub;
+    d.flags = flags;
     std::unique_ptr<bpp_circuit> c(new bpp_circuit());
     std::string err;
     BPP_TRY(circuit::compile(d, c->C, err));
     *out = c.release();
     return BPP_OK;
   });
+}
+
+int bpp_circuit_create_pub(const bpp_circuit_desc* desc, uint32_t n_pub, bpp_circuit** out) {
+  return bpp_circuit_create_ex(desc, n_pub, 0, out);
 }
 
 int bpp_circuit_create(const bpp_circuit_desc* desc, bpp_circuit** out) {

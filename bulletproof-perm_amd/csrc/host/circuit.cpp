@@ -33,6 +33,7 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
     err = "circuit: " + what;
     return rc;
   };
+  if (d.flags & ~(kLarge | kTiled)) return fail(ERR_ARG, "unknown flag bits");
   if (!d.m_in || !d.n_gates) return fail(ERR_ARG, "no inputs or no gates");
   if (d.m_in > kMaxInputs || d.n_gates > kMaxGates || d.n_asserts > kMaxAsserts || d.n_aux > kMaxAux)
     return fail(ERR_LEN, "more inputs, gates, asserts or auxiliary values than any circuit that fits");
@@ -89,8 +90,10 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
   C.m = m_in + 1;
   C.nv = m_in;
   C.n_pub = d.n_pub;
-  if (!lds_fits(C.Q, C.n_p, n))
-    return fail(ERR_LEN, "Q = " + std::to_string(C.Q) + ", n = " + std::to_string(n) + " beyond the kernels' LDS");
+  C.tiled = (d.flags & kTiled) != 0;
+  if (!d.flags && !lds_fits(C.Q, C.n_p, n))
+    return fail(ERR_LEN, "Q = " + std::to_string(C.Q) + ", n = " + std::to_string(n) +
+                             " beyond the one-workgroup kernels' LDS (BPP_CIRCUIT_LARGE lifts this)");
   P->side_aux.assign(d.side_aux, d.side_aux + 2 * (size_t)n);
   P->lc_off.assign(d.lc_off, d.lc_off + nlc + 1);
   P->lc_var.assign(d.lc_var, d.lc_var + T);

@@ -41,7 +41,9 @@ struct Desc {
   const uint32_t* lc_var;    // [T]
   const uint8_t* lc_coef;    // [T][32]
   uint32_t n_pub = 0;        // (bpp_circuit_create_pub's; not a field of bpp_circuit_desc)
+  uint32_t flags = 0;        // (bpp_circuit_create_ex's kLarge | kTiled; never part of the digest)
 };
+constexpr uint32_t kLarge = 1u, kTiled = 2u;  // BPP_CIRCUIT_LARGE, BPP_CIRCUIT_TILED (TILED implies LARGE)
 
 // variable ids of lc_var
 inline uint32_t var_one() { return 0; }
@@ -80,8 +82,9 @@ void digest(const Desc& d, uint8_t out[32]);
 // Validates and compiles: ERR_ARG for m_in = 0 or n = 0, ids or aux indices
 // out of range, a definition reading a wire of gate h >= g, a nonempty
 // combination on a free side, unsorted or duplicate ids, a zero coefficient, a
-// non-monotone lc_off; ERR_NONCANONICAL for a coefficient >= l; ERR_LEN beyond
-// lds_fits or kMaxPub.  C.program is the compiled program.
+// non-monotone lc_off, unknown flag bits; ERR_NONCANONICAL for a coefficient
+// >= l; ERR_LEN beyond kMaxPub, the kMax* below or, without kLarge, lds_fits.
+// C.program is the compiled program; C.tiled = the kTiled flag.
 int compile(const Desc& d, perm::Circuit& C, std::string& err);
 
 // The host witness: a_L, a_R, a_O (n_p each, padding gates zero) from v
@@ -101,7 +104,20 @@ inline size_t witness_program_lds(uint32_t n) { return (size_t)3 * n * 32 + 32; 
 inline size_t witness_program_staged_lds(const Program& P) {
   return witness_program_lds(P.n) + ((size_t)P.m_in + P.n_pub) * 32 + P.dev.size() * 4;
 }
-// "every per-proof kernel's workgroup fits its LDS": k_poly_coef and
+// k_witness_program_wide keeps the 3n wires in global memory ([P][3n][8] words,
+// "wp_wires", inside what prove_wipe zeroes) and only the fail word in LDS.
+constexpr size_t witness_program_wide_lds() { return 32; }
+// Which kernels a circuit's batches launch: each by its own bound, or all of
+// the large-circuit ones under kTiled.
+inline bool witness_wide(const perm::Circuit& C) { return C.tiled || witness_program_lds(C.n) > perm::kLdsMax; }
+inline bool poly_coef_split(const perm::Circuit& C) {
+  return C.tiled || perm::poly_coef_lds(C.Q, C.n_p) > perm::kLdsMax;
+}
+inline bool verify_scalars_split(const perm::Circuit& C) {
+  return C.tiled || perm::verify_scalars_lds(C.Q, C.n_p) > perm::kLdsMax;
+}
+// "every per-proof kernel's workgroup fits its LDS" (what a circuit created
+// without kLarge must satisfy): k_poly_coef and
 // k_verify_scalars (perm.h, the formulas their launches use) and
 // k_witness_program -- Q <= 1507 at n_p >= 256, n <= 682
 inline bool lds_fits(uint32_t Q, uint32_t n_p, uint32_t n) {

@@ -46,6 +46,10 @@ struct Circuit {
   // absorbs ("pub", 32 bytes each) right after the prefix below
   uint32_t n_pub = 0;
   std::vector<Entry> WU;  // (col = the public input's index)
+  // BPP_CIRCUIT_TILED: the large-circuit kernels (split row tables, wires in
+  // global memory) even where the narrow ones fit.  How the statement is
+  // computed, never part of it: no digest, transcript or proof byte reads it.
+  bool tiled = false;
 };
 
 Circuit build(uint32_t k);
@@ -100,6 +104,17 @@ inline size_t poly_coef_lds(uint32_t Q, uint32_t n_p) {
 inline size_t verify_scalars_lds(uint32_t Q, uint32_t n_p) {
   return ((size_t)Q + 1 + 2 * (n_p < kPolyLanes ? n_p : kPolyLanes)) * 32 + (kPolyLanes / 64) * 2 * 32;
 }
+// The same two kernels with the row table split in two (k_poly_coef_tiled,
+// k_verify_scalars[_pub]_tiled; large circuits, circuit.h): lo[i] = z^i for i <
+// kRowLo and hi[j] = z^(kRowLo j) for j <= Q / kRowLo in place of z^0..z^Q, the
+// rest as above; nred = 7 (2) scalars of workgroup-sum scratch per wave.  Below
+// kLdsMax for every Q a circuit may have (static_assert).
+constexpr uint32_t kRowLo = 256;
+constexpr size_t split_tables_lds(uint32_t Q, uint32_t n_p, uint32_t nred) {
+  return ((size_t)kRowLo + (Q / kRowLo) + 1 + 2 * (n_p < kPolyLanes ? n_p : kPolyLanes)) * 32 +
+         (kPolyLanes / 64) * nred * 32;
+}
+static_assert(split_tables_lds((3u << 16) + 1, 1u << 16, 7) <= kLdsMax, "Q <= 2 kMaxGates + kMaxAsserts + 1 fits");
 // The chain witness kernels (poly.hip chain_prefix_products; k_witness and
 // k_witness_cards: 2 chains of k, k_witness_deck: 1): the prefix products
 // [chains][k] and two scan buffers [chains][lanes] of 32-byte scalars.  256

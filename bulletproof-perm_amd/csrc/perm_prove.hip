@@ -191,7 +191,8 @@ namespace perm_impl BPP_HIDDEN {
 // production entry point (bpp_perm_prove_batch_entropy) on its context, and
 // by each sub-batch thread on its child context (BPP_PROVE_STREAMS > 1).
 static const char* const kSecretWs[] = {"pb_rng_in", "pb_gamma", "mt_s",  "pv_v",   "pv_g",    "pv_gx",  "poly_vec",
-                                        "poly_hf",   "pf_l",     "pf_r",  "ipa_am", "ipa_bm",  "ipa_am1", "ipa_bm1"};
+                                        "poly_hf",   "pf_l",     "pf_r",  "ipa_am", "ipa_bm",  "ipa_am1", "ipa_bm1",
+                                        "wp_wires"};  // (k_witness_program_wide's wires)
 static const char* const kSecretHost[] = {"pp_v", "pp_g", "ipa_zc_a", "ipa_zc_b"};  // (ipa_zc_*: bpp_ipa_prove zeroes them itself)
 static_assert(sizeof(kSecretWs) / sizeof(kSecretWs[0]) <= WIPE_MAX, "WipeSpans too small");
 int prove_wipe(bpp_ctx* ctx) {
@@ -279,8 +280,9 @@ struct ProveBatch {
   // products fit the workgroup's LDS; the host restatement beyond that
   // (BPP_DECK_HOST_WITNESS=1: the deck circuit's host witness at every k, for
   // the test that compares the two paths)
-  // a caller-defined circuit fits k_witness_program's LDS by construction
-  // (circuit::lds_fits); BPP_CIRCUIT_HOST_WITNESS=1: its host witness
+  // a caller-defined circuit's device witness has no size bound: witness_program_dev
+  // picks the kernel by the wires' size and the TILED flag (LDS, or global memory
+  // for a large circuit); BPP_CIRCUIT_HOST_WITNESS=1: its host witness at every size
   const bool dev_witness = C.program ? !circuit_host_witness()
                            : C.deck  ? k <= DECK_WITNESS_DEV_MAX && !deck_host_witness()
                                      : k <= perm::chain_witness_dev_max(2);

@@ -76,7 +76,9 @@ int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uin
 // C.program over its own values (d_vals [P][m_in], d_aux [P][n_aux], d_x [P],
 // canonical): a_L, a_R, a_O into their slots of d_sc, and into fail[p] (pinned
 // host memory, valid after the next ctx_sync) 1 + the first assert that does
-// not hold, or 0.
+// not hold, or 0.  The kernel is chosen by the wires' size and the circuit's
+// TILED flag (circuit::witness_wide): k_witness_program_wide keeps them in the
+// workspace "wp_wires", which prove_wipe zeroes; no size is refused.
 int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
                         const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail,
                         const uint32_t* d_pub = nullptr);  // (d_pub [P][n_pub] canonical: the public inputs)

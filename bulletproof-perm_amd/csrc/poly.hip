@@ -109,12 +109,45 @@ FE_INLINE void sc_block_sum(sc (&v)[K], uint32_t* lds) {
       _Pragma("unroll") for (int j = 0; j < K; ++j) v[j] = sc_add(v[j], sc_load(lds + (u * K + j) * 8));
 }
 
+// The row powers as the kernels read them: row_at(zp, q) = z^(q+1), Montgomery.
+// SPLIT = false: one LDS table z^0..z^Q (zp = its entry 1).  SPLIT = true
+// (large circuits, perm::split_tables_lds): zp[i] = z^i for i < ROW_LO and
+// hi[j] = z^(ROW_LO j) for j <= Q >> ROW_LO_LG, z^e = zp[e mod ROW_LO]
+// hi[e / ROW_LO] -- one more multiply a read, and Q no longer sets the table's
+// size (the y tables' scheme, POW_LO, with the second factor looked up instead
+// of carried).  A free function over a plain struct: as a member function the
+// same read changed k_verify_scalars' spills.
+#define ROW_LO 256
+#define ROW_LO_LG 8
+static_assert(ROW_LO == 1 << ROW_LO_LG && ROW_LO == perm::kRowLo, "perm::split_tables_lds states ROW_LO");
+template <bool SPLIT>
+struct RowPow {
+  const uint32_t* zp;
+  const uint32_t* hi;
+};
+template <bool SPLIT>
+FE_INLINE sc row_at(const RowPow<SPLIT> r, uint32_t q) {
+  if constexpr (SPLIT) {
+    const uint32_t e = q + 1;
+    return sc_mont(sc_load(r.zp + 8 * (e & (ROW_LO - 1))), sc_load(r.hi + 8 * (e >> ROW_LO_LG)));
+  } else {
+    return sc_load(r.zp + 8 * q);
+  }
+}
+// The split form's second table (every lane calls, after the sc_tables3 that
+// built lo; ends with a barrier): hi = the powers of z^ROW_LO = lo[ROW_LO - 1] z
+FE_INLINE void row_hi_table(uint32_t* hi, uint32_t NH, const uint32_t* lo, const sc& zR, const sc& oneR) {
+  if (threadIdx.x == 0) sc_table_pow_init(hi, NH, sc_mont(sc_load(lo + 8 * (ROW_LO - 1)), zR), oneR);
+  sc_tables3({hi, NH, false}, {hi, 1, false}, {hi, 1, false});
+}
+
 // sum over the column's entries of z^(q+1) * val (Montgomery)
+template <class Rows>
 FE_INLINE sc col_sum(const uint32_t* __restrict__ cp, const uint32_t* __restrict__ ce, uint32_t col,
-                     const uint32_t* zp) {
+                     const Rows zp) {
   sc acc = sc_zero();
   for (uint32_t e = cp[col]; e < cp[col + 1]; ++e)
-    acc = sc_add(acc, sc_mont(sc_load(zp + 8 * ce[9 * e]), sc_load(ce + 9 * e + 1)));
+    acc = sc_add(acc, sc_mont(row_at(zp, ce[9 * e]), sc_load(ce + 9 * e + 1)));
   return acc;
 }
 
@@ -124,11 +157,12 @@ FE_INLINE sc col_sum(const uint32_t* __restrict__ cp, const uint32_t* __restrict
 // doubled k_poly_coef (126 -> 292 us) and dominated k_verify_scalars.
 // Valid in lane 0; `red` is the workgroup-sum scratch.
 #define HEAVY_COL 8
+template <class Rows>
 FE_INLINE sc col_sum_block(const uint32_t* __restrict__ cp, const uint32_t* __restrict__ ce, uint32_t col,
-                           const uint32_t* zp, uint32_t* red) {
+                           const Rows zp, uint32_t* red) {
   sc v[1] = {sc_zero()};
   for (uint32_t e = cp[col] + threadIdx.x; e < cp[col + 1]; e += blockDim.x)
-    v[0] = sc_add(v[0], sc_mont(sc_load(zp + 8 * ce[9 * e]), sc_load(ce + 9 * e + 1)));
+    v[0] = sc_add(v[0], sc_mont(row_at(zp, ce[9 * e]), sc_load(ce + 9 * e + 1)));
   sc_block_sum<1>(v, red);
   __syncthreads();  // red is reused by the next call
   return v[0];
@@ -138,90 +172,14 @@ FE_INLINE sc col_sum_block(const uint32_t* __restrict__ cp, const uint32_t* __re
 // t_out[p] = t_1..t_6, <z^Q W_V, gamma_p> (gamma: [P][m] canonical)
 #define POLY_NT 7
 static_assert(POLY_T == perm::kPolyLanes && POLY_NT == 7, "perm::poly_coef_lds / verify_scalars_lds state these");
-__global__ void __launch_bounds__(POLY_T) k_poly_coef(uint32_t n_p, uint32_t m, uint32_t Q, uint32_t per,
-                                                   const uint32_t* __restrict__ sc_in,
-                                                   const uint32_t* __restrict__ ch,
-                                                   const uint32_t* __restrict__ cp, const uint32_t* __restrict__ ce,
-                                                   const uint32_t* __restrict__ gamma, uint32_t* __restrict__ vec,
-                                                   uint32_t* __restrict__ hf, uint32_t* __restrict__ t_out) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  const uint32_t NY = min(n_p, (uint32_t)POW_LO);
-  uint32_t* zt = lds;               // [Q + 1] z^e
-  uint32_t* yt = zt + 8 * (Q + 1);  // [NY] y^i
-  uint32_t* yit = yt + 8 * NY;      // [NY] y^-i
-  uint32_t* red = yit + 8 * NY;     // reduction scratch
-  const uint32_t* zp = zt + 8;      // z^(q+1)
-  const uint32_t p = blockIdx.x;
-  const sc oneR = sc_one_mont();
-  const sc yR = sc_to_mont(sc_load(ch + 24 * p)), yiR = sc_to_mont(sc_load(ch + 24 * p + 8)),
-           zR = sc_to_mont(sc_load(ch + 24 * p + 16));
-  if (threadIdx.x == 0) {
-    sc_table_pow_init(zt, Q + 1, zR, oneR);
-    sc_table_pow_init(yt, NY, yR, oneR);
-    sc_table_pow_init(yit, NY, yiR, oneR);
-  }
-  sc_tables3({zt, Q + 1, false}, {yt, NY, false}, {yit, NY, false});
-  sc yhi = oneR, yihi = oneR, ystep = oneR, yistep = oneR;  // (y^POW_LO)^r
-  if (n_p > POW_LO) {
-    ystep = sc_mont(sc_load(yt + 8 * (POW_LO - 1)), yR);
-    yistep = sc_mont(sc_load(yit + 8 * (POW_LO - 1)), yiR);
-  }
-  sc t[POLY_NT];
-  _Pragma("unroll") for (int j = 0; j < POLY_NT; ++j) t[j] = sc_zero();
-  for (uint32_t i = threadIdx.x; i < n_p; i += blockDim.x) {
-    const uint32_t* s = sc_in + (size_t)p * per * 8;
-    const sc aL = sc_to_mont(sc_load(s + 8 * (1 + i)));
-    const sc aR = sc_to_mont(sc_load(s + 8 * (1 + n_p + i)));
-    const sc l2 = sc_to_mont(sc_load(s + 8 * (2 + 2 * n_p + i)));  // a_O
-    const sc l3 = sc_to_mont(sc_load(s + 8 * (3 + 3 * n_p + i)));  // s_L
-    const sc sR = sc_to_mont(sc_load(s + 8 * (3 + 4 * n_p + i)));
-    sc yp = sc_load(yt + 8 * (i % POW_LO)), yip = sc_load(yit + 8 * (i % POW_LO));
-    if (i >= POW_LO) {
-      yp = sc_mont(yp, yhi);
-      yip = sc_mont(yip, yihi);
-    }
-    if (n_p > POW_LO) {
-      yhi = sc_mont(yhi, ystep);
-      yihi = sc_mont(yihi, yistep);
-    }
-    const sc zWL = col_sum(cp, ce, i, zp), zWR = col_sum(cp + (n_p + 1), ce, i, zp),
-             zWO = col_sum(cp + 2 * (n_p + 1), ce, i, zp);
-    const sc l1 = sc_add(aL, sc_mont(zWR, yip));
-    const sc r0 = sc_sub(zWO, yp);
-    const sc r1 = sc_add(sc_mont(aR, yp), zWL);
-    const sc r3 = sc_mont(sR, yp);
-    t[0] = sc_add(t[0], sc_mont(l1, r0));
-    t[1] = sc_add(t[1], sc_add(sc_mont(l1, r1), sc_mont(l2, r0)));
-    t[2] = sc_add(t[2], sc_add(sc_mont(l2, r1), sc_mont(l3, r0)));
-    t[3] = sc_add(t[3], sc_add(sc_mont(l1, r3), sc_mont(l3, r1)));
-    t[4] = sc_add(t[4], sc_mont(l2, r3));
-    t[5] = sc_add(t[5], sc_mont(l3, r3));
-    uint32_t* v = vec + ((size_t)p * n_p + i) * POLY_SLOTS * 8;
-    sc_store(v + 0, l1);
-    sc_store(v + 8, r0);
-    sc_store(v + 16, r1);
-    sc_store(v + 24, r3);
-    sc_store(v + 32, l2);
-    sc_store(v + 40, l3);
-    sc_store(hf + ((size_t)p * n_p + i) * 8, sc_from_mont(yip));  // H factors y^-i
-  }
-  // tau_x's <z^Q W_V, gamma>: V column j of the fourth CSR block (Montgomery)
-  // times gamma_j (canonical) is canonical z^Q W_V[j] gamma_j; to_mont keeps
-  // the sum in the Montgomery domain of the other six
-  const uint32_t* cpv = cp + 3 * (n_p + 1);
-  const uint32_t* gam = gamma + 8 * (size_t)p * m;
-  for (uint32_t j = threadIdx.x; j < m; j += blockDim.x)
-    if (cpv[j + 1] - cpv[j] <= HEAVY_COL) t[6] = sc_add(t[6], sc_mont(col_sum(cpv, ce, j, zp), sc_to_mont(sc_load(gam + 8 * j))));
-  const uint32_t* heavy = cpv + m + 1;  // [count, columns...] (build_csr)
-  for (uint32_t h = 0; h < heavy[0]; ++h) {
-    const uint32_t j = heavy[1 + h];
-    const sc cs = col_sum_block(cpv, ce, j, zp, red);
-    if (threadIdx.x == 0) t[6] = sc_add(t[6], sc_mont(cs, sc_to_mont(sc_load(gam + 8 * j))));
-  }
-  sc_block_sum<POLY_NT>(t, red);
-  if (threadIdx.x == 0)
-    _Pragma("unroll") for (int j = 0; j < POLY_NT; ++j) sc_store(t_out + (POLY_NT * p + j) * 8, sc_from_mont(t[j]));
-}
+// (the kernel's text: poly_coef_kernel.inc)
+#define POLY_COEF_KERNEL k_poly_coef
+#define POLY_COEF_SPLIT false
+#include "poly_coef_kernel.inc"
+// the row table in two (RowPow): large circuits, or TILED
+#define POLY_COEF_KERNEL k_poly_coef_tiled
+#define POLY_COEF_SPLIT true
+#include "poly_coef_kernel.inc"
 
 // grid = P, block = poly_block(n_p)
 __global__ void __launch_bounds__(POLY_T) k_poly_x(uint32_t n_p, const uint32_t* __restrict__ xs,
@@ -501,7 +459,10 @@ __global__ void __launch_bounds__(64 * (VC_W + 1)) k_verify_consts(uint32_t coun
 // Montgomery values), added to the lane's own acc[1] before the block sum: no
 // barrier, no reduction and no LDS of its own, and a public input read by many
 // rows costs what its entries cost.  pub: [count][n_pub][8] words, canonical.
-template <bool DECK, bool PUB = false>
+//
+// SPLIT (the _tiled kernels; large circuits): the row table in two (RowPow);
+// dynamic LDS = perm::split_tables_lds(Q, n_p, 2).
+template <bool DECK, bool PUB = false, bool SPLIT = false>
 FE_INLINE void verify_scalars_body(uint32_t* lds, uint32_t n_p, uint32_t m, uint32_t Q, uint32_t lg,
                                    const uint32_t* __restrict__ rec, const uint32_t* __restrict__ kc,
                                    const uint32_t* __restrict__ cp, const uint32_t* __restrict__ ce,
@@ -512,11 +473,13 @@ FE_INLINE void verify_scalars_body(uint32_t* lds, uint32_t n_p, uint32_t m, uint
                                    const uint32_t* __restrict__ pub = nullptr, uint32_t n_pub = 0) {
   __builtin_amdgcn_s_setprio(2);  // (ahead of the proof-point decompression beside it)
   const uint32_t NY = min(n_p, (uint32_t)POW_LO);
-  uint32_t* zt = lds;                // [Q + 1] z^e, Montgomery
-  uint32_t* yt = zt + 8 * (Q + 1);   // [NY] y^e
+  const uint32_t NZ = SPLIT ? (uint32_t)ROW_LO : Q + 1, NH = SPLIT ? (Q >> ROW_LO_LG) + 1 : 0u;
+  uint32_t* zt = lds;                // [Q + 1] z^e, Montgomery; SPLIT: [ROW_LO] z^i
+  uint32_t* zh = zt + 8 * NZ;        // SPLIT: [NH] z^(ROW_LO j)
+  uint32_t* yt = zh + 8 * NH;        // [NY] y^e
   uint32_t* st = yt + 8 * NY;        // [NY] s_i / s_0 (below)
   uint32_t* red = st + 8 * NY;       // reduction scratch
-  const uint32_t* zp = zt + 8;       // z^(q+1)
+  const RowPow<SPLIT> zp = {SPLIT ? zt : zt + 8, zh};  // z^(q+1)
   const uint32_t p = blockIdx.x, nrec = VREC_U + lg;
   const uint32_t* R = rec + (size_t)p * nrec * 8;
   const uint32_t* K = kc + (size_t)p * VK_N * 8;
@@ -528,7 +491,7 @@ FE_INLINE void verify_scalars_body(uint32_t* lds, uint32_t n_p, uint32_t m, uint
   // verification_scalars): st[i] = s_i / s_0 for i < NY as a doubling table
   // over the factors u_{lg-1-k}^2, the bits from POW_LO_LG up per lane
   if (threadIdx.x == 0) {
-    sc_table_pow_init(zt, Q + 1, ldk(VK_Z), oneR);
+    sc_table_pow_init(zt, NZ, ldk(VK_Z), oneR);
     sc_table_pow_init(yt, NY, ldk(VK_Y), oneR);
     sc_store(st, oneR);
   }
@@ -536,7 +499,8 @@ FE_INLINE void verify_scalars_body(uint32_t* lds, uint32_t n_p, uint32_t m, uint
     const sc u = ldm(VREC_U + lg - 1 - b);
     sc_store(st + 8 * (1u << b), sc_mont(u, u));
   }
-  sc_tables3({zt, Q + 1, false}, {yt, NY, false}, {st, NY, true});
+  sc_tables3({zt, NZ, false}, {yt, NY, false}, {st, NY, true});
+  if constexpr (SPLIT) row_hi_table(zh, NH, zt, ldk(VK_Z), oneR);
   VS_T(1);
   auto s_of = [&](uint32_t i) {  // s_i / s_0
     sc v = sc_load(st + 8 * (i % POW_LO));
@@ -577,14 +541,14 @@ FE_INLINE void verify_scalars_body(uint32_t* lds, uint32_t n_p, uint32_t m, uint
   VS_T(2);
   for (uint32_t q = threadIdx.x; q < Q; q += blockDim.x) {
     const sc c = q + 1 == Q ? ldk(VK_NXP) : sc_to_mont(sc_load(cR + 8 * q));
-    acc[1] = sc_add(acc[1], sc_mont(sc_load(zp + 8 * q), c));
+    acc[1] = sc_add(acc[1], sc_mont(row_at(zp, q), c));
   }
   if constexpr (PUB) {
     const uint32_t* wv = wu + ((2 * n_wu + 7) & ~7u);
     const uint32_t* up = pub + 8 * (size_t)p * n_pub;
     for (uint32_t e = threadIdx.x; e < n_wu; e += blockDim.x) {
       const sc au = sc_mont(sc_load(wv + 8 * (size_t)e), sc_to_mont(sc_load(up + 8 * (size_t)wu[2 * e + 1])));
-      acc[1] = sc_add(acc[1], sc_mont(sc_load(zp + 8 * wu[2 * e]), au));
+      acc[1] = sc_add(acc[1], sc_mont(row_at(zp, wu[2 * e]), au));
     }
   }
   VS_T(3);
@@ -623,7 +587,7 @@ FE_INLINE void verify_scalars_body(uint32_t* lds, uint32_t n_p, uint32_t m, uint
       n = h;
       __syncthreads();
     }
-    if (threadIdx.x == 0) acc[1] = sc_add(acc[1], sc_mont(sc_load(zp + 8 * (Q - 2)), sc_load(prod)));
+    if (threadIdx.x == 0) acc[1] = sc_add(acc[1], sc_mont(row_at(zp, Q - 2), sc_load(prod)));
   }
   if (threadIdx.x == 0) {
     // B: wt (r F t_hat - r x^2 (delta' + F zc) + w F (a b - t_hat)); B_blinding: wt F (r tau_x + mu)
@@ -663,6 +627,24 @@ __global__ void __launch_bounds__(POLY_T) __attribute__((amdgpu_waves_per_eu(VS_
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   verify_scalars_body<false, true>(lds, n_p, m, Q, lg, rec, kc, cp, ce, cR, gen, sc_out, NG, npt, nullptr, 0, wu, n_wu,
                                    pub, n_pub);
+}
+
+#define VERIFY_SCALARS_ARGS                                                                                          \
+  uint32_t n_p, uint32_t m, uint32_t Q, uint32_t lg, const uint32_t *__restrict__ rec, const uint32_t *__restrict__ kc, \
+      const uint32_t *__restrict__ cp, const uint32_t *__restrict__ ce, const uint32_t *__restrict__ cR,            \
+      uint32_t *__restrict__ gen, uint32_t *__restrict__ sc_out, uint32_t NG, uint32_t npt
+#define VERIFY_SCALARS_PASS lds, n_p, m, Q, lg, rec, kc, cp, ce, cR, gen, sc_out, NG, npt, nullptr, 0
+// (dynamic LDS = perm::split_tables_lds(Q, n_p, 2))
+__global__ void __launch_bounds__(POLY_T) __attribute__((amdgpu_waves_per_eu(VS_WPE))) k_verify_scalars_tiled(
+    VERIFY_SCALARS_ARGS) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  verify_scalars_body<false, false, true>(VERIFY_SCALARS_PASS);
+}
+__global__ void __launch_bounds__(POLY_T) __attribute__((amdgpu_waves_per_eu(VS_WPE))) k_verify_scalars_pub_tiled(
+    VERIFY_SCALARS_ARGS, const uint32_t* __restrict__ wu, uint32_t n_wu, const uint32_t* __restrict__ pub,
+    uint32_t n_pub) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  verify_scalars_body<false, true, true>(VERIFY_SCALARS_PASS, wu, n_wu, pub, n_pub);
 }
 
 // sc_out[i] = sum_p gen[p][i] (one workgroup per generator column)
@@ -979,16 +961,33 @@ int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uin
 // every level reads them there; taken whenever they fit beside the wires
 // (circuit::witness_program_staged_lds), the plain form beyond.
 // dynamic LDS = 32 B (the fail word) + 3n x 32 B [+ (m_in + n_pub) x 32 B + the image].
-template <bool STAGE>
+//
+// WP_WIDE (k_witness_program_wide; large circuits, more than kLdsMax of wires):
+// the 3n wires live in this proof's rows of the global array wide_wires
+// ([P][3n][8] words, Montgomery form; "wp_wires", which prove_wipe zeroes),
+// program and inputs are read from global memory as in WP_GLOBAL, LDS holds the
+// fail word alone.  Phases and barriers are the same.  The wires are written and
+// read again by lanes of ONE workgroup across __syncthreads(): its
+// workgroup-scope release (the stores have left the wave before the barrier)
+// and acquire order them, and a workgroup's waves share their CU's vector L1,
+// so no wider scope is needed; each wave also drains its own stores (vmcnt(0))
+// before it arrives at such a barrier, which the workgroup-scope release alone
+// does not wait for on this target.  The array is reached through a plain pointer --
+// neither const nor __restrict__, which would let the compiler keep or hoist a
+// load of a wire over the barrier that publishes it.
+enum { WP_GLOBAL = 0, WP_STAGE = 1, WP_WIDE = 2 };
+template <int MODE>
 FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, uint32_t n_p, uint32_t n_aux, uint32_t A,
                                     uint32_t nlev, uint32_t per, const uint32_t* __restrict__ prog,
                                     uint32_t prog_words, uint32_t o_lc, uint32_t o_wire, uint32_t o_lev, uint32_t o_gate,
                                     uint32_t o_var, uint32_t o_coef, const uint32_t* __restrict__ vals,
                                     const uint32_t* __restrict__ aux, const uint32_t* __restrict__ xs,
                                     uint32_t* __restrict__ sc_out, uint32_t* __restrict__ fail, uint32_t n_pub,
-                                    const uint32_t* __restrict__ pubs) {
+                                    const uint32_t* __restrict__ pubs, uint32_t* wide_wires = nullptr) {
+  constexpr bool STAGE = MODE == WP_STAGE;
   uint32_t* bad = lds;                        // 1 + the first failing assert (8 words kept for alignment)
   uint32_t* wires = lds + 8;                  // [3n] Montgomery
+  if constexpr (MODE == WP_WIDE) wires = wide_wires + 8 * 3 * (size_t)n * blockIdx.x;
   uint32_t* vm = wires + 8 * 3 * (size_t)n;   // STAGE: [m_in] inputs, Montgomery
   uint32_t* um = vm + 8 * (size_t)m_in;       // STAGE: [n_pub] public inputs, Montgomery
   uint32_t* image = um + 8 * (size_t)n_pub;   // STAGE: [prog_words] the device image
@@ -1039,6 +1038,7 @@ FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, ui
                                   : sc_to_mont(sc_load(aux + 8 * ((size_t)p * n_aux + a)));
     sc_store(wires + 8 * (3 * (size_t)(u >> 1) + (u & 1u)), v);
   }
+  if constexpr (MODE == WP_WIDE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the wires' stores, below)
   __syncthreads();
   for (uint32_t lev = 0; lev < nlev; ++lev) {
     for (uint32_t u = lev_off[lev] + t; u < lev_off[lev + 1]; u += nt) {
@@ -1054,6 +1054,7 @@ FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, ui
       }
       sc_store(wires + 8 * (3 * (size_t)g + 2), sc_mont(side[0], side[1]));
     }
+    if constexpr (MODE == WP_WIDE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
   uint32_t* o = sc_out + 8 * (size_t)p * per;
@@ -1086,12 +1087,17 @@ FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, ui
       sc_out, fail, n_pub, pubs
 __global__ void __launch_bounds__(256) k_witness_program(WITNESS_PROGRAM_ARGS) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  witness_program_body<true>(lds, WITNESS_PROGRAM_PASS);
+  witness_program_body<WP_STAGE>(lds, WITNESS_PROGRAM_PASS);
 }
 // the plain form: program and inputs read from global memory
 __global__ void __launch_bounds__(256) k_witness_program_global(WITNESS_PROGRAM_ARGS) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  witness_program_body<false>(lds, WITNESS_PROGRAM_PASS);
+  witness_program_body<WP_GLOBAL>(lds, WITNESS_PROGRAM_PASS);
+}
+// the wide form: the wires in global memory too (wires: [P][3n][8] words)
+__global__ void __launch_bounds__(256) k_witness_program_wide(WITNESS_PROGRAM_ARGS, uint32_t* wires) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  witness_program_body<WP_WIDE>(lds, WITNESS_PROGRAM_PASS, wires);
 }
 
 int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
@@ -1100,13 +1106,15 @@ int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const 
   if (!P) return BPP_OK;
   const circuit::Program& G = *C.program;
   if (G.n_pub && !d_pub) return BPP_ERR_ARG;
-  const bool stage = circuit::witness_program_staged_lds(G) <= perm::kLdsMax;
-  const size_t lds = stage ? circuit::witness_program_staged_lds(G) : circuit::witness_program_lds(G.n);
-  if (lds > perm::kLdsMax) {
-    ctx->err = "witness_program_dev: gates beyond the kernel's LDS budget";
-    return BPP_ERR_LEN;
-  }
-  void* d_prog = nullptr;
+  // by size and flag: the wires in global memory (large circuits, or TILED),
+  // else in LDS with the program staged beside them while that fits
+  const bool wide = circuit::witness_wide(C);
+  const bool stage = !wide && circuit::witness_program_staged_lds(G) <= perm::kLdsMax;
+  const size_t lds = wide    ? circuit::witness_program_wide_lds()
+                     : stage ? circuit::witness_program_staged_lds(G)
+                             : circuit::witness_program_lds(G.n);
+  void *d_prog = nullptr, *d_wires = nullptr;
+  if (wide) BPP_TRY(ctx_ws(ctx, "wp_wires", (size_t)P * 3 * G.n * 32, &d_wires));  // (witness data: prove_wipe)
   BPP_TRY(ctx_ws(ctx, "wp_prog", G.dev.size() * 4, &d_prog));
   BPP_TRY(ctx_h2d_const(ctx, "wp_prog", d_prog, G.dev.data(), G.dev.size() * 4));  // the circuit: same every batch
   // whole waves, no more lanes than the padded gates (narrow levels leave the
@@ -1114,12 +1122,18 @@ int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const 
   const unsigned nt = std::min<unsigned>(256, std::max<unsigned>(64, (C.n_p + 63) & ~63u));
   {
     ProfScope ps(ctx, "witness_program");
-    hipLaunchKernelGGL(stage ? k_witness_program : k_witness_program_global, dim3(P), dim3(nt), lds, ctx->stream,
-                       G.m_in, G.n, C.n_p, G.n_aux, G.A, (uint32_t)G.level_off.size() - 1, per,
-                       (const uint32_t*)d_prog, (uint32_t)G.dev.size(), G.dev_lc_off, G.dev_lc_wire, G.dev_level_off,
-                       G.dev_level_gate, G.dev_vars, G.dev_coefs, d_vals, d_aux, d_x, d_sc, fail, G.n_pub, d_pub);
+#define WITNESS_PROGRAM_LAUNCH                                                                                      \
+  G.m_in, G.n, C.n_p, G.n_aux, G.A, (uint32_t)G.level_off.size() - 1, per, (const uint32_t*)d_prog,                \
+      (uint32_t)G.dev.size(), G.dev_lc_off, G.dev_lc_wire, G.dev_level_off, G.dev_level_gate, G.dev_vars, G.dev_coefs, \
+      d_vals, d_aux, d_x, d_sc, fail, G.n_pub, d_pub
+    if (wide)
+      hipLaunchKernelGGL(k_witness_program_wide, dim3(P), dim3(nt), lds, ctx->stream, WITNESS_PROGRAM_LAUNCH,
+                         (uint32_t*)d_wires);
+    else
+      hipLaunchKernelGGL(stage ? k_witness_program : k_witness_program_global, dim3(P), dim3(nt), lds, ctx->stream,
+                         WITNESS_PROGRAM_LAUNCH);
   }
-  return ctx_check_launch(ctx, stage ? "k_witness_program" : "k_witness_program_global");
+  return ctx_check_launch(ctx, wide ? "k_witness_program_wide" : stage ? "k_witness_program" : "k_witness_program_global");
 }
 
 int witness_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_pi, const uint32_t* d_x,
@@ -1231,14 +1245,15 @@ int poly_coef_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32
   BPP_TRY(ctx_h2d_const(ctx, "poly_cp", d_cp, cp.data(), cp.size() * 4));  // the circuit: same every batch
   BPP_TRY(ctx_h2d_const(ctx, "poly_ce", d_ce, ce.data(), ce.size() * 4));
   const unsigned nt = poly_block(C);
-  const size_t lds = perm::poly_coef_lds(C.Q, C.n_p);
+  const bool split = C.program && circuit::poly_coef_split(C);  // (a large circuit's row table, or TILED)
+  const size_t lds = split ? perm::split_tables_lds(C.Q, C.n_p, POLY_NT) : perm::poly_coef_lds(C.Q, C.n_p);
   {
     ProfScope ps(ctx, "poly_coef");
-    hipLaunchKernelGGL(k_poly_coef, dim3(P), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, per, d_sc,
+    hipLaunchKernelGGL(split ? k_poly_coef_tiled : k_poly_coef, dim3(P), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, per, d_sc,
                        (const uint32_t*)d_ch, (const uint32_t*)d_cp, (const uint32_t*)d_ce, d_gamma,
                        (uint32_t*)d_vec, (uint32_t*)d_hf, (uint32_t*)d_t);
   }
-  BPP_TRY(ctx_check_launch(ctx, "k_poly_coef"));
+  BPP_TRY(ctx_check_launch(ctx, split ? "k_poly_coef_tiled" : "k_poly_coef"));
   t.resize((size_t)P * POLY_NT);
   BPP_TRY(ctx_sync(ctx));
   memcpy(t.data(), d_t, (size_t)P * POLY_NT * 32);
@@ -1301,7 +1316,8 @@ int verify_scalars_dev_rec(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count,
   BPP_TRY(ctx_h2d_const(ctx, "vs_ce", d_ce, ce.data(), ce.size() * 4));
   BPP_TRY(ctx_h2d_const(ctx, "vs_c", d_c, cw.data(), cw.size() * 4));
   const unsigned nt = poly_block(C);
-  const size_t lds = perm::verify_scalars_lds(C.Q, C.n_p);
+  const bool split = C.program && circuit::verify_scalars_split(C);  // (a large circuit's row table, or TILED)
+  const size_t lds = split ? perm::split_tables_lds(C.Q, C.n_p, 2) : perm::verify_scalars_lds(C.Q, C.n_p);
   if (C.lg > VC_LGMAX) return BPP_ERR_LEN;  // (k_verify_consts' LDS tables)
   void *d_kc = nullptr, *d_deck = nullptr;
   BPP_TRY(ctx_ws(ctx, "vs_kc", (size_t)count * VK_N * 32, &d_kc));
@@ -1331,11 +1347,11 @@ int verify_scalars_dev_rec(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count,
                          C.Q, C.lg, d_rec, (const uint32_t*)d_kc, (const uint32_t*)d_cp, (const uint32_t*)d_ce,
                          (const uint32_t*)d_c, (uint32_t*)d_gen, d_sc, NG, npt, (const uint32_t*)d_deck, C.k);
     else if (C.n_pub)
-      hipLaunchKernelGGL(k_verify_scalars_pub, dim3(count), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, C.lg, d_rec,
+      hipLaunchKernelGGL(split ? k_verify_scalars_pub_tiled : k_verify_scalars_pub, dim3(count), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, C.lg, d_rec,
                          (const uint32_t*)d_kc, (const uint32_t*)d_cp, (const uint32_t*)d_ce, (const uint32_t*)d_c,
                          (uint32_t*)d_gen, d_sc, NG, npt, (const uint32_t*)d_wu, n_wu, d_pub, C.n_pub);
     else
-      hipLaunchKernelGGL(k_verify_scalars, dim3(count), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, C.lg, d_rec,
+      hipLaunchKernelGGL(split ? k_verify_scalars_tiled : k_verify_scalars, dim3(count), dim3(nt), lds, ctx->stream, C.n_p, C.m, C.Q, C.lg, d_rec,
                          (const uint32_t*)d_kc, (const uint32_t*)d_cp, (const uint32_t*)d_ce, (const uint32_t*)d_c,
                          (uint32_t*)d_gen, d_sc, NG, npt);
     hipLaunchKernelGGL(k_verify_merge, dim3(NG), dim3(POLY_T), 0, ctx->stream, count, NG, (const uint32_t*)d_gen,

@@ -483,7 +483,8 @@ int bpp_deck_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size
  * one workgroup's 64 KB of LDS -- (Q + 1 + 2 min(n_p, 256)) x 32 B + 896 B for
  * the polynomial and verifier kernels, i.e. Q <= 1507 at n_p >= 256, and
  * 3 n_gates x 32 B + 32 B for the witness kernel, i.e. n_gates <= 682.  512
- * gates with both sides defined (Q = 1025 + n_asserts) fit. */
+ * gates with both sides defined (Q = 1025 + n_asserts) fit.  Larger circuits:
+ * bpp_circuit_create_ex with BPP_CIRCUIT_LARGE, below. */
 typedef struct bpp_circuit bpp_circuit;
 #define BPP_SIDE_LC 0xFFFFFFFFu
 typedef struct {
@@ -600,6 +601,36 @@ int bpp_circuit_verify_batch_pub(bpp_ctx* ctx, const bpp_gens* g, const bpp_circ
 int bpp_circuit_verify_batch_each_pub(bpp_ctx* ctx, const bpp_gens* g, const bpp_circuit* c, size_t count,
                                       const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
                                       const uint8_t* pub, uint8_t* ok_out);
+
+/* ----------------------------------------------------- large circuits */
+/* The bounds of bpp_circuit_create and _create_pub (Q <= 1507, n_gates <= 682)
+ * are the size of one workgroup's 64 KB of LDS in three kernels, not the
+ * protocol's.  bpp_circuit_create_ex(desc, n_pub, flags, ..) is
+ * bpp_circuit_create_pub(desc, n_pub, ..) with flags:
+ *   BPP_CIRCUIT_LARGE  accept circuits beyond those bounds.  The bounds left
+ *     are m_in, n_aux <= 2^20, n_gates, n_asserts, n_pub <= 2^16 (BPP_ERR_LEN
+ *     beyond), the split row table's own LDS -- (256 + (Q >> 8) + 1 +
+ *     2 min(n_p, 256)) x 32 B + 896 B, below 64 KB for every Q those allow --
+ *     and n_p <= bpp_gens_len(g) at prove and verify time.  A batch of such a
+ *     circuit launches, each by its own bound, the polynomial and verifier
+ *     kernels that read z^e as lo[e mod 256] hi[e / 256] from two short tables
+ *     (where (Q + 1 + 2 min(n_p, 256)) x 32 B + 896 B exceeds 64 KB) and the
+ *     witness kernel that keeps its 3 n_gates wires in device memory (where
+ *     3 n_gates x 32 B + 32 B does; that array is part of what the prover wipes).
+ *     These paths are exercised up to n_p = 2048 and have not been run beyond it.
+ *   BPP_CIRCUIT_TILED  use those kernels even where the narrow ones fit
+ *     (implies LARGE; for tests and A/B measurements).
+ * flags = 0 is bpp_circuit_create_pub, bounds included; unknown flag bits are
+ * BPP_ERR_ARG.  Flags choose how a statement is computed and are no part of
+ * it: the digest, the matrices, the transcript, the proof bytes and the proof
+ * length do not depend on them, and a proof made under a circuit created with
+ * LARGE or TILED verifies under the same description created without them
+ * (where that can be created), and the reverse.  Every bpp_circuit_* entry
+ * point and bpp_verify_groups[_each] take such a circuit with no new argument;
+ * BPP_CIRCUIT_HOST_WITNESS=1 selects the host witness at every size. */
+#define BPP_CIRCUIT_LARGE 1u
+#define BPP_CIRCUIT_TILED 2u
+int bpp_circuit_create_ex(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags, bpp_circuit** out);
 
 /* Mixed batches: proofs of different statements verified in one call with ONE
  * GPU MSM.  A group is `count` proofs of one statement under one label: the
