@@ -58,7 +58,7 @@ struct bpp_ctx {
     bool busy = false;
     uint64_t ticket = 0;
     hipEvent_t done = nullptr;
-    uint32_t c = 0, wb = 0, Wn = 0, nterms = 1;
+    uint32_t c = 0, wb = 0, Wn = 0, nterms = 1, rshift = 0;  // (horner_host_terms)
     void* h = nullptr;  // window terms (child's pinned buffer)
   };
   MsmSlot msm_slot[BPP_MSM_INFLIGHT];

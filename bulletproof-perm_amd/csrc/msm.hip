@@ -63,7 +63,7 @@ int msm_engine(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx, con
                const uint32_t* d_tbl1, uint32_t n0, bool fb, uint32_t* terms_out, uint32_t rlog,
                uint32_t* rshift_out) {
   if (terms_out) *terms_out = 1;
-  if (rshift_out) *rshift_out = rlog + 6;
+  if (rshift_out) *rshift_out = rlog;
   const MsmGeom g = msm_geom(M, T, c, wb, Wn, fb);
   const size_t nseg = fb ? (size_t)M : (size_t)M * Wn;
   const size_t NB = nseg * g.B;
@@ -223,48 +223,36 @@ int msm_engine(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx, con
     }
     BPP_TRY(ctx_check_launch(ctx, "k_msm_fixup_heavy"));
     if (rlog != RWAVE_LOG && rlog != RWAVE_LOG_LONE) rlog = RWAVE_LOG;
-    uint32_t rl = rlog;
-    if (rlog == RWAVE_LOG_LONE) {
-      // an MSM alone: 2^rl buckets a lane with rl <= RWAVE_LOG_LONE, as few as
-      // keep >= 512 waves in flight (a window range of the split verifier
-      // MSM, 2 x 2^14 buckets, ran k_msm_reduce_wave<3> on 64 waves: 124 us
-      // of latency chain, tools/shard_model.py) and nw <= RWAVE_NW_MAX
-      while (rl > 0 && (((size_t)nseg * g.B) >> (6 + rl)) < 512 && (g.B >> (6 + rl - 1)) <= RWAVE_NW_MAX) --rl;
-    }
-    const uint32_t rshift = rl + 6;
-    if (terms_out && M == 1 && !fb && g.B >= (1u << rshift) && g.B <= ((uint32_t)RWAVE_NW_MAX << rshift)) {
-      // power-of-two weights left to the host Horner (k_msm_reduce_wave)
-      const uint32_t nw = g.B >> rshift;
-      uint32_t J = 0;
-      while ((1u << J) < nw) ++J;
-      void* part = nullptr;
-      BPP_TRY(ctx_ws(ctx, "msm_rpart", nseg * nw * 2 * P3_BYTES, &part));
-      BPP_TRY(ctx_ws(ctx, "msm_wsum_terms", nseg * (1 + J) * P3_BYTES, &wsum));
-      ProfScope ps(ctx, "msm_reduce");
-      if (rlog == RWAVE_LOG) {
-        hipLaunchKernelGGL(k_msm_reduce_wave<RWAVE_LOG>, dim3((unsigned)(nseg * nw)), dim3(64), 0, ctx->stream,
-                           (const uint32_t*)boff, K, (const uint32_t*)head, (const uint32_t*)tail,
-                           (const uint32_t*)bsum, g, (uint32_t*)part);
-        hipLaunchKernelGGL(k_msm_reduce_bits<RWAVE_LOG>, dim3((unsigned)(nseg * (1 + J))), dim3(64), 0, ctx->stream,
-                           (const uint32_t*)part, g, 1 + J, (uint32_t*)wsum);
-      } else {
-        auto launch = [&](auto kw, auto kb) {
-          hipLaunchKernelGGL(kw, dim3((unsigned)(nseg * nw)), dim3(64), 0, ctx->stream, (const uint32_t*)boff, K,
-                             (const uint32_t*)head, (const uint32_t*)tail, (const uint32_t*)bsum, g, (uint32_t*)part);
-          hipLaunchKernelGGL(kb, dim3((unsigned)(nseg * (1 + J))), dim3(64), 0, ctx->stream, (const uint32_t*)part, g,
-                             1 + J, (uint32_t*)wsum);
-        };
-        static_assert(RWAVE_LOG_LONE == 3, "lone reduce shapes 0..3");
-        switch (rl) {
-          case 0: launch(k_msm_reduce_wave<0>, k_msm_reduce_bits<0>); break;
-          case 1: launch(k_msm_reduce_wave<1>, k_msm_reduce_bits<1>); break;
-          case 2: launch(k_msm_reduce_wave<2>, k_msm_reduce_bits<2>); break;
-          default: launch(k_msm_reduce_wave<3>, k_msm_reduce_bits<3>); break;
-        }
+    if (terms_out && M == 1 && !fb && g.B >= (64u << rlog) && g.B <= ((uint32_t)RWAVE_NW_MAX << (rlog + 6))) {
+      // lane sums, then the fold into X and the bit sums Y_k, whose
+      // power-of-two weights are left to the host Horner
+      const uint32_t J = g.B >> rlog;  // lanes per segment
+      const uint32_t nt = std::min<uint32_t>(rlog == RWAVE_LOG ? RFOLD_T : RFOLD_T_LONE, J), q = J / nt;
+      static std::atomic<uint64_t> fold_attr{0};  // per device: 80 KB of dynamic LDS at 512 lanes
+      const uint64_t dev_bit = 1ull << (ctx->device & 63);
+      if (!(fold_attr.load() & dev_bit)) {
+        BPP_HIP(hipFuncSetAttribute((const void*)k_msm_reduce_fold, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    RFOLD_T_LONE * P3_BYTES));
+        fold_attr.fetch_or(dev_bit);
       }
-      BPP_TRY(ctx_check_launch(ctx, "k_msm_reduce_wave/bits"));
-      *terms_out = 1 + J;
-      if (rshift_out) *rshift_out = rshift;
+      uint32_t lj = 0, lq = 0;
+      while ((1u << lj) < J) ++lj;
+      while ((1u << lq) < q) ++lq;
+      void* part = nullptr;
+      BPP_TRY(ctx_ws(ctx, "msm_rpart", nseg * J * 2 * P3_BYTES, &part));
+      BPP_TRY(ctx_ws(ctx, "msm_wsum_terms", nseg * (1 + lj) * P3_BYTES, &wsum));
+      ProfScope ps(ctx, "msm_reduce");
+      auto launch = [&](auto kl) {
+        hipLaunchKernelGGL(kl, dim3((unsigned)(nseg * (J / 64))), dim3(64), 0, ctx->stream, (const uint32_t*)boff, K,
+                           (const uint32_t*)head, (const uint32_t*)tail, (const uint32_t*)bsum, g, (uint32_t*)part);
+      };
+      if (rlog == RWAVE_LOG) launch(k_msm_reduce_lanes<RWAVE_LOG>);
+      else launch(k_msm_reduce_lanes<RWAVE_LOG_LONE>);
+      hipLaunchKernelGGL(k_msm_reduce_fold, dim3((unsigned)(nseg * (2 + lq))), dim3(nt), (size_t)nt * P3_BYTES,
+                         ctx->stream, (const uint32_t*)part, J, (uint32_t)nseg, (uint32_t*)wsum);
+      BPP_TRY(ctx_check_launch(ctx, "k_msm_reduce_lanes/fold"));
+      *terms_out = 1 + lj;
+      if (rshift_out) *rshift_out = rlog;
       *d_wsum_out = (uint32_t*)wsum;
       return BPP_OK;
     }
@@ -323,7 +311,7 @@ int msm_single_dev(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx,
   // alone on the device: the latency-shaped bucket reduction
   const uint32_t rlog = RWAVE_LOG_LONE;
   uint32_t* d_ws = nullptr;
-  uint32_t nterms = 1, rshift = rlog + 6;
+  uint32_t nterms = 1, rshift = rlog;
   BPP_TRY(msm_engine(ctx, d_scal, d_pidx, nullptr, 1, (uint32_t)n, c, wb, Wn, d_tbl, &d_ws, d_tbl1, n0, false,
                      &nterms, rlog, &rshift));
   void* h = nullptr;
@@ -601,7 +589,7 @@ static int msm_submit(bpp_ctx* ctx, const void* d_scalars, const void* h_scalars
     // accumulations measured slower, 1.17 vs 1.04 ms per 2^20 MSM)
     uint32_t* d_ws = nullptr;
     const int rc = msm_engine(ch, (const uint32_t*)d_scalars, nullptr, nullptr, 1, (uint32_t)n, c, w_begin, sl.Wn,
-                              tbl->d, &d_ws, nullptr, 0xffffffffu, false, &sl.nterms);
+                              tbl->d, &d_ws, nullptr, 0xffffffffu, false, &sl.nterms, RWAVE_LOG, &sl.rshift);
     if (rc) {
       ctx->err = ch->err;
       return rc;
@@ -647,7 +635,7 @@ int bpp_msm_collect(bpp_ctx* ctx, uint64_t ticket, uint8_t out[32], uint8_t part
     }
     sl.busy = false;
     h25519::ge r = h25519::ge_identity();
-    if (sl.h && sl.Wn) r = horner_host_terms((const uint32_t*)sl.h, sl.Wn, sl.nterms, sl.c, sl.wb);
+    if (sl.h && sl.Wn) r = horner_host_terms((const uint32_t*)sl.h, sl.Wn, sl.nterms, sl.c, sl.wb, sl.rshift);
     sl.h = nullptr;
     if (out) h25519::encode(out, r);
     if (partial) h25519::ge_to_words((uint32_t*)partial, r);
@@ -978,16 +966,16 @@ int msm_multi(bpp_ctx* ctx, const uint32_t* d_scal, const uint32_t* d_pidx, cons
   const uint32_t c = msm_choose_c((double)T / (double)M);
   const uint32_t W = (254 + c - 1) / c;
   uint32_t* d_ws = nullptr;
-  uint32_t nterms = 1;
+  uint32_t nterms = 1, rshift = 0;
   BPP_TRY(msm_engine(ctx, d_scal, d_pidx, (const uint32_t*)d_off, M, T, c, 0, W, d_tbl, &d_ws, d_tbl1, n0, false,
-                     M == 1 ? &nterms : nullptr));
+                     M == 1 ? &nterms : nullptr, RWAVE_LOG, &rshift));
   if (M <= 8) {
     void* h = nullptr;
     BPP_TRY(ctx_pinned(ctx, (size_t)M * W * nterms * P3_BYTES, &h));
     BPP_HIP(hipMemcpyAsync(h, d_ws, (size_t)M * W * nterms * P3_BYTES, hipMemcpyDeviceToHost, ctx->stream));
     BPP_TRY(ctx_sync(ctx));
     for (uint32_t m = 0; m < M; ++m)
-      out[m] = horner_host_terms((const uint32_t*)h + (size_t)m * W * nterms * P3_WORDS, W, nterms, c, 0);
+      out[m] = horner_host_terms((const uint32_t*)h + (size_t)m * W * nterms * P3_WORDS, W, nterms, c, 0, rshift);
     return BPP_OK;
   }
   const MsmGeom g = msm_geom(M, T, c, 0, W);

@@ -23,6 +23,7 @@
 //   n*W mixed adds (K4) + W*2^c full adds (K5) + (W-1)*c doublings (K6).
 #pragma once
 #include "ge_io.cuh"
+#include "dt_walk.cuh"  // block tree of k_msm_reduce_fold and k_dt_msm
 
 // Bits [pos, pos+c) of a 256-bit little-endian scalar (c <= 24).
 FE_INLINE uint32_t scalar_bits(const uint32_t s[8], int pos, int c) {
@@ -388,17 +389,6 @@ FE_INLINE ge_p3 ge_shfl_xor(const ge_p3& a, int m) {
   }
   return o;
 }
-// value of lane (self + d) of the wave (d < 64; lanes past the end read their own)
-FE_INLINE ge_p3 ge_shfl_down(const ge_p3& a, int d) {
-  ge_p3 o;
-  _Pragma("unroll") for (int k = 0; k < FE_LIMBS; ++k) {
-    o.X.v[k] = __shfl_down(a.X.v[k], d, 64);
-    o.Y.v[k] = __shfl_down(a.Y.v[k], d, 64);
-    o.Z.v[k] = __shfl_down(a.Z.v[k], d, 64);
-    o.T.v[k] = __shfl_down(a.T.v[k], d, 64);
-  }
-  return o;
-}
 #define RED_LMAX 8
 FE_INLINE ge_p3 lds_tree_sum(uint32_t* lds, ge_p3 v) {
   store_p3(lds, threadIdx.x, v);
@@ -455,89 +445,143 @@ __global__ void __launch_bounds__(RED_T) k_msm_reduce_final(const uint32_t* __re
   if (threadIdx.x == 0) store_p3(wsum, seg, tot);
 }
 
-// Bucket reduction for one large MSM (B >= 1024 buckets per window) whose
+// Bucket reduction for one large MSM (64 L <= B buckets per window) whose
 // power-of-two weights are left to the host Horner, which doubles between
-// windows anyway.  With L = RWAVE_L buckets per lane and
-// b = 64 L w + L t + i (wave w, lane t, i < L):
-//   sum_b (b+1) S_b = sum_{w,t} acc_{w,t}            acc = sum_i (i+1) S_b
-//                   + L sum_w sum_{t>=1} suf_{w,t}    suf = suffix sum of the lanes' run = sum_i S_b
-//                   + 64 L sum_w w R_w                R_w = suf_{w,0}
-// k_msm_reduce_wave: one 64-lane wave per (segment, w): 2L running-sum
-//   additions per lane, a 6-step suffix scan, v = acc + L suf (t >= 1), a
-//   6-step butterfly; writes V_w = sum_t v and R_w.
-// k_msm_reduce_bits: one wave per (segment, term): term 0 is X = sum_w V_w,
-//   term 1 + j is Y_j = sum_{w : bit j of w} R_w, so that
-//   sum_b (b+1) S_b = X + sum_j 2^(log2(64 L)+j) Y_j (horner_host_terms).
-// In a stream of MSMs (bpp_msm_submit) L = 16 (32 waves per 2^15-bucket window): 2^20 three in flight 0.888 /
-// 0.892 ms per MSM against 0.913 / 0.899 at L = 8 (whose reduce costs more
-// issue slots: 12 scan / butterfly additions per 8 buckets instead of per
-// 16); alone the reduce takes 0.233 vs 0.170 ms and L = 32 0.339 ms
-// (0.899 / 0.904 pipelined).  An MSM that runs alone (bpp_msm, the verifier's
-// single MSM) has idle SIMDs to spare and uses L = 8: twice the waves of the
-// stream shape, 2/3 of its serial chain (msm_single_dev; config 5's 17 x 2^14
-// buckets, two interleaved passes: reduce 0.159-0.166 ms at L = 8 against
-// 0.205-0.209 at L = 4, 0.231-0.234 at 2, 0.228-0.231 at 16, 0.363-0.387 at
-// 32 -- the 12 scan / butterfly additions per lane, not the chain, set the
-// cost; profiles/r05_reduce_l_ab.txt).
+// windows anyway.  Lane j of a segment owns buckets b = L j + i, i < L:
+//   sum_b (b+1) S_b = sum_j acc_j + L sum_j j run_j
+//                   = X + sum_k 2^(log2 L + k) Y_k,   Y_k = sum_{j : bit k of j} run_j
+// over all J = B / L lanes of the segment (horner_host_terms, rshift = log2 L).
+// k_msm_reduce_lanes: one 64-lane wave per 64 lanes: the descending running
+//   sums acc_j = sum_i (i+1) S_b, run_j = sum_i S_b with the first non-empty
+//   bucket peeled (run = S, acc = run), stored for every lane.  No scan,
+//   doubling or butterfly: at most 2L - 2 additions a lane, none in a lane
+//   whose buckets are all empty.
+// k_msm_reduce_fold: blocks of nt = min(RFOLD_T or RFOLD_T_LONE, J) lanes,
+//   2 + log2 q blocks per segment with q = J / nt; lane t of a block sums
+//   over j = i nt + t:
+//     block 0      X: q - 1 additions a lane, then the block tree (nt - 1);
+//     block 1      r_t = sum_i run_j, q - 1 a lane, then the bit tree: level
+//                  s folds the upper half of the node row onto the lower and
+//                  leaves it in place as the row of bit log2 nt - 1 - s of t,
+//                  and halves every earlier row the same way, (s + 1) nt /
+//                  2^(s+1) additions, < 2 nt in all; Y_k ends in slot 2^k;
+//     block 2 + k  Y_(log2 nt + k): the i with bit k set, q / 2 - 1 a lane,
+//                  then the block tree.
+//   A run_j joins r_t and half of the log2 q upper-bit sums (q = 8 in both
+//   shapes at 2^15 buckets: 2.5 sums), an acc_j one; every later addition is
+//   among nt values, whatever J.  Both trees give a level of at most nt / 4
+//   additions four lanes per addition (ge_add_quad).
+// Issue, in wave-wide additions per wave of the lane kernel (J / 64 of them
+// per segment), stream shape L = 16, B = 2^15, J = 2048, nt = 256, q = 8:
+//   lanes 2L - 2 = 30.  Fold: X 4 x 7 and its block tree 2 + (4 + 2 + 1 + 4)
+//   waves, the bracket quad additions at a third of the multiplies; r_t 4 x 7
+//   and the bit tree 2 + 2 + 2 + (4 + 3 + 2 + 1 + 1); three upper-bit blocks
+//   4 x 3 + 13 each: 161 per 32 waves = 5.0 with a quad addition counted as
+//   a whole one, 3.9 by its multiplies: 2L + 3.0 of the budget 2L + 5
+//   (k_msm_reduce_wave + k_msm_reduce_bits before: 2L + 17 and a second
+//   butterfly).
+// Chain, first bucket load to last term: 2L - 2 in the lane, q - 1 + log2 nt
+//   in the fold: 2L + 13 in the stream, 2L + 14 alone (L = 8, nt = 512,
+//   q = 8), of the budget 2L + 24.
+// VGPRs (gfx950): k_msm_reduce_lanes<4> 245, <3> 237 (k_msm_reduce_wave<4>:
+//   256 and 1 wave per SIMD); k_msm_reduce_fold 187.
+// L: in a stream of MSMs (bpp_msm_submit) 16, alone (bpp_msm, the verifier's
+// single MSM: idle SIMDs to spare, latency counts) 8; L = 8 in the stream
+// measured 0.844-0.848 against 0.842-0.857 ms per MSM and the fold at 512
+// lanes 0.850-0.861 (no separation; profiles/r07_reduce_ab.txt), alone the
+// fold at 512 lanes takes 0.180-0.182 ms against 0.188-0.190 at 256.
 #ifndef RWAVE_LOG
 #define RWAVE_LOG 4  // log2 buckets per lane (MSM streams)
 #endif
 #ifndef RWAVE_LOG_LONE
 #define RWAVE_LOG_LONE 3  // log2 buckets per lane when the MSM runs alone (latency)
 #endif
-#define RWAVE_L (1 << RWAVE_LOG)
-#define RWAVE_SHIFT (RWAVE_LOG + 6)  // log2(RWAVE_L * 64)
-#define RWAVE_NW_MAX 256             // waves per segment k_msm_reduce_bits folds
+#define RWAVE_NW_MAX 256  // B <= 64 L RWAVE_NW_MAX buckets per window
+#define RFOLD_T 256       // lanes of a k_msm_reduce_fold block in MSM streams (40 KB of LDS)
+#define RFOLD_T_LONE 512  // ... of an MSM that runs alone (80 KB)
 template <int LOG>
-__global__ void __launch_bounds__(64) k_msm_reduce_wave(const uint32_t* __restrict__ boff, uint32_t K,
-                                                       const uint32_t* __restrict__ head,
-                                                       const uint32_t* __restrict__ tail,
-                                                       const uint32_t* __restrict__ bsum, MsmGeom g,
-                                                       uint32_t* __restrict__ part) {
+__global__ void __launch_bounds__(64) k_msm_reduce_lanes(const uint32_t* __restrict__ boff, uint32_t K,
+                                                        const uint32_t* __restrict__ head,
+                                                        const uint32_t* __restrict__ tail,
+                                                        const uint32_t* __restrict__ bsum, MsmGeom g,
+                                                        uint32_t* __restrict__ part) {
   constexpr uint32_t L = 1u << LOG;
-  const uint32_t nw = g.B >> (LOG + 6);
-  const uint32_t seg = blockIdx.x / nw, w = blockIdx.x % nw;
-  const uint32_t t = threadIdx.x;
-  const uint32_t lo = (w * 64 + t) * L;
-  const size_t base = (size_t)seg * g.B + lo;
+  const size_t lane = (size_t)blockIdx.x * 64 + threadIdx.x;  // seg * J + j
+  const size_t base = lane * L;                               // seg * B + L j
+  const size_t lanes = (size_t)gridDim.x * 64;
   uint32_t bo[L + 1];
   _Pragma("unroll") for (uint32_t k = 0; k <= L; ++k) bo[k] = boff[base + k];
   ge_p3 run = ge_identity();
   ge_p3 acc = ge_identity();
   // a lane whose buckets are all empty (most of the narrow top window's)
-  // keeps run = acc = identity without the additions
-  if (bo[0] != bo[L])
+  // stores run = acc = identity without an addition
+  if (bo[0] != bo[L]) {
+    bool have = false;  // a non-empty bucket seen: run and acc hold points
     for (int i = (int)L - 1; i >= 0; --i) {
-      if (bo[i] != bo[i + 1]) run = ge_add(run, bucket_total(base + i, bo[i], bo[i + 1], K, head, tail, bsum));
-      acc = ge_add(acc, run);
+      const bool ne = bo[i] != bo[i + 1];
+      if (ne) {
+        const ge_p3 s = bucket_total(base + i, bo[i], bo[i + 1], K, head, tail, bsum);
+        if (have) run = ge_add(run, s);
+        else run = s;
+      }
+      if (have) acc = ge_add(acc, run);
+      else if (ne) acc = run;
+      have |= ne;
     }
-  ge_p3 suf = run;  // inclusive suffix sum over lanes t..63
-  _Pragma("unroll") for (int d = 1; d < 64; d <<= 1) {
-    const ge_p3 s2 = ge_add(suf, ge_shfl_down(suf, d));
-    if (t + d < 64) suf = s2;
   }
-  ge_p3 sufL = suf;  // L * suf
-  _Pragma("unroll") for (int k = 0; k < LOG; ++k) sufL = ge_dbl(sufL);
-  ge_p3 v = ge_add(acc, sufL);
-  if (t == 0) v = acc;
-  _Pragma("unroll") for (int k = 1; k < 64; k <<= 1) v = ge_add(v, ge_shfl_xor(v, k));
-  if (t == 0) {
-    store_p3(part, 2 * (size_t)blockIdx.x, v);
-    store_p3(part, 2 * (size_t)blockIdx.x + 1, suf);  // lane 0: R_w
-  }
+  store_p3(part, lane, acc);
+  store_p3(part, lanes + lane, run);
 }
 
-// terms per segment = 1 + log2(nw); lane t folds waves t, t + 64, ...
-template <int LOG>
-__global__ void __launch_bounds__(64) k_msm_reduce_bits(const uint32_t* __restrict__ part, MsmGeom g,
-                                                       uint32_t nterms, uint32_t* __restrict__ out) {
-  const uint32_t nw = g.B >> (LOG + 6);
-  const uint32_t seg = blockIdx.x / nterms, term = blockIdx.x % nterms;
-  ge_p3 v = ge_identity();
-  for (uint32_t w = threadIdx.x; w < nw; w += 64)
-    if (term == 0 || ((w >> (term - 1)) & 1u)) v = ge_add(v, load_p3(part, 2 * ((size_t)seg * nw + w) + (term ? 1 : 0)));
-  _Pragma("unroll") for (int k = 1; k < 64; k <<= 1) v = ge_add(v, ge_shfl_xor(v, k));
-  if (threadIdx.x == 0) store_p3(out, blockIdx.x, v);
+// part: acc of every lane (nseg * J points), then run of every lane; out:
+// nterms = 1 + log2 J points per segment, X then Y_0, Y_1, ...
+__global__ void __launch_bounds__(RFOLD_T_LONE) k_msm_reduce_fold(const uint32_t* __restrict__ part, uint32_t J,
+                                                                 uint32_t nseg, uint32_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t tl[];  // blockDim.x extended points
+  const uint32_t nt = blockDim.x, t = threadIdx.x;               // a power of two, <= J
+  const uint32_t q = J / nt;
+  const uint32_t ln = 31 - __clz(nt), lq = 31 - __clz(q);
+  const uint32_t nterms = 1 + ln + lq;
+  const uint32_t seg = blockIdx.x / (2 + lq), role = blockIdx.x % (2 + lq);
+  const uint32_t* src = part + ((size_t)(role ? nseg : 0) * J + (size_t)seg * J) * P3_WORDS;
+  const size_t o = (size_t)seg * nterms;
+  if (role >= 2) {  // Y_(ln + k): lanes j = i nt + t with bit k of i
+    const uint32_t bit = 1u << (role - 2);
+    ge_p3 v = load_p3(src, (size_t)bit * nt + t);
+    for (uint32_t i = bit + 1; i < q; ++i)
+      if (i & bit) v = ge_add(v, load_p3(src, (size_t)i * nt + t));
+    dt_block_tree(tl, v, nt, out, (uint32_t)(o + 1 + ln + (role - 2)));
+    return;
+  }
+  ge_p3 v = load_p3(src, t);
+  for (uint32_t i = 1; i < q; ++i) v = ge_add(v, load_p3(src, (size_t)i * nt + t));
+  if (role == 0) {
+    dt_block_tree(tl, v, nt, out, (uint32_t)o);
+    return;
+  }
+  // bit tree: row 0 = nodes in slots [0, 2h), row p >= 1 = the partial sums
+  // of bit ln - p in slots [nt >> p, (nt >> p) + 2h)
+  lds_store_p3(tl, nt, t, v);
+  __syncthreads();
+  for (uint32_t s = 0, h = nt >> 1; h > 0; ++s, h >>= 1) {
+    const uint32_t na = (s + 1) * h;  // additions at this level
+    if (4 * na > nt) {
+      if (t < na) {
+        const uint32_t row = t >> (ln - 1 - s), m = t & (h - 1u);
+        const uint32_t p = (row ? nt >> row : 0u) + m;
+        lds_store_p3(tl, nt, p, ge_add(lds_load_p3(tl, nt, p), lds_load_p3(tl, nt, p + h)));
+      }
+    } else if ((t & ~63u) < 4 * na) {  // wave-uniform: four lanes per addition (dt_block_tree_segs)
+      const uint32_t i = t >> 2, c = t & 3;
+      const bool live = i < na;
+      const uint32_t row = i >> (ln - 1 - s), m = i & (h - 1u);
+      const uint32_t p = live ? (row ? nt >> row : 0u) + m : 0u;
+      const fe r = ge_add_quad(lds_load_p3(tl, nt, p), lds_load_p3(tl, nt, live ? p + h : 0u), c);
+      if (live) lds_store_coord(tl, nt, p, c, r);
+    }
+    __syncthreads();
+  }
+  if (t < ln) store_p3(out, o + 1 + t, lds_load_p3(tl, nt, 1u << t));
 }
 
 // One lane per MSM: Horner over its W window sums.

@@ -21,13 +21,13 @@ def main():
     ev.sort()
     last = max(i for i, e in enumerate(ev) if "k_verify_replay_g" in e[2])
     j = last
-    while j > 0 and "reduce_bits" not in ev[j][2]:
+    while j > 0 and "reduce_fold" not in ev[j][2]:
         j -= 1
     t0 = ev[j + 1][0]
     print("start_us  end_us  dur_us  event")
     for e in ev[j + 1:]:
         print("%8.1f %8.1f %7.1f  %s" % ((e[0] - t0) / 1e3, (e[1] - t0) / 1e3, (e[1] - e[0]) / 1e3, e[2]))
-        if "reduce_bits" in e[2]:
+        if "reduce_fold" in e[2]:
             break
 
 
