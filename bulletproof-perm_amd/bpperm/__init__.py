@@ -108,6 +108,21 @@ class Context:
         check(self.lib.bpp_debug_secret_residue(self.h, C.byref(nz)), "bpp_debug_secret_residue", self.h)
         return nz.value
 
+    def circuit_hints(self, circuit, v, pub=None) -> "list[list[bytes]]":
+        """The hint kernel alone (bpp_debug_circuit_hints; a test hook): v[p] =
+        the m_in inputs of proof p, pub[p] = its n_pub public inputs (32-byte
+        scalars, or each proof's joined) -> each proof's n_aux derived values."""
+        count = len(v)
+        row = lambda rows, what: b"".join(x if isinstance(x, (bytes, bytearray)) else _join(x, 32, what) for x in rows)
+        vb, ub = row(v, "v"), row(pub, "pub") if pub is not None else b""
+        if len(vb) != 32 * circuit.m_in * count or len(ub) != 32 * circuit.n_pub * count:
+            raise ValueError("circuit_hints: expected m_in scalars in v and n_pub in pub per proof")
+        n = circuit.n_aux
+        out = C.create_string_buffer(max(32 * n * count, 1))
+        check(self.lib.bpp_debug_circuit_hints(self.h, circuit.h, count, _buf(vb), _buf(ub), out),
+              "bpp_debug_circuit_hints", self.h)
+        return [[out.raw[32 * (p * n + i):32 * (p * n + i) + 32] for i in range(n)] for p in range(count)]
+
     # ---------------------------------------------------------- profiling
     def profile(self, enable: bool = True):
         check(self.lib.bpp_ctx_profile(self.h, 1 if enable else 0), "bpp_ctx_profile", self.h)
@@ -780,6 +795,11 @@ class _CircuitDescC(C.Structure):
                 ("lc_var", C.POINTER(C.c_uint32)), ("lc_coef", C.c_char_p)]
 
 
+class _CircuitHintsC(C.Structure):
+    _fields_ = [("op", C.POINTER(C.c_uint32)), ("lc_off", C.POINTER(C.c_uint32)), ("lc_var", C.POINTER(C.c_uint32)),
+                ("lc_coef", C.c_char_p)]
+
+
 class Circuit:
     """A compiled caller-defined circuit (bpp_circuit_create, or
     bpp_circuit_create_pub when desc.n_pub; no GPU): desc is a
@@ -790,11 +810,16 @@ class Circuit:
     one-workgroup LDS bounds (682 gates, Q = 1507); tiled=True
     (BPP_CIRCUIT_TILED, implies large) uses the large-circuit kernels even where
     the narrow ones fit.  Neither is part of the statement: digest, matrices and
-    proof bytes are the same."""
+    proof bytes are the same.  A desc with hints (desc.hints, a
+    gadgets.CircuitHints: one hint per auxiliary value) is created through
+    bpp_circuit_create_hinted, and CircuitProver.prove_batch then derives aux
+    on the GPU; hints=False forces the plain entry point.  Hints are no part
+    of the statement either."""
 
     LARGE, TILED = 1, 2  # BPP_CIRCUIT_LARGE, BPP_CIRCUIT_TILED
 
-    def __init__(self, desc, large: bool = False, tiled: bool = False, flags: "int | None" = None):
+    def __init__(self, desc, large: bool = False, tiled: bool = False, flags: "int | None" = None,
+                 hints: bool = True):
         """flags: the raw flag word in place of large / tiled (tests)."""
         self.lib = _lib.load()
         self.desc = desc
@@ -806,7 +831,18 @@ class Circuit:
         d = _CircuitDescC(desc.m_in, desc.n_gates, desc.n_aux, desc.n_asserts, self._keep[0], self._keep[1],
                           self._keep[2], self._keep[3])
         h = C.c_void_p()
-        if flags:
+        hd = getattr(desc, "hints", None) if hints else None
+        if hd is not None:
+            # (the C struct carries no count: one hint per auxiliary value is checked here)
+            if len(hd.op) != desc.n_aux or len(hd.lc_off) != desc.n_aux + 1:
+                raise ValueError("hints: one hint per auxiliary value (op [n_aux], lc_off [n_aux + 1])")
+            if len(hd.lc_var) != len(hd.lc_coef) or (hd.lc_off and hd.lc_off[-1] > len(hd.lc_var)):
+                raise ValueError("hints: lc_var / lc_coef shorter than lc_off says")
+            self._keep_hints = (u32a(hd.op), u32a(hd.lc_off), u32a(hd.lc_var), b"".join(hd.lc_coef))
+            hc = _CircuitHintsC(*self._keep_hints)
+            check(self.lib.bpp_circuit_create_hinted(C.byref(d), getattr(desc, "n_pub", 0), flags, C.byref(hc),
+                                                     C.byref(h)), "bpp_circuit_create_hinted")
+        elif flags:
             check(self.lib.bpp_circuit_create_ex(C.byref(d), getattr(desc, "n_pub", 0), flags, C.byref(h)),
                   "bpp_circuit_create_ex")
         elif getattr(desc, "n_pub", 0):
@@ -815,6 +851,7 @@ class Circuit:
             check(self.lib.bpp_circuit_create(C.byref(d), C.byref(h)), "bpp_circuit_create")
         self.h = h
         self.n_pub = int(self.lib.bpp_circuit_n_pub(h))
+        self.has_hints = bool(self.lib.bpp_circuit_has_hints(h))
         n_p, Q, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
         dg = C.create_string_buffer(32)
         check(self.lib.bpp_circuit_info(h, C.byref(n_p), C.byref(Q), C.byref(m), dg), "bpp_circuit_info")
@@ -845,6 +882,18 @@ class Circuit:
         val = C.create_string_buffer(max(32 * cnt, 1))
         check(self.lib.bpp_circuit_matrix(self.h, which, q, col, val, C.byref(n)), "bpp_circuit_matrix")
         return [(q[i], col[i], val.raw[32 * i:32 * i + 32]) for i in range(cnt)]
+
+    def hint_eval(self, v, pub=None):
+        """The hints' host reference (bpp_circuit_hint_eval; no GPU): the n_aux
+        auxiliary values, 32-byte scalars, from v (m_in scalars) and pub (the
+        n_pub public inputs)."""
+        vb = _join(v, 32, "v")
+        ub = _join(pub, 32, "pub") if pub is not None else b""
+        if len(vb) != 32 * self.m_in or len(ub) != 32 * self.n_pub:
+            raise ValueError("hint_eval: expected m_in scalars in v and n_pub in pub")
+        out = C.create_string_buffer(max(32 * self.n_aux, 1))
+        check(self.lib.bpp_circuit_hint_eval(self.h, _buf(vb), _buf(ub), out), "bpp_circuit_hint_eval")
+        return [out.raw[32 * i:32 * i + 32] for i in range(self.n_aux)]
 
     def eval(self, v, aux, x: bytes, pub=None):
         """The host witness: (a_L, a_R, a_O) as lists of n_p 32-byte scalars,
@@ -891,7 +940,8 @@ class CircuitProver:
                     out: "tuple | None" = None, pub=None):
         """v[p] = the m_in committed inputs of proof p, aux[p] = its n_aux
         auxiliary values, gammas[p] = the m_in blindings of V_0..V_{m_in-1}
-        (None: drawn) -- 32-byte scalars (or each proof's joined); seeds32 = 32
+        (None: drawn) -- 32-byte scalars (or each proof's joined); aux = None on
+        a circuit with hints: derived on the GPU from v and pub; seeds32 = 32
         bytes per proof (None: the OS CSPRNG).  out = (proofs, V) ctypes buffers
         to write into instead of fresh ones.  pub[p] = the n_pub public inputs
         of proof p (bpp_circuit_prove_batch_pub; None: the entry point without
@@ -904,7 +954,8 @@ class CircuitProver:
         if len(vb) != 32 * c.m_in * count:
             raise ValueError("v: expected m_in scalars of 32 bytes per proof")
         ab = row(aux, "aux") if aux is not None else b""
-        if len(ab) != 32 * c.n_aux * count:
+        # (no aux on a circuit with hints: NULL, and the library derives the values on the GPU)
+        if len(ab) != 32 * c.n_aux * count and not (aux is None and c.has_hints):
             raise ValueError("aux: expected n_aux scalars of 32 bytes per proof")
         gb = None
         if gammas is not None:

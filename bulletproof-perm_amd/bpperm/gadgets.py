@@ -13,6 +13,14 @@ A linear combination (LC) is built from b.input(), b.challenge, b.public()
 A defined side may read wires of EARLIER gates only.  b.free_mul() makes a gate
 whose two sides are fed from the per-proof auxiliary values (its two aux
 indices are 2t, 2t + 1 for the t-th free gate, left then right).
+
+b.hint(op, lc, arg) makes one free side WITH the rule the prover derives its
+value by (bpp_circuit_hints): aux = op(lc mod l), lc over {1, v_j, u_i}.  mul()
+takes it on either side.  When every auxiliary value has a hint, build() emits
+them (CircuitDesc.hints) and the prover needs no aux from its caller:
+
+    inv = b.hint(HINT_INV, v0 - v1)
+    b.assert_zero(b.mul(v0 - v1, inv)[2] - 1)   # v0 != v1
 """
 from __future__ import annotations
 
@@ -23,6 +31,9 @@ L = 2**252 + 27742317777372353535851937790883648493
 SIDE_LC = 0xFFFFFFFF
 
 _ONE, _V, _X, _U, _W = 0, 1, 2, 3, 4  # variable kinds, in id order (_U: public inputs)
+
+# BPP_HINT_*: aux = w, bit `arg` of w, 1 - that bit, w^-1 (0 for 0), [w = 0]
+HINT_VALUE, HINT_BIT, HINT_NOT_BIT, HINT_INV, HINT_IS_ZERO = 0, 1, 2, 3, 4
 
 
 class LC:
@@ -68,6 +79,25 @@ class LC:
 
 
 @dataclass
+class CircuitHints:
+    """The arrays of bpp_circuit_hints: one hint per auxiliary value.  op[t] =
+    HINT_* | arg << 8; the terms of hint t are lc_var / lc_coef [lc_off[t],
+    lc_off[t + 1])."""
+    op: list
+    lc_off: list
+    lc_var: list
+    lc_coef: list
+
+
+class Hint:
+    """A free gate side with a hint (CircuitBuilder.hint): aux index `index`."""
+    __slots__ = ("index",)
+
+    def __init__(self, index: int):
+        self.index = index
+
+
+@dataclass
 class CircuitDesc:
     """The arrays of bpp_circuit_desc.  lc_coef: one 32-byte little-endian
     scalar per term."""
@@ -83,6 +113,8 @@ class CircuitDesc:
     aux_of: "Callable[[Sequence[int]], list] | None" = field(default=None, compare=False)
     # public inputs u_0..u_{n_pub-1} (bpp_circuit_create_pub's argument, not an array of bpp_circuit_desc)
     n_pub: int = 0
+    # the hint program (bpp_circuit_create_hinted), no part of the statement; None: aux is the caller's
+    hints: "CircuitHints | None" = field(default=None, compare=False)
 
     def coef_bytes(self) -> bytes:
         return b"".join(self.lc_coef)
@@ -94,6 +126,7 @@ class CircuitBuilder:
         self.n_pub = 0
         self.n_aux = 0
         self.sides = []    # per gate: [left, right], each an LC (defined) or an aux index (free)
+        self.hints = []    # per aux value: (op, arg, LC), or None (the caller's)
         self.asserts = []
         self.one = LC({(_ONE, 0, 0): 1})
         self.challenge = LC({(_X, 0, 0): 1})
@@ -117,14 +150,31 @@ class CircuitBuilder:
     def _wires(self, g: int):
         return tuple(LC({(_W, g, s): 1}) for s in range(3))
 
+    def hint(self, op: int, lc, arg: int = 0) -> Hint:
+        """A free side whose value the prover derives: aux = op(lc mod l), lc
+        over {1, v_j, u_i} (neither x nor a wire: aux exists before x does);
+        arg: the bit index of HINT_BIT / HINT_NOT_BIT.  For mul(), either side."""
+        lc = LC.of(lc)
+        if op not in (HINT_VALUE, HINT_BIT, HINT_NOT_BIT, HINT_INV, HINT_IS_ZERO):
+            raise ValueError(f"hint: unknown op {op}")
+        if not 0 <= arg <= 252 or (arg and op not in (HINT_BIT, HINT_NOT_BIT)):
+            raise ValueError("hint: arg is a bit index <= 252, for HINT_BIT / HINT_NOT_BIT only")
+        if any(kind in (_X, _W) for (kind, _i, _s) in lc.t):
+            raise ValueError("hint: reads x or a wire")
+        self.hints.append((op, arg, lc))
+        self.n_aux += 1
+        return Hint(self.n_aux - 1)
+
     def mul(self, left, right):
-        """A gate with defined sides; returns its wires (l, r, o)."""
+        """A gate whose sides are defined (linear combinations) or hinted free
+        sides (hint()); returns its wires (l, r, o)."""
         g = len(self.sides)
-        for side in (LC.of(left), LC.of(right)):
-            for (kind, h, _s) in side.t:
+        sides = [s.index if isinstance(s, Hint) else LC.of(s) for s in (left, right)]
+        for side in sides:
+            for (kind, h, _s) in (side.t if isinstance(side, LC) else ()):
                 if kind == _W and h >= g:
                     raise ValueError(f"gate {g}: a definition reads a wire of gate {h}")
-        self.sides.append([LC.of(left), LC.of(right)])
+        self.sides.append(sides)
         return self._wires(g)
 
     def free_mul(self):
@@ -132,6 +182,7 @@ class CircuitBuilder:
         its wires (l, r, o)."""
         self.sides.append([self.n_aux, self.n_aux + 1])
         self.n_aux += 2
+        self.hints += [None, None]
         return self._wires(len(self.sides) - 1)
 
     def assert_zero(self, lc):
@@ -148,7 +199,7 @@ class CircuitBuilder:
 
         side_aux, lc_off, lc_var, lc_coef = [], [0], [], []
 
-        def emit(lc: LC):
+        def emit(lc: LC, lc_off=lc_off, lc_var=lc_var, lc_coef=lc_coef):
             for vid, c in sorted((var_id(k), c) for k, c in lc.t.items()):
                 lc_var.append(vid)
                 lc_coef.append(c.to_bytes(32, "little"))
@@ -164,7 +215,14 @@ class CircuitBuilder:
                     lc_off.append(len(lc_var))
         for a in self.asserts:
             emit(a)
-        return CircuitDesc(m_in, n, self.n_aux, len(self.asserts), side_aux, lc_off, lc_var, lc_coef, aux_of, n_pub)
+        hints = None
+        if self.n_aux and all(h is not None for h in self.hints):  # every aux value has a hint
+            hints = CircuitHints([], [0], [], [])
+            for op, arg, lc in self.hints:
+                hints.op.append(op | arg << 8)
+                emit(lc, hints.lc_off, hints.lc_var, hints.lc_coef)
+        return CircuitDesc(m_in, n, self.n_aux, len(self.asserts), side_aux, lc_off, lc_var, lc_coef, aux_of, n_pub,
+                           hints)
 
 
 # --------------------------------------------------------------------- gadgets
@@ -205,6 +263,28 @@ def member_of(values: Sequence[int]) -> CircuitDesc:
     return b.build()
 
 
+def _range_bits(b: CircuitBuilder, target: LC, nbits: int):
+    """target < 2^nbits (target over {1, v_j, u_i}): a gate per bit with both
+    sides free and hinted (l = the bit of target, r = 1 - it), an assert o = 0
+    and an assert l + r - 1 = 0; one more assert covers the weighted bit sum."""
+    total = LC()
+    for i in range(nbits):
+        l, r, o = b.mul(b.hint(HINT_BIT, target, i), b.hint(HINT_NOT_BIT, target, i))
+        b.assert_zero(o)
+        b.assert_zero(l + r - 1)
+        total = total + l * (1 << i)
+    b.assert_zero(total - target)
+
+
+def _bits_aux(x: int, nbits: int) -> list:
+    """_range_bits' auxiliary values for target = x."""
+    out = []
+    for i in range(nbits):
+        bit = (x % L >> i) & 1
+        out += [bit, 1 - bit]
+    return out
+
+
 def in_range(nbits: int) -> CircuitDesc:
     """v_0 < 2^nbits.  Each bit takes a gate with both sides free (l = bit, r =
     1 - bit), an assert o = 0 and an assert l + r - 1 = 0; one more assert
@@ -213,13 +293,7 @@ def in_range(nbits: int) -> CircuitDesc:
         raise ValueError("1 <= nbits <= 252")
     b = CircuitBuilder()
     v = b.input()
-    total = LC()
-    for i in range(nbits):
-        l, r, o = b.free_mul()
-        b.assert_zero(o)
-        b.assert_zero(l + r - 1)
-        total = total + l * (1 << i)
-    b.assert_zero(total - v)
+    _range_bits(b, v, nbits)
 
     def aux_of(vals):
         x = int(vals[0]) % L
@@ -245,13 +319,7 @@ def in_range_many(count: int, nbits: int) -> CircuitDesc:
     b = CircuitBuilder()
     vs = b.inputs(count)
     for v in vs:
-        total = LC()
-        for i in range(nbits):
-            l, r, o = b.free_mul()
-            b.assert_zero(o)
-            b.assert_zero(l + r - 1)
-            total = total + l * (1 << i)
-        b.assert_zero(total - v)
+        _range_bits(b, v, nbits)
 
     def aux_of(vals):
         out = []
@@ -260,6 +328,66 @@ def in_range_many(count: int, nbits: int) -> CircuitDesc:
             for i in range(nbits):
                 bit = (x >> i) & 1
                 out += [bit, 1 - bit]
+        return out
+
+    return b.build(aux_of)
+
+
+def not_equal() -> CircuitDesc:
+    """v_0 != v_1: (v_0 - v_1) * inv = 1, one gate whose right side is free and
+    hinted with the inverse of the difference.  Equal cards: the hint is 0 and
+    the assert o - 1 = 0 does not hold."""
+    return distinct(2)
+
+
+def distinct(k: int) -> CircuitDesc:
+    """v_0..v_{k-1} are pairwise different ("my hand has no repeated card"):
+    not_equal over all pairs i < j in lexicographic order, k (k - 1) / 2 gates,
+    one hint and one assert each."""
+    if k < 2:
+        raise ValueError("k >= 2")
+    b = CircuitBuilder()
+    v = b.inputs(k)
+    pairs = [(i, j) for i in range(k) for j in range(i + 1, k)]
+    for i, j in pairs:
+        b.assert_zero(b.mul(v[i] - v[j], b.hint(HINT_INV, v[i] - v[j]))[2] - 1)
+
+    def aux_of(vals):
+        d = [(int(vals[i]) - int(vals[j])) % L for i, j in pairs]
+        return [pow(x, -1, L) if x else 0 for x in d]
+
+    return b.build(aux_of)
+
+
+def less_than(nbits: int) -> CircuitDesc:
+    """v_0 < v_1, both below 2^nbits: v_0, v_1 and v_1 - v_0 - 1 are each below
+    2^nbits (in_range's bit gates over each), 3 nbits gates.  nbits <= 250, so
+    that no sum of two such values wraps mod l."""
+    return ascending(2, nbits)
+
+
+def ascending(k: int, nbits: int) -> CircuitDesc:
+    """v_0 < v_1 < .. < v_{k-1}, all below 2^nbits ("my hand is in ascending
+    order"): every v_i, then every v_{i+1} - v_i - 1, below 2^nbits;
+    (2k - 1) nbits gates."""
+    if k < 2:
+        raise ValueError("k >= 2")
+    if not 1 <= nbits <= 250:
+        raise ValueError("1 <= nbits <= 250")
+    b = CircuitBuilder()
+    v = b.inputs(k)
+    for x in v:
+        _range_bits(b, x, nbits)
+    for i in range(k - 1):
+        _range_bits(b, v[i + 1] - v[i] - 1, nbits)
+
+    def aux_of(vals):
+        x = [int(a) % L for a in vals]
+        out = []
+        for a in x:
+            out += _bits_aux(a, nbits)
+        for i in range(k - 1):
+            out += _bits_aux(x[i + 1] - x[i] - 1, nbits)
         return out
 
     return b.build(aux_of)

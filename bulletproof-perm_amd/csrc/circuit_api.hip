@@ -7,6 +7,7 @@
 
 #include "host/circuit.h"
 #include "perm_internal.h"
+#include "poly.h"
 
 using namespace perm_impl;
 
@@ -52,7 +53,8 @@ int circuit_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* aux, con
 
 extern "C" {
 
-int bpp_circuit_create_ex(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags, bpp_circuit** out) {
+int bpp_circuit_create_hinted(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags,
+                              const bpp_circuit_hints* hints, bpp_circuit** out) {
   return bpp_guard(nullptr, [&]() -> int {
     if (!desc || !out) return BPP_ERR_ARG;
     *out = nullptr;
@@ -60,12 +62,18 @@ int bpp_circuit_create_ex(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t
                        desc->side_aux, desc->lc_off,  desc->lc_var, desc->lc_coef};
     d.n_pub = n_pub;
     d.flags = flags;
+    circuit::HintDesc h = {};
+    if (hints) h = {hints->op, hints->lc_off, hints->lc_var, hints->lc_coef};
     std::unique_ptr<bpp_circuit> c(new bpp_circuit());
     std::string err;
-    BPP_TRY(circuit::compile(d, c->C, err));
+    BPP_TRY(circuit::compile(d, c->C, err, hints ? &h : nullptr));
     *out = c.release();
     return BPP_OK;
   });
+}
+
+int bpp_circuit_create_ex(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags, bpp_circuit** out) {
+  return bpp_circuit_create_hinted(desc, n_pub, flags, nullptr, out);
 }
 
 int bpp_circuit_create_pub(const bpp_circuit_desc* desc, uint32_t n_pub, bpp_circuit** out) {
@@ -79,6 +87,62 @@ int bpp_circuit_create(const bpp_circuit_desc* desc, bpp_circuit** out) {
 void bpp_circuit_destroy(bpp_circuit* c) { delete c; }
 
 uint32_t bpp_circuit_n_pub(const bpp_circuit* c) { return c ? c->C.n_pub : 0; }
+
+int bpp_circuit_has_hints(const bpp_circuit* c) { return c && c->C.program->hints ? 1 : 0; }
+
+int bpp_circuit_hint_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* pub, uint8_t* aux_out) {
+  return bpp_guard(nullptr, [&]() -> int {
+    if (!c || !v) return BPP_ERR_ARG;
+    const circuit::Program& P = *c->C.program;
+    if (!P.hints || (!pub && P.n_pub) || (!aux_out && P.n_aux)) return BPP_ERR_ARG;
+    std::vector<Sc> vs(P.m_in), us(P.n_pub), as(P.n_aux);
+    for (uint32_t j = 0; j < P.m_in; ++j)
+      if (!hsc::from_canonical(vs[j], v + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
+    for (uint32_t j = 0; j < P.n_pub; ++j)
+      if (!hsc::from_canonical(us[j], pub + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
+    circuit::hint_eval(P, vs.data(), us.data(), as.data());
+    if (P.n_aux) memcpy(aux_out, as.data(), 32 * (size_t)P.n_aux);  // (canonical Sc == its 32 bytes)
+    for (auto* s : {&vs, &as}) std::fill(s->begin(), s->end(), hsc::zero());
+    return BPP_OK;
+  });
+}
+
+// Test hook: k_hint_aux alone over count proofs' v and pub, the derived values
+// back to the host; the workspaces it used are wiped as a batch's are.
+int bpp_debug_circuit_hints(bpp_ctx* ctx, const bpp_circuit* c, size_t count, const uint8_t* v, const uint8_t* pub,
+                            uint8_t* aux_out) {
+  return bpp_guard(ctx, [&]() -> int {
+    if (!ctx || !c || !c->C.program->hints) return BPP_ERR_ARG;
+    const circuit::Program& P = *c->C.program;
+    if (!count || !P.n_aux) return BPP_OK;
+    if (!v || !aux_out || (!pub && P.n_pub) || count > 0xFFFFFFFFu) return BPP_ERR_ARG;
+    std::vector<int> bad(count, BPP_OK);
+    check_canonical(v, P.m_in, count, bad);
+    check_canonical(pub, P.n_pub, count, bad);
+    if (first_bad(bad) != SIZE_MAX) return BPP_ERR_NONCANONICAL;
+    BPP_HIP(hipSetDevice(ctx->device));
+    // v and pub through the batch's own upload workspace and a staging span that
+    // prove_wipe zeroes, as draws_upload stages them
+    const size_t vb = count * 32 * (size_t)P.m_in, ub = count * 32 * (size_t)P.n_pub;
+    void *d_in = nullptr, *d_aux = nullptr;
+    uint8_t* stage = nullptr;
+    BPP_TRY(ctx_ws(ctx, "pb_rng_in", vb + ub, &d_in));
+    BPP_TRY(ctx_h2d_stage(ctx, vb + ub, &stage));
+    ctx_secret_span(ctx, stage, vb + ub);
+    memcpy(stage, v, vb);
+    if (ub) memcpy(stage + vb, pub, ub);
+    int rc = ctx_h2d_staged(ctx, d_in, stage, vb + ub);
+    if (rc == BPP_OK) rc = ctx_ws(ctx, "pb_aux_hint", count * 32 * (size_t)P.n_aux, &d_aux);
+    if (rc == BPP_OK)
+      rc = hint_aux_dev(ctx, c->C, (uint32_t)count, (const uint32_t*)d_in,
+                        ub ? (const uint32_t*)((const uint8_t*)d_in + vb) : nullptr, (uint32_t*)d_aux);
+    if (rc == BPP_OK) rc = ctx_sync(ctx);
+    if (rc == BPP_OK && hipMemcpy(aux_out, d_aux, count * 32 * (size_t)P.n_aux, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = BPP_ERR_DEVICE;
+    const int wrc = prove_wipe(ctx);
+    return rc ? rc : wrc;
+  });
+}
 
 int bpp_circuit_info(const bpp_circuit* c, uint32_t* n_p, uint32_t* Q, uint32_t* m, uint8_t digest[32]) {
   if (!c) return BPP_ERR_ARG;
@@ -125,7 +189,9 @@ int bpp_circuit_prove_batch_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circu
   return bpp_guard(ctx, [&]() -> int {
     if (!c || (!label && llen)) return BPP_ERR_ARG;
     const uint32_t m_in = c->C.nv, n_aux = c->C.program->n_aux;
-    if ((!v || (!aux && n_aux) || !proofs_out || !V_out) && count) return BPP_ERR_ARG;
+    // aux == NULL on a circuit with hints: the values are derived on the GPU (k_hint_aux)
+    const bool derive = !aux && n_aux && c->C.program->hints;
+    if ((!v || (!aux && n_aux && !derive) || !proofs_out || !V_out) && count) return BPP_ERR_ARG;
     if (!pub && c->C.n_pub && count) return BPP_ERR_ARG;
     // every scalar of the witness is checked before any device work and
     // before any output byte is written (it needs neither the context nor
@@ -148,7 +214,7 @@ int bpp_circuit_prove_batch_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circu
     if (!count) return BPP_OK;
     ProveInputs in;
     in.values = {v, m_in};
-    in.aux = {n_aux ? aux : nullptr, n_aux};
+    in.aux = {n_aux ? aux : nullptr, n_aux};  // (p = nullptr with n_aux > 0: derived from the circuit's hints)
     in.gammas = {gammas, m_in};
     in.pub = {c->C.n_pub ? pub : nullptr, c->C.n_pub};
     return prove_batch_entropy(ctx, G, c->C, count, seeds32, label, llen, proofs_out, V_out, &in);

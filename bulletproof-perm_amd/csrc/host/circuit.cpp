@@ -28,7 +28,82 @@ void digest(const Desc& d, uint8_t out[32]) {
   sh.read(out, 32);
 }
 
-int compile(const Desc& d, perm::Circuit& C, std::string& err) {
+namespace {
+
+// the flagged variable id of a term for the device images: | kTermOne for the
+// coefficient 1, | kTermNeg for -1 (no multiply)
+uint32_t dev_term(uint32_t var, const Sc& a) {
+  const Sc one = hsc::one(), neg1 = hsc::neg(hsc::one());
+  return var | (a == one ? kTermOne : a == neg1 ? kTermNeg : 0u);
+}
+
+// Validates the hint program of a circuit with m_in inputs, n_pub public inputs
+// and n_aux auxiliary values, and builds its device image.
+int compile_hints(const HintDesc& h, uint32_t m_in, uint32_t n_pub, uint32_t n_aux, std::shared_ptr<const Hints>& out,
+                  std::string& err) {
+  auto fail = [&](int rc, std::string what) {
+    err = "circuit hints: " + what;
+    return rc;
+  };
+  if (!n_aux) {  // (no aux value, no hint: an empty program)
+    out = std::make_shared<Hints>();
+    return OK;
+  }
+  if (!h.op || !h.lc_off) return fail(ERR_ARG, "null op or lc_off");
+  if (h.lc_off[0] != 0) return fail(ERR_ARG, "lc_off[0] is not 0");
+  for (uint32_t t = 0; t < n_aux; ++t)
+    if (h.lc_off[t + 1] < h.lc_off[t]) return fail(ERR_ARG, "lc_off decreases at " + std::to_string(t + 1));
+  const size_t T = h.lc_off[n_aux];
+  if (T && (!h.lc_var || !h.lc_coef)) return fail(ERR_ARG, "null lc_var or lc_coef");
+  auto H = std::make_shared<Hints>();
+  H->op.assign(h.op, h.op + n_aux);
+  H->lc_off.assign(h.lc_off, h.lc_off + n_aux + 1);
+  H->lc_var.assign(h.lc_var, h.lc_var + T);
+  H->lc_coef.resize(T);
+  const uint32_t x_id = 1 + m_in, wbase = 2 + m_in + n_pub;
+  for (uint32_t t = 0; t < n_aux; ++t) {
+    const std::string where = "hint " + std::to_string(t);
+    const uint32_t op = h.op[t] & 0xFFu, arg = h.op[t] >> 8;
+    if (op >= kHintOps) return fail(ERR_ARG, where + ": unknown op");
+    if (arg && op != kHintBit && op != kHintNotBit) return fail(ERR_ARG, where + ": an arg on an op that takes none");
+    if (arg > kHintMaxBit) return fail(ERR_ARG, where + ": bit index above 252");
+    for (size_t e = h.lc_off[t]; e < h.lc_off[t + 1]; ++e) {
+      const uint32_t var = h.lc_var[e];
+      if (var >= wbase) return fail(ERR_ARG, where + ": variable id out of range, or a wire");
+      if (var == x_id) return fail(ERR_ARG, where + ": reads x (aux exists before x does)");
+      if (e > h.lc_off[t] && var <= h.lc_var[e - 1]) return fail(ERR_ARG, where + ": ids not strictly increasing");
+      if (!hsc::from_canonical(H->lc_coef[e], h.lc_coef + 32 * e))
+        return fail(ERR_NONCANONICAL, where + ": coefficient not below l");
+      if (hsc::is_zero(H->lc_coef[e])) return fail(ERR_ARG, where + ": zero coefficient");
+    }
+  }
+  // the lane order: by op, INV first, hints of one op in index order
+  std::vector<uint32_t> order(n_aux);
+  for (uint32_t t = 0; t < n_aux; ++t) order[t] = t;
+  auto rank = [&](uint32_t t) { return (H->op[t] & 0xFFu) == kHintInv ? 0u : 1u + (H->op[t] & 0xFFu); };
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rank(a) < rank(b); });
+  std::vector<uint32_t>& dev = H->dev;
+  for (uint32_t t : order) {
+    const uint32_t rec[4] = {t, H->op[t], H->lc_off[t], H->lc_off[t + 1]};
+    dev.insert(dev.end(), rec, rec + 4);
+  }
+  H->dev_vars = (uint32_t)dev.size();
+  for (size_t e = 0; e < T; ++e) dev.push_back(dev_term(H->lc_var[e], H->lc_coef[e]));
+  dev.resize((dev.size() + 7) & ~(size_t)7, 0);
+  H->dev_coefs = (uint32_t)dev.size();
+  for (size_t e = 0; e < T; ++e) {
+    uint32_t w[8];
+    const Sc cR = hsc::to_mont(H->lc_coef[e]);
+    memcpy(w, cR.v, 32);
+    dev.insert(dev.end(), w, w + 8);
+  }
+  out = H;
+  return OK;
+}
+
+}  // namespace
+
+int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* hints) {
   auto fail = [&](int rc, std::string what) {
     err = "circuit: " + what;
     return rc;
@@ -79,6 +154,10 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
         return fail(ERR_NONCANONICAL, where + ": coefficient not below l");
       if (hsc::is_zero(P->lc_coef[t])) return fail(ERR_ARG, where + ": zero coefficient");
     }
+  }
+  if (hints) {
+    const int rc = compile_hints(*hints, m_in, d.n_pub, d.n_aux, P->hints, err);
+    if (rc != OK) return rc;
   }
   C = perm::Circuit();
   C.k = 0;  // (no cards: nothing downstream of the witness reads k)
@@ -154,14 +233,7 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err) {
   P->dev_level_gate = (uint32_t)dev.size();
   dev.insert(dev.end(), P->level_gate.begin(), P->level_gate.end());
   P->dev_vars = (uint32_t)dev.size();
-  const Sc neg1 = hsc::neg(hsc::one());
-  for (size_t t = 0; t < T; ++t) {
-    const Sc& a = P->lc_coef[t];
-    const Sc one = hsc::one();
-    dev.push_back(P->lc_var[t] | (!memcmp(&a, &one, sizeof(Sc))    ? kTermOne
-                                  : !memcmp(&a, &neg1, sizeof(Sc)) ? kTermNeg
-                                                                   : 0u));
-  }
+  for (size_t t = 0; t < T; ++t) dev.push_back(dev_term(P->lc_var[t], P->lc_coef[t]));
   dev.resize((dev.size() + 7) & ~(size_t)7, 0);
   P->dev_coefs = (uint32_t)dev.size();
   for (size_t t = 0; t < T; ++t) {
@@ -207,6 +279,26 @@ void eval(const Program& P, uint32_t n_p, const Sc* v, const Sc* aux, const Sc& 
       *bad_assert = a + 1;
       break;
     }
+}
+
+void hint_eval(const Program& P, const Sc* v, const Sc* pub, Sc* aux) {
+  const Hints& H = *P.hints;
+  for (uint32_t t = 0; t < P.n_aux; ++t) {
+    Sc w = hsc::zero();
+    for (size_t e = H.lc_off[t]; e < H.lc_off[t + 1]; ++e) {
+      const uint32_t var = H.lc_var[e];
+      const Sc val = var == 0 ? hsc::one() : var <= P.m_in ? v[var - 1] : pub[var - 2 - P.m_in];
+      w = hsc::add(w, hsc::mul(H.lc_coef[e], val));
+    }
+    const uint32_t op = H.op[t] & 0xFFu, arg = H.op[t] >> 8;
+    const uint64_t bit = (w.v[arg >> 6] >> (arg & 63)) & 1;  // (arg = 0 for the ops without one)
+    aux[t] = op == kHintValue    ? w
+             : op == kHintBit    ? hsc::from_u64(bit)
+             : op == kHintNotBit ? hsc::from_u64(1 - bit)
+             : op == kHintInv    ? hsc::invert(w)  // (w^(l - 2): 0 for w = 0)
+                                 : hsc::from_u64(hsc::is_zero(w) ? 1 : 0);
+    w = hsc::zero();
+  }
 }
 
 }  // namespace circuit

@@ -54,8 +54,39 @@ inline uint32_t var_wire(uint32_t m_in, uint32_t h, uint32_t lro, uint32_t n_pub
   return 2 + m_in + n_pub + 3 * h + lro;
 }
 
+// A hint program (bpp_circuit_hints): how the prover derives aux_t from {1, v_j,
+// u_i}.  aux_t = op(w), w = the hint's combination mod l (empty: 0):
+//   kHintValue  w                 kHintBit     bit `arg` of w in [0, l)
+//   kHintInv    w^-1, 0 for w = 0  kHintNotBit  1 - that bit
+//   kHintIsZero 1 when w = 0, else 0
+// op word = op | arg << 8 (arg <= 252, BIT / NOT_BIT only).  A hint reads
+// neither x (aux exists before x does) nor wires.  Attached at creation; no
+// part of the statement: digest, matrices, transcript and proof bytes do not
+// see it.
+enum : uint32_t { kHintValue = 0, kHintBit = 1, kHintNotBit = 2, kHintInv = 3, kHintIsZero = 4, kHintOps = 5 };
+constexpr uint32_t kHintMaxBit = 252;
+struct HintDesc {
+  const uint32_t* op;       // [n_aux]
+  const uint32_t* lc_off;   // [n_aux + 1]
+  const uint32_t* lc_var;   // [T]: 0 = one, 1 + j = v_j, 2 + m_in + i = u_i
+  const uint8_t* lc_coef;   // [T][32]
+};
+struct Hints {
+  std::vector<uint32_t> op, lc_off, lc_var;
+  std::vector<hsc::Sc> lc_coef;
+  // what k_hint_aux reads, one upload: a record of 4 words per LANE -- the
+  // hint's index t, its op word, its terms [begin, end) -- in an order grouped
+  // by op (INV first: its lanes run a few hundred products, a BIT lane none),
+  // so that the lanes of one wave run one op wherever the counts allow; then
+  // the T terms' variable ids (| kTermOne / kTermNeg as in Program::dev), then
+  // (from a multiple of 8 words) their Montgomery coefficients [T][8]
+  std::vector<uint32_t> dev;
+  uint32_t dev_vars = 0, dev_coefs = 0;
+};
+
 struct Program {
   uint32_t m_in = 0, n = 0, n_aux = 0, A = 0, n_pub = 0;
+  std::shared_ptr<const Hints> hints;  // (compile with a HintDesc; null: aux is the caller's)
   std::vector<uint32_t> side_aux, lc_off, lc_var;
   std::vector<hsc::Sc> lc_coef;
   // gates by dependency level: level = 1 + the highest level among the gates
@@ -85,7 +116,16 @@ void digest(const Desc& d, uint8_t out[32]);
 // non-monotone lc_off, unknown flag bits; ERR_NONCANONICAL for a coefficient
 // >= l; ERR_LEN beyond kMaxPub, the kMax* below or, without kLarge, lds_fits.
 // C.program is the compiled program; C.tiled = the kTiled flag.
-int compile(const Desc& d, perm::Circuit& C, std::string& err);
+// hints: nullptr, or the hint program (one hint per aux value), validated the
+// same way: ERR_ARG for an unknown op, arg > 252, an arg on an op that takes
+// none, an id out of range or naming x or a wire, unsorted ids, a zero
+// coefficient, a non-monotone lc_off; ERR_NONCANONICAL for a coefficient >= l.
+int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* hints = nullptr);
+
+// The hints' host reference: aux [n_aux] from v [m_in] and pub [n_pub]
+// (canonical).  What BPP_CIRCUIT_HOST_WITNESS=1 runs in the prover, and what
+// k_hint_aux must equal.
+void hint_eval(const Program& P, const hsc::Sc* v, const hsc::Sc* pub, hsc::Sc* aux);
 
 // The host witness: a_L, a_R, a_O (n_p each, padding gates zero) from v
 // [m_in], aux [n_aux] and x; *bad_assert = 1 + the first assert that does not

@@ -192,7 +192,8 @@ namespace perm_impl BPP_HIDDEN {
 // by each sub-batch thread on its child context (BPP_PROVE_STREAMS > 1).
 static const char* const kSecretWs[] = {"pb_rng_in", "pb_gamma", "mt_s",  "pv_v",   "pv_g",    "pv_gx",  "poly_vec",
                                         "poly_hf",   "pf_l",     "pf_r",  "ipa_am", "ipa_bm",  "ipa_am1", "ipa_bm1",
-                                        "wp_wires"};  // (k_witness_program_wide's wires)
+                                        "wp_wires",      // (k_witness_program_wide's wires)
+                                        "pb_aux_hint"};  // (k_hint_aux's derived auxiliary values)
 static const char* const kSecretHost[] = {"pp_v", "pp_g", "ipa_zc_a", "ipa_zc_b"};  // (ipa_zc_*: bpp_ipa_prove zeroes them itself)
 static_assert(sizeof(kSecretWs) / sizeof(kSecretWs[0]) <= WIPE_MAX, "WipeSpans too small");
 int prove_wipe(bpp_ctx* ctx) {
@@ -295,7 +296,7 @@ struct ProveBatch {
   // blindings [P][nv] and gamma_nv / 2 [P] ("pv_v", "pv_g", "pv_gx", taken once), and the IPA inputs
   uint32_t *d_gamma = nullptr, *d_s = nullptr, *d_pi = nullptr;
   uint32_t *d_v = nullptr, *d_g = nullptr, *d_gx_half = nullptr;
-  const uint32_t* d_aux = nullptr;  // a program's uploaded auxiliary values [P][n_aux]
+  const uint32_t* d_aux = nullptr;  // a program's auxiliary values [P][n_aux]: uploaded, or derived ("pb_aux_hint")
   const uint32_t* d_pub = nullptr;  // a program's uploaded public inputs [P][n_pub]
   uint32_t *d_l = nullptr, *d_r = nullptr, *d_hf = nullptr;
   MsmPoints pts;
@@ -337,7 +338,9 @@ int ProveBatch::draws_upload() {
       ctx->err = "prove_batch: seeds of different lengths in one batch";
       return BPP_ERR_ARG;
     }
-  if (C.program && !(in && in->values.p && (in->aux.p || !C.program->n_aux) && (in->pub.p || !C.n_pub))) {
+  // (no aux rows on a circuit with hints: derived below, and nothing of them is staged or uploaded)
+  const bool derive_aux = C.program && in && !in->aux.p && C.program->n_aux && C.program->hints;
+  if (C.program && !(in && in->values.p && (in->aux.p || !C.program->n_aux || derive_aux) && (in->pub.p || !C.n_pub))) {
     ctx->err = "prove_batch: a caller-defined circuit takes the caller's v, aux and public inputs";
     return BPP_ERR_ARG;
   }
@@ -382,6 +385,10 @@ int ProveBatch::draws_upload() {
           keep(st.cards, in->values);
           keep(st.aux, in->aux);
           keep(st.pub, in->pub);
+          if (derive_aux) {  // the host witness's aux from the host hints
+            st.aux.resize(C.program->n_aux);
+            circuit::hint_eval(*C.program, st.cards.data(), st.pub.data(), st.aux.data());
+          }
         }
       }
       perm::transcript_prefix(C, st.tr);
@@ -394,6 +401,7 @@ int ProveBatch::draws_upload() {
     }
   });
   BPP_TRY(ctx_h2d_staged(ctx, dst, stage, L.bytes));
+  ctx_work(ctx, "prove_stage_bytes", L.bytes);
   const uint8_t* base = (const uint8_t*)dst;
   d_pi = (uint32_t*)(base + L.pi);
   BPP_TRY(ctx_ws(ctx, "pv_v", (size_t)P * nv * 32, (void**)&d_v));
@@ -408,6 +416,12 @@ int ProveBatch::draws_upload() {
   d_aux = L.aux.dev(dst);
   d_pub = L.pub.dev(dst);
   const uint32_t* d_src = L.values.dev(dst);
+  if (derive_aux && dev_witness) {  // k_hint_aux over the uploaded v and pub rows, in front of k_witness_program
+    uint32_t* d_hint = nullptr;
+    BPP_TRY(ctx_ws(ctx, "pb_aux_hint", (size_t)P * C.program->n_aux * 32, (void**)&d_hint));
+    BPP_TRY(hint_aux_dev(ctx, C, (uint32_t)P, d_src, d_pub, d_hint));
+    d_aux = d_hint;
+  }
   if (C.deck) {
     void* d_deck = nullptr;
     BPP_TRY(ctx_ws(ctx, "pb_deck", (size_t)k * 32, &d_deck));

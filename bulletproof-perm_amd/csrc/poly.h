@@ -82,3 +82,10 @@ int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uin
 int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
                         const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail,
                         const uint32_t* d_pub = nullptr);  // (d_pub [P][n_pub] canonical: the public inputs)
+// hint_aux_dev (k_hint_aux): the auxiliary values of a circuit with hints
+// (C.program->hints), one lane per (proof, hint), from d_vals [P][m_in] and
+// d_pub [P][n_pub] into d_aux [P][n_aux] (canonical), which witness_program_dev
+// then reads as a caller's.  Enqueued on ctx's stream; d_aux is secret (the
+// prover keeps it in "pb_aux_hint", which prove_wipe zeroes).
+int hint_aux_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals, const uint32_t* d_pub,
+                 uint32_t* d_aux);

@@ -1136,6 +1136,78 @@ int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const 
   return ctx_check_launch(ctx, wide ? "k_witness_program_wide" : stage ? "k_witness_program" : "k_witness_program_global");
 }
 
+// k_hint_aux: the auxiliary values of a circuit with hints, in front of
+// k_witness_program.  One lane per (proof, hint): blockIdx.y = the proof, lane
+// i of the row takes record i of the hints' device image (circuit::Hints::dev:
+// the hint's index t, its op word, its terms [b, e)), whose order groups the
+// hints by op, so the lanes of a wave run one op wherever the counts allow.
+// w = the combination over {1, v_j, u_i}, accumulated CANONICAL: a term of
+// coefficient 1 or -1 (the id's flag) adds or subtracts the canonical value, and
+// a general term is sc_mont(value, coefficient R) = value x coefficient, so a
+// BIT lane over v_j runs no product at all.  aux_t = op(w), canonical, to
+// aux[p][t].  Branches (the op, the term flags, the term count, the exponent of
+// sc_inv_mont) and addresses (t, the variable ids) come from the hint program
+// alone; the value is tested and its bit taken with selects and shifts.  No LDS.
+__global__ void __launch_bounds__(256) k_hint_aux(uint32_t n_aux, uint32_t m_in, uint32_t n_pub,
+                                                  const uint32_t* __restrict__ prog, uint32_t o_var, uint32_t o_coef,
+                                                  const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pubs,
+                                                  uint32_t* __restrict__ aux) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x, p = blockIdx.y;
+  if (i >= n_aux) return;
+  const uint4 rec = reinterpret_cast<const uint4*>(prog)[i];  // t, op | arg << 8, b, e
+  const uint32_t* vp = vals + 8 * (size_t)p * m_in;
+  const uint32_t* up = pubs + 8 * (size_t)p * n_pub;  // (not read when n_pub = 0)
+  sc one = sc_zero();
+  one.v[0] = 1;
+  sc w = sc_zero();
+  for (uint32_t e = rec.z; e < rec.w; ++e) {
+    const uint32_t tv = prog[o_var + e], var = tv & circuit::kTermVar;
+    const sc val = var == 0 ? one : sc_load(var <= m_in ? vp + 8 * (size_t)(var - 1) : up + 8 * (size_t)(var - 2 - m_in));
+    if (tv & circuit::kTermOne)
+      w = sc_add(w, val);
+    else if (tv & circuit::kTermNeg)
+      w = sc_sub(w, val);
+    else
+      w = sc_add(w, sc_mont(val, sc_load(prog + o_coef + 8 * (size_t)e)));
+  }
+  const uint32_t op = rec.y & 0xFFu, arg = rec.y >> 8;
+  sc r = w;  // (circuit::kHintValue)
+  if (op == circuit::kHintInv) {
+    r = sc_from_mont(sc_inv_mont(sc_to_mont(w)));
+  } else if (op != circuit::kHintValue) {
+    uint32_t word = 0, nz = 0;
+    _Pragma("unroll") for (uint32_t k = 0; k < 8; ++k) {
+      word = k == (arg >> 5) ? w.v[k] : word;  // (arg: the program's, the same for a hint's every proof)
+      nz |= w.v[k];
+    }
+    const uint32_t bit = (word >> (arg & 31u)) & 1u;
+    r = sc_zero();
+    r.v[0] = op == circuit::kHintBit ? bit : op == circuit::kHintNotBit ? 1u - bit : (uint32_t)(nz == 0);
+  }
+  sc_store(aux + 8 * ((size_t)p * n_aux + rec.x), r);
+}
+
+int hint_aux_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals, const uint32_t* d_pub,
+                 uint32_t* d_aux) {
+  const circuit::Program& G = *C.program;
+  if (!G.hints || (G.n_pub && !d_pub)) return BPP_ERR_ARG;
+  if (!P || !G.n_aux) return BPP_OK;
+  const circuit::Hints& H = *G.hints;
+  void* d_prog = nullptr;
+  BPP_TRY(ctx_ws(ctx, "ha_prog", H.dev.size() * 4, &d_prog));
+  BPP_TRY(ctx_h2d_const(ctx, "ha_prog", d_prog, H.dev.data(), H.dev.size() * 4));  // the circuit: same every batch
+  {
+    ProfScope ps(ctx, "hint_aux");
+    constexpr uint32_t kRows = 65535;  // (gridDim.y's bound)
+    for (uint32_t p0 = 0; p0 < P; p0 += kRows)
+      hipLaunchKernelGGL(k_hint_aux, dim3((G.n_aux + 255) / 256, std::min(kRows, P - p0)), dim3(256), 0, ctx->stream,
+                         G.n_aux, G.m_in, G.n_pub, (const uint32_t*)d_prog, H.dev_vars, H.dev_coefs,
+                         d_vals + 8 * (size_t)p0 * G.m_in, d_pub ? d_pub + 8 * (size_t)p0 * G.n_pub : nullptr,
+                         d_aux + 8 * (size_t)p0 * G.n_aux);
+  }
+  return ctx_check_launch(ctx, "k_hint_aux");
+}
+
 int witness_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_pi, const uint32_t* d_x,
                 uint32_t per, uint32_t* d_sc, const uint32_t* d_vals) {
   if (!P) return BPP_OK;

@@ -225,6 +225,20 @@ FE_INLINE sc sc_one_mont() {
   return sc_to_mont(one);
 }
 
+// a^-1 for a Montgomery a (a R -> a^-1 R), 0 for 0: a^(l - 2) by left-to-right
+// square-and-multiply.  The exponent is a public constant (its top bit 252,
+// bits 125..251 zero), so every lane runs the same 252 squarings and 72
+// products whatever a is: no branch or address depends on the value.
+FE_INLINE sc sc_inv_mont(const sc& a) {
+  sc r = a;  // (bit 252)
+  _Pragma("nounroll") for (int i = 251; i >= 0; --i) {
+    r = sc_mont(r, r);
+    const uint32_t e = SC_L[i >> 5] - ((i >> 5) == 0 ? 2u : 0u);  // (l - 2: no borrow out of word 0)
+    if ((e >> (i & 31)) & 1u) r = sc_mont(r, a);
+  }
+  return r;
+}
+
 // canonical w mod l for w < 2^256: w = q 2^252 + rest (q < 16), w - q l =
 // rest - q delta is in (-l, 2^252), one conditional addition of l (taken
 // only when rest < q delta: probability ~2^-125 for random w).

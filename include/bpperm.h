@@ -81,7 +81,9 @@ void bpp_ctx_profile_reset(bpp_ctx* ctx);
  * direct-table MSMs count every window of every term), "padds" (additions of
  * two extended points in trees and bucket reductions), "msm_launches", and
  * the direct-table kernel's own "dt_terms" / "dt_madds" / "dt_launches".  The
- * roofline of the proof path (96 B x terms) reads these. */
+ * roofline of the proof path (96 B x terms) reads these.
+ * "prove_stage_bytes": the bytes a prover batch staged and uploaded for its
+ * draws and inputs (templates, pi, v, aux, gammas, pub). */
 int bpp_ctx_work_get(bpp_ctx* ctx, const char* name, uint64_t* value);
 void bpp_ctx_work_reset(bpp_ctx* ctx);
 
@@ -519,7 +521,8 @@ int bpp_circuit_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* aux,
                      uint8_t* aR, uint8_t* aO, uint32_t* bad_assert);
 /* Proves count statements of c:
  *   v       count x m_in x 32 B: the committed inputs (proof-major);
- *   aux     count x n_aux x 32 B: the free sides' values (NULL when n_aux = 0);
+ *   aux     count x n_aux x 32 B: the free sides' values (NULL when n_aux = 0,
+ *           or to have them derived from the circuit's hints, "circuit hints" below);
  *   gammas  NULL, or count x m_in x 32 B: the blindings of V_0..V_{m_in-1};
  *   seeds32, label, proofs_out as bpp_deck_prove_batch; V_out count x (m_in + 1) x 32 B.
  * Every v, aux and gamma is checked canonical before any device work
@@ -631,6 +634,58 @@ int bpp_circuit_verify_batch_each_pub(bpp_ctx* ctx, const bpp_gens* g, const bpp
 #define BPP_CIRCUIT_LARGE 1u
 #define BPP_CIRCUIT_TILED 2u
 int bpp_circuit_create_ex(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags, bpp_circuit** out);
+
+/* ------------------------------------------------------- circuit hints */
+/* Every free gate side is fed from aux, and aux is a pure function of v and the
+ * public inputs: the bits of a range check, the inverse of a difference.  A
+ * hint program, attached at creation, tells the PROVER how to derive each
+ * aux_t, and bpp_circuit_prove_batch[_pub] then takes aux == NULL: the values
+ * are produced on the GPU (k_hint_aux, one lane per proof and hint, in front of
+ * k_witness_program) from the v and pub rows already uploaded, and none of
+ * them is staged, checked, uploaded or wiped on the host.
+ *   aux_t = op_t(w_t),  w_t = the hint's sparse combination over {1, v_j, u_i}
+ *   mod l (an empty combination: w_t = 0).
+ * A hint reads neither x -- aux exists before x does -- nor a wire nor another
+ * hint.  One hint per auxiliary value, in aux order: op [n_aux], lc_off
+ * [n_aux + 1]; hints == NULL is bpp_circuit_create_ex (no hints at all).
+ * BPP_ERR_ARG: an unknown op, arg > 252, an arg on an op that takes none, an id
+ * out of range or naming x or a wire, ids not strictly ascending, a zero
+ * coefficient, a non-monotone lc_off; BPP_ERR_NONCANONICAL: a coefficient >= l.
+ * Hints are no part of the statement: the digest, the matrices, the transcript
+ * and the proof bytes do not see them; bpp_circuit_create_hinted(d, n_pub, f, h)
+ * and bpp_circuit_create_ex(d, n_pub, f) give the same bpp_circuit_info, proofs
+ * made under either verify under the other, and no verifier reads them.
+ * Proving: aux == NULL with n_aux > 0 derives the values on a circuit with
+ * hints and stays BPP_ERR_ARG on one without; aux != NULL is used as given on
+ * both.  An assert that does not hold over derived values (not_equal on equal
+ * cards: the hint is 0) is reported as any other: BPP_ERR_ARG naming the proof
+ * and the assert, no output byte, secrets wiped -- the derived values, secret as
+ * aux is, among them.  Under BPP_CIRCUIT_HOST_WITNESS=1 the host derives them
+ * (bpp_circuit_hint_eval's code). */
+#define BPP_HINT_VALUE    0u  /* aux_t = w                                            */
+#define BPP_HINT_BIT      1u  /* aux_t = bit `arg` of w as an integer in [0, l)       */
+#define BPP_HINT_NOT_BIT  2u  /* aux_t = 1 - that bit                                 */
+#define BPP_HINT_INV      3u  /* aux_t = w^-1 mod l, 0 when w = 0                     */
+#define BPP_HINT_IS_ZERO  4u  /* aux_t = 1 when w = 0, else 0                         */
+typedef struct {
+  const uint32_t* op;      /* [n_aux]  BPP_HINT_* | arg << 8 (arg <= 252, BIT / NOT_BIT only) */
+  const uint32_t* lc_off;  /* [n_aux + 1] */
+  const uint32_t* lc_var;  /* 0 = one, 1 + j = v_j, 2 + m_in + i = u_i; x and wires are refused */
+  const uint8_t*  lc_coef; /* [T][32] canonical, nonzero; ids strictly ascending per hint */
+} bpp_circuit_hints;
+int bpp_circuit_create_hinted(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags,
+                              const bpp_circuit_hints* hints, bpp_circuit** out);
+int bpp_circuit_has_hints(const bpp_circuit* c);
+/* The hints' host reference (no GPU): aux_out = n_aux x 32 B from v (m_in x
+ * 32 B) and pub (n_pub x 32 B; NULL when n_pub = 0), canonical scalars
+ * (BPP_ERR_NONCANONICAL otherwise); BPP_ERR_ARG on a circuit without hints. */
+int bpp_circuit_hint_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* pub, uint8_t* aux_out);
+/* Test hook beside bpp_debug_secret_residue: runs ONLY the device kernel over
+ * count proofs (v count x m_in x 32 B, pub count x n_pub x 32 B) and copies the
+ * derived values back (aux_out count x n_aux x 32 B); what it left on the
+ * device and in staging is wiped before it returns. */
+int bpp_debug_circuit_hints(bpp_ctx* ctx, const bpp_circuit* c, size_t count, const uint8_t* v, const uint8_t* pub,
+                            uint8_t* aux_out);
 
 /* Mixed batches: proofs of different statements verified in one call with ONE
  * GPU MSM.  A group is `count` proofs of one statement under one label: the
