@@ -123,6 +123,24 @@ class Context:
               "bpp_debug_circuit_hints", self.h)
         return [[out.raw[32 * (p * n + i):32 * (p * n + i) + 32] for i in range(n)] for p in range(count)]
 
+    def circuit_witness(self, circuit, v, x, pub=None):
+        """The witness kernels alone (bpp_debug_circuit_witness; a test hook):
+        v[p], pub[p] as circuit_hints takes them, x[p] = proof p's challenge (32
+        bytes, the caller's) -> (aL, aR, aO, fail): per proof the n_p 32-byte
+        scalars of each vector, and 1 + its first failing assert (0: none)."""
+        count = len(v)
+        row = lambda rows, what: b"".join(x if isinstance(x, (bytes, bytearray)) else _join(x, 32, what) for x in rows)
+        vb, ub, xb = row(v, "v"), row(pub, "pub") if pub is not None else b"", b"".join(x)
+        if len(vb) != 32 * circuit.m_in * count or len(ub) != 32 * circuit.n_pub * count or len(xb) != 32 * count:
+            raise ValueError("circuit_witness: expected m_in scalars in v, n_pub in pub and one x per proof")
+        n = circuit.n_p
+        outs = [C.create_string_buffer(max(32 * n * count, 1)) for _ in range(3)]
+        fail = (C.c_uint32 * max(count, 1))()
+        check(self.lib.bpp_debug_circuit_witness(self.h, circuit.h, count, _buf(vb), _buf(ub), _buf(xb), *outs, fail),
+              "bpp_debug_circuit_witness", self.h)
+        split = lambda o: [[o.raw[32 * (p * n + i):32 * (p * n + i) + 32] for i in range(n)] for p in range(count)]
+        return split(outs[0]), split(outs[1]), split(outs[2]), [fail[p] for p in range(count)]
+
     # ---------------------------------------------------------- profiling
     def profile(self, enable: bool = True):
         check(self.lib.bpp_ctx_profile(self.h, 1 if enable else 0), "bpp_ctx_profile", self.h)
@@ -814,13 +832,20 @@ class Circuit:
     gadgets.CircuitHints: one hint per auxiliary value) is created through
     bpp_circuit_create_hinted, and CircuitProver.prove_batch then derives aux
     on the GPU; hints=False forces the plain entry point.  Hints are no part
-    of the statement either."""
+    of the statement either.  When a hint names x or a wire (a late hint,
+    gadgets.CircuitBuilder.derived) the entry point is
+    bpp_circuit_create_wire_hinted: the witness kernel evaluates such a hint
+    when it reaches the gate it feeds."""
 
     LARGE, TILED = 1, 2  # BPP_CIRCUIT_LARGE, BPP_CIRCUIT_TILED
 
     def __init__(self, desc, large: bool = False, tiled: bool = False, flags: "int | None" = None,
-                 hints: bool = True):
-        """flags: the raw flag word in place of large / tiled (tests)."""
+                 hints: bool = True, wire_hints: "bool | None" = None):
+        """flags: the raw flag word in place of large / tiled (tests).
+        wire_hints: bpp_circuit_create_wire_hinted (True) or
+        bpp_circuit_create_hinted (False); None: the former when desc.hints
+        says that a hint names x or a wire (CircuitHints.wire, which
+        CircuitBuilder.build() sets), else the latter, which refuses such ids."""
         self.lib = _lib.load()
         self.desc = desc
         if flags is None:
@@ -840,8 +865,11 @@ class Circuit:
                 raise ValueError("hints: lc_var / lc_coef shorter than lc_off says")
             self._keep_hints = (u32a(hd.op), u32a(hd.lc_off), u32a(hd.lc_var), b"".join(hd.lc_coef))
             hc = _CircuitHintsC(*self._keep_hints)
-            check(self.lib.bpp_circuit_create_hinted(C.byref(d), getattr(desc, "n_pub", 0), flags, C.byref(hc),
-                                                     C.byref(h)), "bpp_circuit_create_hinted")
+            # (hints that name x or a wire, as CircuitHints.wire says: the entry point that takes them)
+            wire = bool(getattr(hd, "wire", False)) if wire_hints is None else wire_hints
+            create = "bpp_circuit_create_wire_hinted" if wire else "bpp_circuit_create_hinted"
+            check(getattr(self.lib, create)(C.byref(d), getattr(desc, "n_pub", 0), flags, C.byref(hc), C.byref(h)),
+                  create)
         elif flags:
             check(self.lib.bpp_circuit_create_ex(C.byref(d), getattr(desc, "n_pub", 0), flags, C.byref(h)),
                   "bpp_circuit_create_ex")
@@ -893,6 +921,18 @@ class Circuit:
             raise ValueError("hint_eval: expected m_in scalars in v and n_pub in pub")
         out = C.create_string_buffer(max(32 * self.n_aux, 1))
         check(self.lib.bpp_circuit_hint_eval(self.h, _buf(vb), _buf(ub), out), "bpp_circuit_hint_eval")
+        return [out.raw[32 * i:32 * i + 32] for i in range(self.n_aux)]
+
+    def hint_eval_x(self, v, x: bytes, pub=None):
+        """The hints' host reference with x (bpp_circuit_hint_eval_x; no GPU):
+        all n_aux values, early hints as hint_eval gives them, late hints in
+        gate order from the wires so far.  eval(v, that, x) is the witness."""
+        vb = _join(v, 32, "v")
+        ub = _join(pub, 32, "pub") if pub is not None else b""
+        if len(vb) != 32 * self.m_in or len(ub) != 32 * self.n_pub or len(x) != 32:
+            raise ValueError("hint_eval_x: expected m_in scalars in v, n_pub in pub and one in x")
+        out = C.create_string_buffer(max(32 * self.n_aux, 1))
+        check(self.lib.bpp_circuit_hint_eval_x(self.h, _buf(vb), _buf(ub), _buf(x), out), "bpp_circuit_hint_eval_x")
         return [out.raw[32 * i:32 * i + 32] for i in range(self.n_aux)]
 
     def eval(self, v, aux, x: bytes, pub=None):

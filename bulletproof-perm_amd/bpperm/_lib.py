@@ -116,6 +116,9 @@ SIGNATURES = {
     "bpp_circuit_has_hints": (i32, [vp]),
     "bpp_circuit_hint_eval": (i32, [vp, vp, vp, vp]),
     "bpp_debug_circuit_hints": (i32, [vp, vp, sz, vp, vp, vp]),
+    "bpp_circuit_create_wire_hinted": (i32, [vp, u32, u32, vp, C.POINTER(vp)]),
+    "bpp_circuit_hint_eval_x": (i32, [vp, vp, vp, vp, vp]),
+    "bpp_debug_circuit_witness": (i32, [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
     "bpp_circuit_n_pub": (u32, [vp]),
     "bpp_circuit_eval_pub": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u32)]),
     "bpp_circuit_prove_batch_pub": (i32, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp]),

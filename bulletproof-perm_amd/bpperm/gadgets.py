@@ -21,6 +21,15 @@ them (CircuitDesc.hints) and the prover needs no aux from its caller:
 
     inv = b.hint(HINT_INV, v0 - v1)
     b.assert_zero(b.mul(v0 - v1, inv)[2] - 1)   # v0 != v1
+
+b.derived(op, lc, arg) is hint() over the whole variable space of a defined
+side: lc may also read x and wires of EARLIER gates (a late hint,
+bpp_circuit_create_wire_hinted).  The prover evaluates it inside the witness
+kernel when it reaches the gate, so a free side can depend on a product formed
+earlier in the same circuit:
+
+    p = b.mul(v0 - v1, v0 - v2)[2]
+    b.assert_zero(b.mul(p, b.derived(HINT_INV, p))[2] - 1)   # v0 is neither v1 nor v2
 """
 from __future__ import annotations
 
@@ -87,6 +96,8 @@ class CircuitHints:
     lc_off: list
     lc_var: list
     lc_coef: list
+    # a hint names x or a wire (CircuitBuilder.derived): bpp_circuit_create_wire_hinted takes these
+    wire: bool = False
 
 
 class Hint:
@@ -165,15 +176,33 @@ class CircuitBuilder:
         self.n_aux += 1
         return Hint(self.n_aux - 1)
 
+    def derived(self, op: int, lc, arg: int = 0) -> Hint:
+        """hint() over {1, v_j, x, u_i, wires}: a free side whose value the
+        prover derives when it reaches the gate (a late hint when lc reads x or
+        a wire; bpp_circuit_create_wire_hinted).  The gate it feeds comes after
+        every gate whose wire lc reads (mul() checks)."""
+        lc = LC.of(lc)
+        if op not in (HINT_VALUE, HINT_BIT, HINT_NOT_BIT, HINT_INV, HINT_IS_ZERO):
+            raise ValueError(f"derived: unknown op {op}")
+        if not 0 <= arg <= 252 or (arg and op not in (HINT_BIT, HINT_NOT_BIT)):
+            raise ValueError("derived: arg is a bit index <= 252, for HINT_BIT / HINT_NOT_BIT only")
+        self.hints.append((op, arg, lc))
+        self.n_aux += 1
+        return Hint(self.n_aux - 1)
+
     def mul(self, left, right):
         """A gate whose sides are defined (linear combinations) or hinted free
-        sides (hint()); returns its wires (l, r, o)."""
+        sides (hint(), derived()); returns its wires (l, r, o)."""
         g = len(self.sides)
         sides = [s.index if isinstance(s, Hint) else LC.of(s) for s in (left, right)]
         for side in sides:
             for (kind, h, _s) in (side.t if isinstance(side, LC) else ()):
                 if kind == _W and h >= g:
                     raise ValueError(f"gate {g}: a definition reads a wire of gate {h}")
+            if not isinstance(side, LC) and side < len(self.hints) and self.hints[side] is not None:
+                for (kind, h, _s) in self.hints[side][2].t:
+                    if kind == _W and h >= g:
+                        raise ValueError(f"gate {g}: a derived side reads a wire of gate {h}")
         self.sides.append(sides)
         return self._wires(g)
 
@@ -221,6 +250,7 @@ class CircuitBuilder:
             for op, arg, lc in self.hints:
                 hints.op.append(op | arg << 8)
                 emit(lc, hints.lc_off, hints.lc_var, hints.lc_coef)
+                hints.wire = hints.wire or any(kind in (_X, _W) for (kind, _i, _s) in lc.t)
         return CircuitDesc(m_in, n, self.n_aux, len(self.asserts), side_aux, lc_off, lc_var, lc_coef, aux_of, n_pub,
                            hints)
 
@@ -410,6 +440,147 @@ def same_multiset(k: int) -> CircuitDesc:
         ends.append(o)
     b.assert_zero(ends[0] - ends[1])
     return b.build()
+
+
+# ------------------------------------- gadgets whose hints read earlier wires
+
+def derive_aux(desc: CircuitDesc, vals: Sequence[int]) -> list:
+    """The n_aux auxiliary values of a description whose hints read neither x
+    nor a public input, from v alone: the hints over {1, v_j} first, then the
+    gates in order, each late hint from the wires so far (what the prover's
+    witness kernel does).  The aux_of of the gadgets below."""
+    h, m_in = desc.hints, desc.m_in
+    wbase = 2 + m_in + desc.n_pub
+    v = [int(a) % L for a in vals]
+    wires = [0] * (3 * desc.n_gates)
+
+    def lc(off, var, coef, i):
+        w = 0
+        for e in range(off[i], off[i + 1]):
+            vid = var[e]
+            if vid == 0:
+                val = 1
+            elif vid <= m_in:
+                val = v[vid - 1]
+            elif vid < wbase:
+                raise ValueError("derive_aux: the combination reads x or a public input")
+            else:
+                val = wires[vid - wbase]
+            w += int.from_bytes(coef[e], "little") * val
+        return w % L
+
+    def hint(t):
+        w = lc(h.lc_off, h.lc_var, h.lc_coef, t)
+        op, arg = h.op[t] & 0xFF, h.op[t] >> 8
+        return {HINT_VALUE: w, HINT_BIT: (w >> arg) & 1, HINT_NOT_BIT: 1 - ((w >> arg) & 1),
+                HINT_INV: pow(w, L - 2, L), HINT_IS_ZERO: int(w == 0)}[op]
+
+    late = [any(x >= wbase for x in h.lc_var[h.lc_off[t]:h.lc_off[t + 1]]) for t in range(desc.n_aux)]
+    aux = [0 if late[t] else hint(t) for t in range(desc.n_aux)]
+    for g in range(desc.n_gates):
+        for s in range(2):
+            a = desc.side_aux[2 * g + s]
+            if a != SIDE_LC and late[a]:
+                aux[a] = hint(a)
+            wires[3 * g + s] = lc(desc.lc_off, desc.lc_var, desc.lc_coef, 2 * g + s) if a == SIDE_LC else aux[a]
+        wires[3 * g + 2] = wires[3 * g] * wires[3 * g + 1] % L
+    return aux
+
+
+def _with_derived_aux(b: CircuitBuilder) -> CircuitDesc:
+    desc = b.build()
+    desc.aux_of = lambda vals: derive_aux(desc, vals)
+    return desc
+
+
+def _derived_bits(b: CircuitBuilder, target: LC, nbits: int):
+    """_range_bits with derived() in place of hint(): target may read wires of
+    earlier gates.  Returns the (l, r) wires of each bit's gate: the bit and
+    1 - the bit."""
+    total, out = LC(), []
+    for i in range(nbits):
+        l, r, o = b.mul(b.derived(HINT_BIT, target, i), b.derived(HINT_NOT_BIT, target, i))
+        b.assert_zero(o)
+        b.assert_zero(l + r - 1)
+        total = total + l * (1 << i)
+        out.append((l, r))
+    b.assert_zero(total - target)
+    return out
+
+
+def max_of(k: int, nbits: int) -> CircuitDesc:
+    """v_0..v_{k-1} are below 2^nbits and v_k is their maximum.  Every v_i takes
+    in_range's nbits bit gates.  The running maximum M_0 = v_0, M_i = v_i + o_i:
+    step i decomposes d_i = v_i - M_{i-1} - 1 + 2^nbits into nbits + 1 bits, whose
+    top bit c_i says v_i > M_{i-1}, and a gate (1 - c_i) (M_{i-1} - v_i) = o_i.
+    From step 2 on d_i reads the gate output o_{i-1}: its bits are late hints.
+    The last assert is M_{k-1} - v_k = 0.  k nbits + (k - 1)(nbits + 2) gates;
+    nbits <= 249."""
+    if k < 1:
+        raise ValueError("k >= 1")
+    if not 1 <= nbits <= 249:
+        raise ValueError("1 <= nbits <= 249")
+    b = CircuitBuilder()
+    v = b.inputs(k + 1)
+    for x in v[:k]:
+        _range_bits(b, x, nbits)
+    m = v[0]
+    for i in range(1, k):
+        bits = _derived_bits(b, v[i] - m - 1 + (1 << nbits), nbits + 1)
+        m = v[i] + b.mul(bits[nbits][1], m - v[i])[2]
+    b.assert_zero(m - v[k])
+    return _with_derived_aux(b)
+
+
+def not_among(k: int) -> CircuitDesc:
+    """v_0 differs from each of v_1..v_k ("my card is none of those"): the
+    product of the k differences over k - 1 gates, then one gate p * p^-1 whose
+    free side is the inverse of the product wire (a late hint for k >= 2) and
+    one assert o - 1 = 0.  A repeat makes p = 0: the hint is 0 and the assert
+    does not hold."""
+    if k < 1:
+        raise ValueError("k >= 1")
+    b = CircuitBuilder()
+    v = b.inputs(k + 1)
+    p = v[0] - v[1]
+    for j in range(2, k + 1):
+        p = b.mul(p, v[0] - v[j])[2]
+    b.assert_zero(b.mul(p, b.derived(HINT_INV, p))[2] - 1)
+    return _with_derived_aux(b)
+
+
+def blackjack_total(k: int) -> CircuitDesc:
+    """The k hidden ranks v_i are in 1..13 and the public u_0 is the hand's
+    blackjack total S + 10 soft: S = sum min(v_i, 10), soft = 1 exactly when some
+    v_i = 1 and S <= 11.  Per card: v_i - 1 and 13 - v_i in 4 bits (the rank
+    range), v_i + 5 in 5 bits whose top bit f_i says v_i >= 11, a gate f_i (v_i -
+    10) = q_i (min(v_i, 10) = v_i - q_i), and is-zero of v_i - 1 over two gates
+    (w inv = 1 - a_i, w a_i = 0).  Then the chain prod (1 - a_i), the bits of d =
+    11 - S + 2^B (late hints: S reads every q_i), whose top bit says S <= 11, a
+    gate (1 - prod) * that bit = soft, and the assert u_0 - S - 10 soft = 0."""
+    if k < 1:
+        raise ValueError("k >= 1")
+    b = CircuitBuilder()
+    v = b.inputs(k)
+    u = b.public()
+    S, none = LC(), None
+    for x in v:
+        _range_bits(b, x - 1, 4)
+        _range_bits(b, 13 - x, 4)
+        n0 = len(b.sides)
+        _range_bits(b, x + 5, 5)
+        face = b._wires(n0 + 4)[0]
+        S = S + x - b.mul(face, x - 10)[2]
+        o1 = b.mul(x - 1, b.hint(HINT_INV, x - 1))[2]
+        _l, ace, o2 = b.mul(x - 1, b.hint(HINT_IS_ZERO, x - 1))
+        b.assert_zero(o2)
+        b.assert_zero(o1 - 1 + ace)
+        none = 1 - ace if none is None else b.mul(none, 1 - ace)[2]
+    B = max(4, (10 * k - 11).bit_length())  # (2^B > 10 k - 11 >= S - 11: d >= 0, and its bit B says S <= 11)
+    low = _derived_bits(b, 11 - S + (1 << B), B + 1)[B][0]
+    soft = b.mul(1 - none, low)[2]
+    b.assert_zero(u - S - 10 * soft)
+    return _with_derived_aux(b)
 
 
 # ------------------------------------------------- gadgets over public inputs

@@ -49,12 +49,33 @@ int circuit_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* aux, con
   });
 }
 
-}  // namespace
+// bpp_circuit_hint_eval (x == nullptr; not for a circuit with late hints) and bpp_circuit_hint_eval_x
+int circuit_hint_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* pub, const uint8_t* x, bool with_x,
+                      uint8_t* aux_out) {
+  return bpp_guard(nullptr, [&]() -> int {
+    if (!c || !v || (with_x && !x)) return BPP_ERR_ARG;
+    const circuit::Program& P = *c->C.program;
+    if (!P.hints || (!pub && P.n_pub) || (!aux_out && P.n_aux)) return BPP_ERR_ARG;
+    if (!with_x && circuit::has_late_hints(P)) return BPP_ERR_ARG;
+    std::vector<Sc> vs(P.m_in), us(P.n_pub), as(P.n_aux);
+    Sc xs = hsc::zero();
+    for (uint32_t j = 0; j < P.m_in; ++j)
+      if (!hsc::from_canonical(vs[j], v + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
+    for (uint32_t j = 0; j < P.n_pub; ++j)
+      if (!hsc::from_canonical(us[j], pub + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
+    if (with_x && !hsc::from_canonical(xs, x)) return BPP_ERR_NONCANONICAL;
+    if (with_x)
+      circuit::hint_eval_x(P, vs.data(), us.data(), xs, as.data());
+    else
+      circuit::hint_eval(P, vs.data(), us.data(), as.data());
+    if (P.n_aux) memcpy(aux_out, as.data(), 32 * (size_t)P.n_aux);  // (canonical Sc == its 32 bytes)
+    for (auto* s : {&vs, &as}) std::fill(s->begin(), s->end(), hsc::zero());
+    return BPP_OK;
+  });
+}
 
-extern "C" {
-
-int bpp_circuit_create_hinted(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags,
-                              const bpp_circuit_hints* hints, bpp_circuit** out) {
+int create_hinted(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags, const bpp_circuit_hints* hints,
+                  bool wire_hints, bpp_circuit** out) {
   return bpp_guard(nullptr, [&]() -> int {
     if (!desc || !out) return BPP_ERR_ARG;
     *out = nullptr;
@@ -66,10 +87,24 @@ int bpp_circuit_create_hinted(const bpp_circuit_desc* desc, uint32_t n_pub, uint
     if (hints) h = {hints->op, hints->lc_off, hints->lc_var, hints->lc_coef};
     std::unique_ptr<bpp_circuit> c(new bpp_circuit());
     std::string err;
-    BPP_TRY(circuit::compile(d, c->C, err, hints ? &h : nullptr));
+    BPP_TRY(circuit::compile(d, c->C, err, hints ? &h : nullptr, wire_hints));
     *out = c.release();
     return BPP_OK;
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int bpp_circuit_create_hinted(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags,
+                              const bpp_circuit_hints* hints, bpp_circuit** out) {
+  return create_hinted(desc, n_pub, flags, hints, false, out);
+}
+
+int bpp_circuit_create_wire_hinted(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags,
+                                   const bpp_circuit_hints* hints, bpp_circuit** out) {
+  return create_hinted(desc, n_pub, flags, hints, true, out);
 }
 
 int bpp_circuit_create_ex(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags, bpp_circuit** out) {
@@ -91,20 +126,12 @@ uint32_t bpp_circuit_n_pub(const bpp_circuit* c) { return c ? c->C.n_pub : 0; }
 int bpp_circuit_has_hints(const bpp_circuit* c) { return c && c->C.program->hints ? 1 : 0; }
 
 int bpp_circuit_hint_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* pub, uint8_t* aux_out) {
-  return bpp_guard(nullptr, [&]() -> int {
-    if (!c || !v) return BPP_ERR_ARG;
-    const circuit::Program& P = *c->C.program;
-    if (!P.hints || (!pub && P.n_pub) || (!aux_out && P.n_aux)) return BPP_ERR_ARG;
-    std::vector<Sc> vs(P.m_in), us(P.n_pub), as(P.n_aux);
-    for (uint32_t j = 0; j < P.m_in; ++j)
-      if (!hsc::from_canonical(vs[j], v + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
-    for (uint32_t j = 0; j < P.n_pub; ++j)
-      if (!hsc::from_canonical(us[j], pub + 32 * (size_t)j)) return BPP_ERR_NONCANONICAL;
-    circuit::hint_eval(P, vs.data(), us.data(), as.data());
-    if (P.n_aux) memcpy(aux_out, as.data(), 32 * (size_t)P.n_aux);  // (canonical Sc == its 32 bytes)
-    for (auto* s : {&vs, &as}) std::fill(s->begin(), s->end(), hsc::zero());
-    return BPP_OK;
-  });
+  return circuit_hint_eval(c, v, pub, nullptr, false, aux_out);
+}
+
+int bpp_circuit_hint_eval_x(const bpp_circuit* c, const uint8_t* v, const uint8_t* pub, const uint8_t x[32],
+                            uint8_t* aux_out) {
+  return circuit_hint_eval(c, v, pub, x, true, aux_out);
 }
 
 // Test hook: k_hint_aux alone over count proofs' v and pub, the derived values
@@ -114,6 +141,10 @@ int bpp_debug_circuit_hints(bpp_ctx* ctx, const bpp_circuit* c, size_t count, co
   return bpp_guard(ctx, [&]() -> int {
     if (!ctx || !c || !c->C.program->hints) return BPP_ERR_ARG;
     const circuit::Program& P = *c->C.program;
+    if (circuit::has_late_hints(P)) {
+      ctx->err = "the circuit has late hints, which have no value without x: bpp_debug_circuit_witness";
+      return BPP_ERR_ARG;
+    }
     if (!count || !P.n_aux) return BPP_OK;
     if (!v || !aux_out || (!pub && P.n_pub) || count > 0xFFFFFFFFu) return BPP_ERR_ARG;
     std::vector<int> bad(count, BPP_OK);
@@ -139,6 +170,69 @@ int bpp_debug_circuit_hints(bpp_ctx* ctx, const bpp_circuit* c, size_t count, co
     if (rc == BPP_OK) rc = ctx_sync(ctx);
     if (rc == BPP_OK && hipMemcpy(aux_out, d_aux, count * 32 * (size_t)P.n_aux, hipMemcpyDeviceToHost) != hipSuccess)
       rc = BPP_ERR_DEVICE;
+    const int wrc = prove_wipe(ctx);
+    return rc ? rc : wrc;
+  });
+}
+
+// Test hook: the witness kernels alone.  k_hint_aux where the circuit has early
+// hints, then the witness kernel a batch of this circuit launches, over count
+// proofs' v, pub and the caller's x; a_L, a_R, a_O ([count][n_p], canonical)
+// and each proof's fail word back to the host.  Staged and wiped as a batch is.
+int bpp_debug_circuit_witness(bpp_ctx* ctx, const bpp_circuit* c, size_t count, const uint8_t* v, const uint8_t* pub,
+                              const uint8_t* x, uint8_t* aL, uint8_t* aR, uint8_t* aO, uint32_t* fail) {
+  return bpp_guard(ctx, [&]() -> int {
+    if (!ctx || !c) return BPP_ERR_ARG;
+    const circuit::Program& P = *c->C.program;
+    if (P.n_aux && !P.hints) {
+      ctx->err = "bpp_debug_circuit_witness: the circuit's auxiliary values have no hints";
+      return BPP_ERR_ARG;
+    }
+    if (!count) return BPP_OK;
+    if (!v || !x || !aL || !aR || !aO || !fail || (!pub && P.n_pub) || count > 0xFFFFFFFFu) return BPP_ERR_ARG;
+    std::vector<int> bad(count, BPP_OK);
+    check_canonical(v, P.m_in, count, bad);
+    check_canonical(pub, P.n_pub, count, bad);
+    check_canonical(x, 1, count, bad);
+    if (first_bad(bad) != SIZE_MAX) return BPP_ERR_NONCANONICAL;
+    BPP_HIP(hipSetDevice(ctx->device));
+    const uint32_t n_p = c->C.n_p, per = 3 + 5 * n_p;  // (the prover's A_I / A_O / S scalar rows)
+    const size_t vb = count * 32 * (size_t)P.m_in, ub = count * 32 * (size_t)P.n_pub, xb = count * 32;
+    void *d_in = nullptr, *d_aux = nullptr, *d_s = nullptr;
+    uint8_t* stage = nullptr;
+    uint32_t* h_fail = nullptr;
+    BPP_TRY(ctx_ws(ctx, "pb_rng_in", vb + ub + xb, &d_in));
+    BPP_TRY(ctx_h2d_stage(ctx, vb + ub + xb, &stage));
+    ctx_secret_span(ctx, stage, vb + ub + xb);
+    memcpy(stage, v, vb);
+    if (ub) memcpy(stage + vb, pub, ub);
+    memcpy(stage + vb + ub, x, xb);
+    const uint32_t* d_v = (const uint32_t*)d_in;
+    const uint32_t* d_pub = ub ? (const uint32_t*)((const uint8_t*)d_in + vb) : nullptr;
+    const uint32_t* d_x = (const uint32_t*)((const uint8_t*)d_in + vb + ub);
+    int rc = ctx_h2d_staged(ctx, d_in, stage, vb + ub + xb);
+    if (rc == BPP_OK) rc = ctx_ws(ctx, "mt_s", count * (size_t)per * 32 + 32, &d_s);
+    if (rc == BPP_OK) rc = ctx_zc_out(ctx, "wp_fail_h", count * 4, &h_fail);
+    if (rc == BPP_OK && P.n_aux) {
+      rc = ctx_ws(ctx, "pb_aux_hint", count * 32 * (size_t)P.n_aux, &d_aux);
+      if (rc == BPP_OK) rc = hint_aux_dev(ctx, c->C, (uint32_t)count, d_v, d_pub, (uint32_t*)d_aux);
+    }
+    if (rc == BPP_OK)
+      rc = witness_program_dev(ctx, c->C, (uint32_t)count, d_v, (const uint32_t*)d_aux, d_x, per, (uint32_t*)d_s, h_fail,
+                               d_pub, true);
+    if (rc == BPP_OK) rc = ctx_sync(ctx);
+    if (rc == BPP_OK) {
+      std::vector<uint8_t> rows(count * (size_t)per * 32);
+      if (hipMemcpy(rows.data(), d_s, rows.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = BPP_ERR_DEVICE;
+      for (size_t p = 0; p < count && rc == BPP_OK; ++p) {
+        const uint8_t* row = rows.data() + p * (size_t)per * 32;
+        memcpy(aL + p * 32 * (size_t)n_p, row + 32 * (size_t)1, 32 * (size_t)n_p);
+        memcpy(aR + p * 32 * (size_t)n_p, row + 32 * (size_t)(1 + n_p), 32 * (size_t)n_p);
+        memcpy(aO + p * 32 * (size_t)n_p, row + 32 * (size_t)(2 + 2 * n_p), 32 * (size_t)n_p);
+        fail[p] = h_fail[p];
+      }
+      std::fill(rows.begin(), rows.end(), 0);
+    }
     const int wrc = prove_wipe(ctx);
     return rc ? rc : wrc;
   });
@@ -189,7 +283,8 @@ int bpp_circuit_prove_batch_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circu
   return bpp_guard(ctx, [&]() -> int {
     if (!c || (!label && llen)) return BPP_ERR_ARG;
     const uint32_t m_in = c->C.nv, n_aux = c->C.program->n_aux;
-    // aux == NULL on a circuit with hints: the values are derived on the GPU (k_hint_aux)
+    // aux == NULL on a circuit with hints: the values are derived on the GPU (k_hint_aux; late
+    // hints inside the witness kernel)
     const bool derive = !aux && n_aux && c->C.program->hints;
     if ((!v || (!aux && n_aux && !derive) || !proofs_out || !V_out) && count) return BPP_ERR_ARG;
     if (!pub && c->C.n_pub && count) return BPP_ERR_ARG;

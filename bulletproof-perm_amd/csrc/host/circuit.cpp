@@ -37,10 +37,11 @@ uint32_t dev_term(uint32_t var, const Sc& a) {
   return var | (a == one ? kTermOne : a == neg1 ? kTermNeg : 0u);
 }
 
-// Validates the hint program of a circuit with m_in inputs, n_pub public inputs
-// and n_aux auxiliary values, and builds its device image.
-int compile_hints(const HintDesc& h, uint32_t m_in, uint32_t n_pub, uint32_t n_aux, std::shared_ptr<const Hints>& out,
-                  std::string& err) {
+// Validates the hint program of a circuit with m_in inputs, n_pub public inputs,
+// n gates and n_aux auxiliary values, and builds its device image.  wire_hints:
+// ids range over x and the 3n wires too, and a hint that names one is late.
+int compile_hints(const HintDesc& h, uint32_t m_in, uint32_t n_pub, uint32_t n, uint32_t n_aux, bool wire_hints,
+                  std::shared_ptr<const Hints>& out, std::string& err) {
   auto fail = [&](int rc, std::string what) {
     err = "circuit hints: " + what;
     return rc;
@@ -60,7 +61,8 @@ int compile_hints(const HintDesc& h, uint32_t m_in, uint32_t n_pub, uint32_t n_a
   H->lc_off.assign(h.lc_off, h.lc_off + n_aux + 1);
   H->lc_var.assign(h.lc_var, h.lc_var + T);
   H->lc_coef.resize(T);
-  const uint32_t x_id = 1 + m_in, wbase = 2 + m_in + n_pub;
+  const uint32_t x_id = 1 + m_in, wbase = 2 + m_in + n_pub, nvar = wbase + 3 * n;
+  if (wire_hints) H->late.assign(n_aux, 0);
   for (uint32_t t = 0; t < n_aux; ++t) {
     const std::string where = "hint " + std::to_string(t);
     const uint32_t op = h.op[t] & 0xFFu, arg = h.op[t] >> 8;
@@ -69,22 +71,35 @@ int compile_hints(const HintDesc& h, uint32_t m_in, uint32_t n_pub, uint32_t n_a
     if (arg > kHintMaxBit) return fail(ERR_ARG, where + ": bit index above 252");
     for (size_t e = h.lc_off[t]; e < h.lc_off[t + 1]; ++e) {
       const uint32_t var = h.lc_var[e];
-      if (var >= wbase) return fail(ERR_ARG, where + ": variable id out of range, or a wire");
-      if (var == x_id) return fail(ERR_ARG, where + ": reads x (aux exists before x does)");
+      if (wire_hints) {
+        if (var >= nvar) return fail(ERR_ARG, where + ": variable id beyond the last wire");
+        if (var == x_id || var >= wbase) H->late[t] = 1;
+      } else {
+        if (var >= wbase) return fail(ERR_ARG, where + ": variable id out of range, or a wire");
+        if (var == x_id) return fail(ERR_ARG, where + ": reads x (aux exists before x does)");
+      }
       if (e > h.lc_off[t] && var <= h.lc_var[e - 1]) return fail(ERR_ARG, where + ": ids not strictly increasing");
       if (!hsc::from_canonical(H->lc_coef[e], h.lc_coef + 32 * e))
         return fail(ERR_NONCANONICAL, where + ": coefficient not below l");
       if (hsc::is_zero(H->lc_coef[e])) return fail(ERR_ARG, where + ": zero coefficient");
     }
   }
-  // the lane order: by op, INV first, hints of one op in index order
+  for (uint8_t l : H->late) H->n_late += l;
+  if (!H->n_late) H->late.clear();
+  // the lane order: by op, INV first, hints of one op in index order (a late
+  // hint: the empty VALUE, a 0 that nothing reads)
+  auto is_late = [&](uint32_t t) { return !H->late.empty() && H->late[t]; };
   std::vector<uint32_t> order(n_aux);
   for (uint32_t t = 0; t < n_aux; ++t) order[t] = t;
-  auto rank = [&](uint32_t t) { return (H->op[t] & 0xFFu) == kHintInv ? 0u : 1u + (H->op[t] & 0xFFu); };
+  auto rank = [&](uint32_t t) {
+    const uint32_t op = is_late(t) ? (uint32_t)kHintValue : H->op[t] & 0xFFu;
+    return op == kHintInv ? 0u : 1u + op;
+  };
   std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rank(a) < rank(b); });
   std::vector<uint32_t>& dev = H->dev;
   for (uint32_t t : order) {
-    const uint32_t rec[4] = {t, H->op[t], H->lc_off[t], H->lc_off[t + 1]};
+    const uint32_t rec[4] = {t, is_late(t) ? (uint32_t)kHintValue : H->op[t], is_late(t) ? 0u : H->lc_off[t],
+                             is_late(t) ? 0u : H->lc_off[t + 1]};
     dev.insert(dev.end(), rec, rec + 4);
   }
   H->dev_vars = (uint32_t)dev.size();
@@ -103,7 +118,7 @@ int compile_hints(const HintDesc& h, uint32_t m_in, uint32_t n_pub, uint32_t n_a
 
 }  // namespace
 
-int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* hints) {
+int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* hints, bool wire_hints) {
   auto fail = [&](int rc, std::string what) {
     err = "circuit: " + what;
     return rc;
@@ -156,8 +171,30 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* h
     }
   }
   if (hints) {
-    const int rc = compile_hints(*hints, m_in, d.n_pub, d.n_aux, P->hints, err);
+    const int rc = compile_hints(*hints, m_in, d.n_pub, n, d.n_aux, wire_hints, P->hints, err);
     if (rc != OK) return rc;
+  }
+  if (has_late_hints(*P)) {
+    // a late hint's wires come from gates before every side it feeds, and the
+    // levels count them: again over the gates in order, definitions and late hints
+    const Hints& H = *P->hints;
+    std::fill(level.begin(), level.end(), 0);
+    for (uint32_t g = 0; g < n; ++g)
+      for (uint32_t s = 0; s < 2; ++s) {
+        const size_t i = 2 * (size_t)g + s;
+        const uint32_t a = d.side_aux[i];
+        if (a != SIDE_LC && !H.late[a]) continue;
+        const uint32_t* var = a == SIDE_LC ? d.lc_var : H.lc_var.data();
+        const size_t b = a == SIDE_LC ? d.lc_off[i] : H.lc_off[a], e = a == SIDE_LC ? d.lc_off[i + 1] : H.lc_off[a + 1];
+        for (size_t t = b; t < e; ++t) {
+          if (var[t] < wbase) continue;
+          const uint32_t h = (var[t] - wbase) / 3;
+          if (h >= g)
+            return fail(ERR_ARG, "gate " + std::to_string(g) + (s ? " right" : " left") + ": its late hint " +
+                                     std::to_string(a) + " reads a wire of gate " + std::to_string(h));
+          level[g] = std::max(level[g], level[h] + 1);
+        }
+      }
   }
   C = perm::Circuit();
   C.k = 0;  // (no cards: nothing downstream of the witness reads k)
@@ -232,13 +269,35 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* h
   dev.insert(dev.end(), P->level_off.begin(), P->level_off.end());
   P->dev_level_gate = (uint32_t)dev.size();
   dev.insert(dev.end(), P->level_gate.begin(), P->level_gate.end());
+  // late hints: a record per side, and their terms behind the description's T
+  std::vector<uint32_t> late_var;
+  std::vector<Sc> late_coef;
+  if (has_late_hints(*P)) {
+    const Hints& H = *P->hints;
+    std::vector<uint32_t> at(d.n_aux, 0xFFFFFFFFu);  // where hint a's terms begin (one copy however many sides it feeds)
+    P->dev_late = (uint32_t)dev.size();
+    for (size_t i = 0; i < 2 * (size_t)n; ++i) {
+      const uint32_t a = P->side_aux[i];
+      uint32_t rec[3] = {kNoLateHint, 0, 0};
+      if (a != SIDE_LC && H.late[a]) {
+        if (at[a] == 0xFFFFFFFFu) {
+          at[a] = (uint32_t)(T + late_var.size());
+          late_var.insert(late_var.end(), H.lc_var.begin() + H.lc_off[a], H.lc_var.begin() + H.lc_off[a + 1]);
+          late_coef.insert(late_coef.end(), H.lc_coef.begin() + H.lc_off[a], H.lc_coef.begin() + H.lc_off[a + 1]);
+        }
+        rec[0] = H.op[a], rec[1] = at[a], rec[2] = at[a] + (H.lc_off[a + 1] - H.lc_off[a]);
+      }
+      dev.insert(dev.end(), rec, rec + 3);
+    }
+  }
   P->dev_vars = (uint32_t)dev.size();
   for (size_t t = 0; t < T; ++t) dev.push_back(dev_term(P->lc_var[t], P->lc_coef[t]));
+  for (size_t t = 0; t < late_var.size(); ++t) dev.push_back(dev_term(late_var[t], late_coef[t]));
   dev.resize((dev.size() + 7) & ~(size_t)7, 0);
   P->dev_coefs = (uint32_t)dev.size();
-  for (size_t t = 0; t < T; ++t) {
+  for (size_t t = 0; t < T + late_var.size(); ++t) {
     uint32_t w[8];
-    const Sc cR = hsc::to_mont(P->lc_coef[t]);
+    const Sc cR = hsc::to_mont(t < T ? P->lc_coef[t] : late_coef[t - T]);
     memcpy(w, cR.v, 32);
     dev.insert(dev.end(), w, w + 8);
   }
@@ -281,6 +340,21 @@ void eval(const Program& P, uint32_t n_p, const Sc* v, const Sc* aux, const Sc& 
     }
 }
 
+namespace {
+
+// op(w) of a hint's op word
+Sc hint_op(uint32_t word, const Sc& w) {
+  const uint32_t op = word & 0xFFu, arg = word >> 8;
+  const uint64_t bit = (w.v[arg >> 6] >> (arg & 63)) & 1;  // (arg = 0 for the ops without one)
+  return op == kHintValue    ? w
+         : op == kHintBit    ? hsc::from_u64(bit)
+         : op == kHintNotBit ? hsc::from_u64(1 - bit)
+         : op == kHintInv    ? hsc::invert(w)  // (w^(l - 2): 0 for w = 0)
+                             : hsc::from_u64(hsc::is_zero(w) ? 1 : 0);
+}
+
+}  // namespace
+
 void hint_eval(const Program& P, const Sc* v, const Sc* pub, Sc* aux) {
   const Hints& H = *P.hints;
   for (uint32_t t = 0; t < P.n_aux; ++t) {
@@ -290,15 +364,42 @@ void hint_eval(const Program& P, const Sc* v, const Sc* pub, Sc* aux) {
       const Sc val = var == 0 ? hsc::one() : var <= P.m_in ? v[var - 1] : pub[var - 2 - P.m_in];
       w = hsc::add(w, hsc::mul(H.lc_coef[e], val));
     }
-    const uint32_t op = H.op[t] & 0xFFu, arg = H.op[t] >> 8;
-    const uint64_t bit = (w.v[arg >> 6] >> (arg & 63)) & 1;  // (arg = 0 for the ops without one)
-    aux[t] = op == kHintValue    ? w
-             : op == kHintBit    ? hsc::from_u64(bit)
-             : op == kHintNotBit ? hsc::from_u64(1 - bit)
-             : op == kHintInv    ? hsc::invert(w)  // (w^(l - 2): 0 for w = 0)
-                                 : hsc::from_u64(hsc::is_zero(w) ? 1 : 0);
+    aux[t] = hint_op(H.op[t], w);
     w = hsc::zero();
   }
+}
+
+void hint_eval_x(const Program& P, const Sc* v, const Sc* pub, const Sc& x, Sc* aux) {
+  const Hints& H = *P.hints;
+  const uint32_t m_in = P.m_in, n = P.n, wbase = 2 + m_in + P.n_pub;
+  std::vector<Sc> wires(3 * (size_t)n, hsc::zero());  // l_h, r_h, o_h at 3h + {0, 1, 2}
+  auto lc = [&](const std::vector<uint32_t>& off, const std::vector<uint32_t>& vars, const std::vector<Sc>& coef,
+                size_t i) {
+    Sc acc = hsc::zero();
+    for (size_t t = off[i]; t < off[i + 1]; ++t) {
+      const uint32_t var = vars[t];
+      const Sc val = var == 0          ? hsc::one()
+                     : var <= m_in     ? v[var - 1]
+                     : var == 1 + m_in ? x
+                     : var < wbase     ? pub[var - 2 - m_in]
+                                       : wires[var - wbase];
+      acc = hsc::add(acc, hsc::mul(coef[t], val));
+    }
+    return acc;
+  };
+  auto late = [&](uint32_t t) { return !H.late.empty() && H.late[t]; };
+  for (uint32_t t = 0; t < P.n_aux; ++t)
+    aux[t] = late(t) ? hsc::zero() : hint_op(H.op[t], lc(H.lc_off, H.lc_var, H.lc_coef, t));
+  if (H.n_late)
+    for (uint32_t g = 0; g < n; ++g) {
+      for (uint32_t s = 0; s < 2; ++s) {
+        const uint32_t a = P.side_aux[2 * g + s];
+        if (a != SIDE_LC && late(a)) aux[a] = hint_op(H.op[a], lc(H.lc_off, H.lc_var, H.lc_coef, a));
+        wires[3 * (size_t)g + s] = a == SIDE_LC ? lc(P.lc_off, P.lc_var, P.lc_coef, 2 * (size_t)g + s) : aux[a];
+      }
+      wires[3 * (size_t)g + 2] = hsc::mul(wires[3 * (size_t)g], wires[3 * (size_t)g + 1]);
+    }
+  std::fill(wires.begin(), wires.end(), hsc::zero());
 }
 
 }  // namespace circuit

@@ -63,12 +63,21 @@ inline uint32_t var_wire(uint32_t m_in, uint32_t h, uint32_t lro, uint32_t n_pub
 // neither x (aux exists before x does) nor wires.  Attached at creation; no
 // part of the statement: digest, matrices, transcript and proof bytes do not
 // see it.
+//
+// Wire hints (bpp_circuit_create_wire_hinted): the combination ranges over the
+// variable space of a defined side, {1, v_j, x, u_i, wires}.  A hint that reads
+// x or a wire is LATE: it has no value before x exists, so it is evaluated
+// where the witness is, when the gate it feeds is reached -- once for each side
+// it feeds, from the wires of earlier gates (a late hint reading a wire of gate
+// h feeds sides of gates g > h only); one that feeds no side is never evaluated.
+// Every other hint is EARLY and is the hint above.
 enum : uint32_t { kHintValue = 0, kHintBit = 1, kHintNotBit = 2, kHintInv = 3, kHintIsZero = 4, kHintOps = 5 };
 constexpr uint32_t kHintMaxBit = 252;
+constexpr uint32_t kNoLateHint = 0xFFFFFFFFu;  // the op word of a side without a late hint (Program::dev)
 struct HintDesc {
   const uint32_t* op;       // [n_aux]
   const uint32_t* lc_off;   // [n_aux + 1]
-  const uint32_t* lc_var;   // [T]: 0 = one, 1 + j = v_j, 2 + m_in + i = u_i
+  const uint32_t* lc_var;   // [T]: 0 = one, 1 + j = v_j, 2 + m_in + i = u_i (wire hints: every id of Desc::lc_var)
   const uint8_t* lc_coef;   // [T][32]
 };
 struct Hints {
@@ -80,8 +89,12 @@ struct Hints {
   // so that the lanes of one wave run one op wherever the counts allow; then
   // the T terms' variable ids (| kTermOne / kTermNeg as in Program::dev), then
   // (from a multiple of 8 words) their Montgomery coefficients [T][8]
+  // A late hint has a record too, {t, VALUE, 0, 0}: its lane writes a 0 that
+  // nothing reads, and k_hint_aux stays the kernel it was.
   std::vector<uint32_t> dev;
   uint32_t dev_vars = 0, dev_coefs = 0;
+  std::vector<uint8_t> late;  // [n_aux]: the hint reads x or a wire (empty: no late hint)
+  uint32_t n_late = 0;
 };
 
 struct Program {
@@ -90,8 +103,8 @@ struct Program {
   std::vector<uint32_t> side_aux, lc_off, lc_var;
   std::vector<hsc::Sc> lc_coef;
   // gates by dependency level: level = 1 + the highest level among the gates
-  // whose wires its definitions read (0: none); level l = level_gate[level_off[l]
-  // .. level_off[l + 1])
+  // whose wires its definitions and its sides' late hints read (0: none); level
+  // l = level_gate[level_off[l] .. level_off[l + 1]).  Scheduling, not statement.
   std::vector<uint32_t> level_off, level_gate;
   // what k_witness_program reads, one upload: side_aux [2n], lc_off [2n + A + 1],
   // lc_wire [2n + A] (the first term of each combination that reads a wire: ids
@@ -99,9 +112,15 @@ struct Program {
   // 1], level_gate [n], the T terms' variable ids (| kTermOne: coefficient 1, |
   // kTermNeg: coefficient -1, no multiply), then (from a multiple of 8 words:
   // 32-byte aligned) their Montgomery coefficients [T][8]; word offsets of the
-  // six tables after side_aux
+  // six tables after side_aux.  With late hints (hints->n_late > 0) the image
+  // gains, behind level_gate at dev_late, a record of 3 words per side -- the
+  // op word of the side's late hint (kNoLateHint: none) and its terms [begin,
+  // end) -- and the late hints' terms behind the T terms of the description, in
+  // the same two tables (ids flagged, coefficients Montgomery), so one term loop
+  // serves both; without late hints the image is what it was.
   std::vector<uint32_t> dev;
   uint32_t dev_lc_off = 0, dev_lc_wire = 0, dev_level_off = 0, dev_level_gate = 0, dev_vars = 0, dev_coefs = 0;
+  uint32_t dev_late = 0;  // (0: no late hint)
   uint8_t digest[32] = {0};
 };
 
@@ -120,12 +139,23 @@ void digest(const Desc& d, uint8_t out[32]);
 // same way: ERR_ARG for an unknown op, arg > 252, an arg on an op that takes
 // none, an id out of range or naming x or a wire, unsorted ids, a zero
 // coefficient, a non-monotone lc_off; ERR_NONCANONICAL for a coefficient >= l.
-int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* hints = nullptr);
+// wire_hints (bpp_circuit_create_wire_hinted): a hint's ids range over x and
+// the wires too; ERR_ARG for an id beyond the last wire and for a late hint that
+// reads a wire of gate h and feeds a side of a gate g <= h (checked for every
+// side the aux index feeds).
+int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* hints = nullptr,
+            bool wire_hints = false);
+inline bool has_late_hints(const Program& P) { return P.hints && P.hints->n_late; }
 
 // The hints' host reference: aux [n_aux] from v [m_in] and pub [n_pub]
 // (canonical).  What BPP_CIRCUIT_HOST_WITNESS=1 runs in the prover, and what
-// k_hint_aux must equal.
+// k_hint_aux must equal.  Not for a circuit with late hints (it has no x).
 void hint_eval(const Program& P, const hsc::Sc* v, const hsc::Sc* pub, hsc::Sc* aux);
+// The same with x: the early hints as hint_eval gives them, then the gates in
+// order, each late hint from the wires so far, at every side it feeds (a late
+// hint that feeds no side stays 0).  eval over this aux is the witness; what
+// the late witness kernels must equal.
+void hint_eval_x(const Program& P, const hsc::Sc* v, const hsc::Sc* pub, const hsc::Sc& x, hsc::Sc* aux);
 
 // The host witness: a_L, a_R, a_O (n_p each, padding gates zero) from v
 // [m_in], aux [n_aux] and x; *bad_assert = 1 + the first assert that does not

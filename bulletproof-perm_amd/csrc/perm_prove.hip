@@ -297,6 +297,9 @@ struct ProveBatch {
   uint32_t *d_gamma = nullptr, *d_s = nullptr, *d_pi = nullptr;
   uint32_t *d_v = nullptr, *d_g = nullptr, *d_gx_half = nullptr;
   const uint32_t* d_aux = nullptr;  // a program's auxiliary values [P][n_aux]: uploaded, or derived ("pb_aux_hint")
+  // no aux rows on a circuit with hints: derived (k_hint_aux; late hints in the witness kernel), and nothing of
+  // them is staged or uploaded
+  const bool derive_aux = C.program && in && !in->aux.p && C.program->n_aux && C.program->hints;
   const uint32_t* d_pub = nullptr;  // a program's uploaded public inputs [P][n_pub]
   uint32_t *d_l = nullptr, *d_r = nullptr, *d_hf = nullptr;
   MsmPoints pts;
@@ -338,8 +341,6 @@ int ProveBatch::draws_upload() {
       ctx->err = "prove_batch: seeds of different lengths in one batch";
       return BPP_ERR_ARG;
     }
-  // (no aux rows on a circuit with hints: derived below, and nothing of them is staged or uploaded)
-  const bool derive_aux = C.program && in && !in->aux.p && C.program->n_aux && C.program->hints;
   if (C.program && !(in && in->values.p && (in->aux.p || !C.program->n_aux || derive_aux) && (in->pub.p || !C.n_pub))) {
     ctx->err = "prove_batch: a caller-defined circuit takes the caller's v, aux and public inputs";
     return BPP_ERR_ARG;
@@ -385,9 +386,10 @@ int ProveBatch::draws_upload() {
           keep(st.cards, in->values);
           keep(st.aux, in->aux);
           keep(st.pub, in->pub);
-          if (derive_aux) {  // the host witness's aux from the host hints
-            st.aux.resize(C.program->n_aux);
-            circuit::hint_eval(*C.program, st.cards.data(), st.pub.data(), st.aux.data());
+          if (derive_aux) {  // the host witness's aux from the host hints (with late hints: once x exists)
+            st.aux.assign(C.program->n_aux, hsc::zero());
+            if (!circuit::has_late_hints(*C.program))
+              circuit::hint_eval(*C.program, st.cards.data(), st.pub.data(), st.aux.data());
           }
         }
       }
@@ -511,7 +513,7 @@ int ProveBatch::pedersen_Vx_witness() {
   uint32_t* h_fail = nullptr;  // a program's failing assert per proof, written in place (ctx_zc_out)
   if (dev_witness && C.program) {
     BPP_TRY(ctx_zc_out(ctx, "wp_fail_h", P * 4, &h_fail));
-    BPP_TRY(witness_program_dev(ctx, C, (uint32_t)P, d_v, d_aux, d_vh + 8 * P, per, d_s, h_fail, d_pub));
+    BPP_TRY(witness_program_dev(ctx, C, (uint32_t)P, d_v, d_aux, d_vh + 8 * P, per, d_s, h_fail, d_pub, derive_aux));
   } else if (dev_witness) {
     if (C.deck)
       BPP_TRY(witness_deck_dev(ctx, C, (uint32_t)P, d_v, d_vh + 8 * P, per, d_s));
@@ -531,6 +533,8 @@ int ProveBatch::pedersen_Vx_witness() {
     S[p]->tr.append_point("V", Vx[p].data());
     if (!dev_witness) {
       ProverState& st = *S[p];
+      if (C.program && derive_aux && circuit::has_late_hints(*C.program))
+        circuit::hint_eval_x(*C.program, st.cards.data(), st.pub.data(), st.x_perm, st.aux.data());
       if (C.program)
         circuit::eval(*C.program, n_p, st.cards.data(), st.aux.data(), st.x_perm, st.aL, st.aR, st.aO, &bad[p],
                       st.pub.data());

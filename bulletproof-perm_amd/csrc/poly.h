@@ -81,7 +81,13 @@ int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uin
 // workspace "wp_wires", which prove_wipe zeroes; no size is refused.
 int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
                         const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail,
-                        const uint32_t* d_pub = nullptr);  // (d_pub [P][n_pub] canonical: the public inputs)
+                        const uint32_t* d_pub = nullptr,  // (d_pub [P][n_pub] canonical: the public inputs)
+                        bool derive_late = false);
+// derive_late (aux derived from the circuit's hints, not a caller's): on a
+// circuit with late hints the k_witness_program*_late kernels run, which
+// evaluate each late hint where its gate is reached and never read its slot of
+// d_aux (d_aux holds the early hints' values; not read at all when every hint
+// is late).  Without it, and on every other circuit, d_aux is read as given.
 // hint_aux_dev (k_hint_aux): the auxiliary values of a circuit with hints
 // (C.program->hints), one lane per (proof, hint), from d_vals [P][m_in] and
 // d_pub [P][n_pub] into d_aux [P][n_aux] (canonical), which witness_program_dev

@@ -975,15 +975,30 @@ int witness_deck_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uin
 // does not wait for on this target.  The array is reached through a plain pointer --
 // neither const nor __restrict__, which would let the compiler keep or hoist a
 // load of a wire over the barrier that publishes it.
+//
+// LATE (the k_witness_program*_late kernels; a circuit with late hints whose
+// aux is derived, host restatement circuit::hint_eval_x): the image holds, at
+// o_late, 3 words per side -- the op word of the side's late hint
+// (circuit::kNoLateHint: none) and its terms [b, e) in the same term tables.
+// The free-side pass skips such a side: its slot of aux is never read.  At its
+// gate's level (which counts the gates the hint reads) the gate's lane forms w
+// with the same term loop, in Montgomery form, applies the op -- INV is
+// sc_inv_mont; BIT, NOT_BIT and IS_ZERO turn w canonical, take the bit or the
+// zero test with k_hint_aux's selects and shifts, and select 0 or one-in-
+// Montgomery-form -- stores the side and forms the product.  As in k_hint_aux,
+// branches (a side has a late hint, its op, its term count) and addresses come
+// from the program alone, never from a value.  Stores, drains and barriers
+// around the wires are those of the kernel without LATE.
 enum { WP_GLOBAL = 0, WP_STAGE = 1, WP_WIDE = 2 };
-template <int MODE>
+template <int MODE, bool LATE = false>
 FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, uint32_t n_p, uint32_t n_aux, uint32_t A,
                                     uint32_t nlev, uint32_t per, const uint32_t* __restrict__ prog,
                                     uint32_t prog_words, uint32_t o_lc, uint32_t o_wire, uint32_t o_lev, uint32_t o_gate,
                                     uint32_t o_var, uint32_t o_coef, const uint32_t* __restrict__ vals,
                                     const uint32_t* __restrict__ aux, const uint32_t* __restrict__ xs,
                                     uint32_t* __restrict__ sc_out, uint32_t* __restrict__ fail, uint32_t n_pub,
-                                    const uint32_t* __restrict__ pubs, uint32_t* wide_wires = nullptr) {
+                                    const uint32_t* __restrict__ pubs, uint32_t* wide_wires = nullptr,
+                                    uint32_t o_late = 0) {
   constexpr bool STAGE = MODE == WP_STAGE;
   uint32_t* bad = lds;                        // 1 + the first failing assert (8 words kept for alignment)
   uint32_t* wires = lds + 8;                  // [3n] Montgomery
@@ -1032,8 +1047,27 @@ FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, ui
     }
     return acc;
   };
+  [[maybe_unused]] const uint32_t* late = pg + o_late;  // LATE: [2n][3] op word, terms [b, e)
+  [[maybe_unused]] auto late_value = [&](uint32_t opw, const sc& w) {  // op(w), Montgomery in and out
+    const uint32_t op = opw & 0xFFu, arg = opw >> 8;
+    if (op == circuit::kHintValue) return w;
+    if (op == circuit::kHintInv) return sc_inv_mont(w);
+    const sc c = sc_from_mont(w);
+    uint32_t word = 0, nz = 0;
+    _Pragma("unroll") for (uint32_t k = 0; k < 8; ++k) {
+      word = k == (arg >> 5) ? c.v[k] : word;  // (arg: the program's, the same for a hint's every proof)
+      nz |= c.v[k];
+    }
+    const uint32_t bit = (word >> (arg & 31u)) & 1u;
+    const uint32_t b = op == circuit::kHintBit ? bit : op == circuit::kHintNotBit ? 1u - bit : (uint32_t)(nz == 0);
+    sc r;
+    _Pragma("unroll") for (uint32_t k = 0; k < 8; ++k) r.v[k] = oneR.v[k] & (0u - b);
+    return r;
+  };
   for (uint32_t u = t; u < 2 * n; u += nt) {  // side u = 2g + s
     const uint32_t a = side_aux[u];
+    if constexpr (LATE)
+      if (late[3 * u] != circuit::kNoLateHint) continue;  // (evaluated at its gate's level)
     const sc v = a == 0xFFFFFFFFu ? terms(sc_zero(), lc_off[u], lc_wire[u])
                                   : sc_to_mont(sc_load(aux + 8 * ((size_t)p * n_aux + a)));
     sc_store(wires + 8 * (3 * (size_t)(u >> 1) + (u & 1u)), v);
@@ -1043,6 +1077,23 @@ FE_INLINE void witness_program_body(uint32_t* lds, uint32_t m_in, uint32_t n, ui
   for (uint32_t lev = 0; lev < nlev; ++lev) {
     for (uint32_t u = lev_off[lev] + t; u < lev_off[lev + 1]; u += nt) {
       const uint32_t g = lev_gate[u];
+      if constexpr (LATE) {
+        // one rolled copy of the side code (the inverse's loop is in it); a side
+        // is finished in its wire slot and the product reads both slots back, so
+        // no side is kept in an indexed array (which the rolled loop would put
+        // in scratch)
+        _Pragma("nounroll") for (uint32_t s = 0; s < 2; ++s) {
+          const uint32_t i = 2 * g + s, wb = lc_wire[i], we = lc_off[i + 1], opw = late[3 * i];
+          uint32_t* slot = wires + 8 * (3 * (size_t)g + s);
+          if (opw != circuit::kNoLateHint)  // (the program's word: the same branch for every proof)
+            sc_store(slot, late_value(opw, terms(sc_zero(), late[3 * i + 1], late[3 * i + 2])));
+          else if (wb < we)
+            sc_store(slot, terms(sc_load(slot), wb, we));
+        }
+        sc_store(wires + 8 * (3 * (size_t)g + 2),
+                 sc_mont(sc_load(wires + 8 * (3 * (size_t)g)), sc_load(wires + 8 * (3 * (size_t)g + 1))));
+        continue;
+      }
       sc side[2];
       _Pragma("unroll") for (uint32_t s = 0; s < 2; ++s) {
         const uint32_t i = 2 * g + s, wb = lc_wire[i], we = lc_off[i + 1];
@@ -1100,15 +1151,31 @@ __global__ void __launch_bounds__(256) k_witness_program_wide(WITNESS_PROGRAM_AR
   witness_program_body<WP_WIDE>(lds, WITNESS_PROGRAM_PASS, wires);
 }
 
+// the same three for a circuit with late hints (LATE above)
+__global__ void __launch_bounds__(256) k_witness_program_late(WITNESS_PROGRAM_ARGS, uint32_t o_late) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  witness_program_body<WP_STAGE, true>(lds, WITNESS_PROGRAM_PASS, nullptr, o_late);
+}
+__global__ void __launch_bounds__(256) k_witness_program_global_late(WITNESS_PROGRAM_ARGS, uint32_t o_late) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  witness_program_body<WP_GLOBAL, true>(lds, WITNESS_PROGRAM_PASS, nullptr, o_late);
+}
+__global__ void __launch_bounds__(256) k_witness_program_wide_late(WITNESS_PROGRAM_ARGS, uint32_t* wires,
+                                                                   uint32_t o_late) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  witness_program_body<WP_WIDE, true>(lds, WITNESS_PROGRAM_PASS, wires, o_late);
+}
+
 int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const uint32_t* d_vals,
                         const uint32_t* d_aux, const uint32_t* d_x, uint32_t per, uint32_t* d_sc, uint32_t* fail,
-                        const uint32_t* d_pub) {
+                        const uint32_t* d_pub, bool derive_late) {
   if (!P) return BPP_OK;
   const circuit::Program& G = *C.program;
   if (G.n_pub && !d_pub) return BPP_ERR_ARG;
   // by size and flag: the wires in global memory (large circuits, or TILED),
   // else in LDS with the program staged beside them while that fits
   const bool wide = circuit::witness_wide(C);
+  const bool late = derive_late && circuit::has_late_hints(G);  // (its own kernels: the hints evaluated at their gates)
   const bool stage = !wide && circuit::witness_program_staged_lds(G) <= perm::kLdsMax;
   const size_t lds = wide    ? circuit::witness_program_wide_lds()
                      : stage ? circuit::witness_program_staged_lds(G)
@@ -1126,14 +1193,24 @@ int witness_program_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t P, const 
   G.m_in, G.n, C.n_p, G.n_aux, G.A, (uint32_t)G.level_off.size() - 1, per, (const uint32_t*)d_prog,                \
       (uint32_t)G.dev.size(), G.dev_lc_off, G.dev_lc_wire, G.dev_level_off, G.dev_level_gate, G.dev_vars, G.dev_coefs, \
       d_vals, d_aux, d_x, d_sc, fail, G.n_pub, d_pub
-    if (wide)
+    if (late && wide)
+      hipLaunchKernelGGL(k_witness_program_wide_late, dim3(P), dim3(nt), lds, ctx->stream, WITNESS_PROGRAM_LAUNCH,
+                         (uint32_t*)d_wires, G.dev_late);
+    else if (late)
+      hipLaunchKernelGGL(stage ? k_witness_program_late : k_witness_program_global_late, dim3(P), dim3(nt), lds,
+                         ctx->stream, WITNESS_PROGRAM_LAUNCH, G.dev_late);
+    else if (wide)
       hipLaunchKernelGGL(k_witness_program_wide, dim3(P), dim3(nt), lds, ctx->stream, WITNESS_PROGRAM_LAUNCH,
                          (uint32_t*)d_wires);
     else
       hipLaunchKernelGGL(stage ? k_witness_program : k_witness_program_global, dim3(P), dim3(nt), lds, ctx->stream,
                          WITNESS_PROGRAM_LAUNCH);
   }
-  return ctx_check_launch(ctx, wide ? "k_witness_program_wide" : stage ? "k_witness_program" : "k_witness_program_global");
+  const char* const plain = wide ? "k_witness_program_wide" : stage ? "k_witness_program" : "k_witness_program_global";
+  const char* const lated = wide    ? "k_witness_program_wide_late"
+                            : stage ? "k_witness_program_late"
+                                    : "k_witness_program_global_late";
+  return ctx_check_launch(ctx, late ? lated : plain);
 }
 
 // k_hint_aux: the auxiliary values of a circuit with hints, in front of

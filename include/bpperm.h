@@ -687,6 +687,52 @@ int bpp_circuit_hint_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t*
 int bpp_debug_circuit_hints(bpp_ctx* ctx, const bpp_circuit* c, size_t count, const uint8_t* v, const uint8_t* pub,
                             uint8_t* aux_out);
 
+/* ------------------------------------------------- circuit hints over wires */
+/* bpp_circuit_create_wire_hinted takes the same bpp_circuit_hints, ops and arg
+ * rule, and the flags of bpp_circuit_create_ex, but a hint's combination ranges
+ * over the variable space of a defined side, with the ids of
+ * bpp_circuit_desc.lc_var: {1, v_j, x, u_i, the wires l_h r_h o_h}.  A hint that
+ * names x or a wire is LATE, every other is EARLY and is the hint above.  A_I
+ * is committed after x_perm and after V_{m_in}, so a free side may depend on x
+ * and on every earlier wire with no change to the statement, the transcript or
+ * a verifier; what a late hint cannot be is supplied by a caller who has no x.
+ *   - a late hint that reads a wire of gate h feeds sides of gates g > h only,
+ *     checked for every side its aux index feeds; an id beyond the last wire
+ *     (2 + m_in + n_pub + 3 n_gates) is refused: BPP_ERR_ARG, as is everything
+ *     bpp_circuit_create_hinted refuses but an id that names x or a wire;
+ *   - a late hint is evaluated once for each side it feeds, from the wires of
+ *     earlier gates, when the witness reaches that gate; one that feeds no side
+ *     is never evaluated;
+ *   - a program without a late hint behaves as under bpp_circuit_create_hinted.
+ * Hints remain no part of the statement: for one description the digest, the
+ * matrices, bpp_circuit_info, the proof bytes and the verifiers are the same
+ * whether it was created plain, hinted or wire-hinted.  A gate's dependency
+ * level counts the gates its sides' late hints read (scheduling only).
+ * Proving: aux == NULL derives every value -- the early ones by k_hint_aux, the
+ * late ones inside the witness kernel (k_witness_program*_late), where they go
+ * straight to the wires and are never stored as aux; aux != NULL is used as
+ * given.  Under BPP_CIRCUIT_HOST_WITNESS=1 the host derives them
+ * (bpp_circuit_hint_eval_x's code) once x exists. */
+int bpp_circuit_create_wire_hinted(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags,
+                                   const bpp_circuit_hints* hints, bpp_circuit** out);
+/* The host reference with x (no GPU): all n_aux values -- early hints as
+ * bpp_circuit_hint_eval gives them, late hints in gate order from the wires so
+ * far (0 for a late hint that feeds no side).  bpp_circuit_eval[_pub] over
+ * aux_out and the same x gives the witness.  x: 32 B canonical.  On a circuit
+ * with a late hint bpp_circuit_hint_eval and bpp_debug_circuit_hints, which have
+ * no x, return BPP_ERR_ARG. */
+int bpp_circuit_hint_eval_x(const bpp_circuit* c, const uint8_t* v, const uint8_t* pub, const uint8_t x[32],
+                            uint8_t* aux_out);
+/* Test hook: ONLY the witness kernels over count proofs -- k_hint_aux where the
+ * circuit has early hints, then the witness kernel a batch of this circuit
+ * launches -- with x supplied by the caller (count x 32 B, canonical; v and pub
+ * as above).  aL, aR, aO: count x n_p x 32 B canonical each; fail[p] = 1 + the
+ * first assert of proof p that does not hold, or 0.  BPP_ERR_ARG on a circuit
+ * with auxiliary values and no hints.  Staged through a recorded span and wiped
+ * before it returns, as bpp_debug_circuit_hints. */
+int bpp_debug_circuit_witness(bpp_ctx* ctx, const bpp_circuit* c, size_t count, const uint8_t* v, const uint8_t* pub,
+                              const uint8_t* x, uint8_t* aL, uint8_t* aR, uint8_t* aO, uint32_t* fail);
+
 /* Mixed batches: proofs of different statements verified in one call with ONE
  * GPU MSM.  A group is `count` proofs of one statement under one label: the
  * two-half shuffle of k cards, the public-deck shuffle of k cards (deck as
