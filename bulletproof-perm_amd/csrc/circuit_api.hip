@@ -5,9 +5,9 @@
 // each proof's public inputs to both.
 #include <string>
 
+#include "circuit_witness.h"
 #include "host/circuit.h"
 #include "perm_internal.h"
-#include "poly.h"
 
 using namespace perm_impl;
 
@@ -72,6 +72,27 @@ int circuit_hint_eval(const bpp_circuit* c, const uint8_t* v, const uint8_t* pub
     for (auto* s : {&vs, &as}) std::fill(s->begin(), s->end(), hsc::zero());
     return BPP_OK;
   });
+}
+
+// The test hooks' inputs on the device as a batch's are: count proofs' v | pub
+// [| x] (x == nullptr: no x rows) in one upload through the batch's own upload
+// workspace and a staging span that prove_wipe zeroes, as draws_upload stages
+// them.  *d_pub: nullptr on a circuit without public inputs.
+int stage_inputs(bpp_ctx* ctx, const circuit::Program& P, size_t count, const uint8_t* v, const uint8_t* pub,
+                 const uint8_t* x, const uint32_t** d_v, const uint32_t** d_pub, const uint32_t** d_x) {
+  const size_t vb = count * 32 * (size_t)P.m_in, ub = count * 32 * (size_t)P.n_pub, xb = x ? count * 32 : 0;
+  void* d_in = nullptr;
+  uint8_t* stage = nullptr;
+  BPP_TRY(ctx_ws(ctx, "pb_rng_in", vb + ub + xb, &d_in));
+  BPP_TRY(ctx_h2d_stage(ctx, vb + ub + xb, &stage));
+  ctx_secret_span(ctx, stage, vb + ub + xb);
+  memcpy(stage, v, vb);
+  if (ub) memcpy(stage + vb, pub, ub);
+  if (xb) memcpy(stage + vb + ub, x, xb);
+  *d_v = (const uint32_t*)d_in;
+  *d_pub = ub ? (const uint32_t*)((const uint8_t*)d_in + vb) : nullptr;
+  if (d_x) *d_x = (const uint32_t*)((const uint8_t*)d_in + vb + ub);
+  return ctx_h2d_staged(ctx, d_in, stage, vb + ub + xb);
 }
 
 int create_hinted(const bpp_circuit_desc* desc, uint32_t n_pub, uint32_t flags, const bpp_circuit_hints* hints,
@@ -152,21 +173,11 @@ int bpp_debug_circuit_hints(bpp_ctx* ctx, const bpp_circuit* c, size_t count, co
     check_canonical(pub, P.n_pub, count, bad);
     if (first_bad(bad) != SIZE_MAX) return BPP_ERR_NONCANONICAL;
     BPP_HIP(hipSetDevice(ctx->device));
-    // v and pub through the batch's own upload workspace and a staging span that
-    // prove_wipe zeroes, as draws_upload stages them
-    const size_t vb = count * 32 * (size_t)P.m_in, ub = count * 32 * (size_t)P.n_pub;
-    void *d_in = nullptr, *d_aux = nullptr;
-    uint8_t* stage = nullptr;
-    BPP_TRY(ctx_ws(ctx, "pb_rng_in", vb + ub, &d_in));
-    BPP_TRY(ctx_h2d_stage(ctx, vb + ub, &stage));
-    ctx_secret_span(ctx, stage, vb + ub);
-    memcpy(stage, v, vb);
-    if (ub) memcpy(stage + vb, pub, ub);
-    int rc = ctx_h2d_staged(ctx, d_in, stage, vb + ub);
+    void* d_aux = nullptr;
+    const uint32_t *d_v = nullptr, *d_pub = nullptr;
+    int rc = stage_inputs(ctx, P, count, v, pub, nullptr, &d_v, &d_pub, nullptr);
     if (rc == BPP_OK) rc = ctx_ws(ctx, "pb_aux_hint", count * 32 * (size_t)P.n_aux, &d_aux);
-    if (rc == BPP_OK)
-      rc = hint_aux_dev(ctx, c->C, (uint32_t)count, (const uint32_t*)d_in,
-                        ub ? (const uint32_t*)((const uint8_t*)d_in + vb) : nullptr, (uint32_t*)d_aux);
+    if (rc == BPP_OK) rc = hint_aux_dev(ctx, c->C, (uint32_t)count, d_v, d_pub, (uint32_t*)d_aux);
     if (rc == BPP_OK) rc = ctx_sync(ctx);
     if (rc == BPP_OK && hipMemcpy(aux_out, d_aux, count * 32 * (size_t)P.n_aux, hipMemcpyDeviceToHost) != hipSuccess)
       rc = BPP_ERR_DEVICE;
@@ -197,20 +208,10 @@ int bpp_debug_circuit_witness(bpp_ctx* ctx, const bpp_circuit* c, size_t count, 
     if (first_bad(bad) != SIZE_MAX) return BPP_ERR_NONCANONICAL;
     BPP_HIP(hipSetDevice(ctx->device));
     const uint32_t n_p = c->C.n_p, per = 3 + 5 * n_p;  // (the prover's A_I / A_O / S scalar rows)
-    const size_t vb = count * 32 * (size_t)P.m_in, ub = count * 32 * (size_t)P.n_pub, xb = count * 32;
-    void *d_in = nullptr, *d_aux = nullptr, *d_s = nullptr;
-    uint8_t* stage = nullptr;
+    void *d_aux = nullptr, *d_s = nullptr;
     uint32_t* h_fail = nullptr;
-    BPP_TRY(ctx_ws(ctx, "pb_rng_in", vb + ub + xb, &d_in));
-    BPP_TRY(ctx_h2d_stage(ctx, vb + ub + xb, &stage));
-    ctx_secret_span(ctx, stage, vb + ub + xb);
-    memcpy(stage, v, vb);
-    if (ub) memcpy(stage + vb, pub, ub);
-    memcpy(stage + vb + ub, x, xb);
-    const uint32_t* d_v = (const uint32_t*)d_in;
-    const uint32_t* d_pub = ub ? (const uint32_t*)((const uint8_t*)d_in + vb) : nullptr;
-    const uint32_t* d_x = (const uint32_t*)((const uint8_t*)d_in + vb + ub);
-    int rc = ctx_h2d_staged(ctx, d_in, stage, vb + ub + xb);
+    const uint32_t *d_v = nullptr, *d_pub = nullptr, *d_x = nullptr;
+    int rc = stage_inputs(ctx, P, count, v, pub, x, &d_v, &d_pub, &d_x);
     if (rc == BPP_OK) rc = ctx_ws(ctx, "mt_s", count * (size_t)per * 32 + 32, &d_s);
     if (rc == BPP_OK) rc = ctx_zc_out(ctx, "wp_fail_h", count * 4, &h_fail);
     if (rc == BPP_OK && P.n_aux) {
@@ -283,9 +284,8 @@ int bpp_circuit_prove_batch_pub(bpp_ctx* ctx, const bpp_gens* G, const bpp_circu
   return bpp_guard(ctx, [&]() -> int {
     if (!c || (!label && llen)) return BPP_ERR_ARG;
     const uint32_t m_in = c->C.nv, n_aux = c->C.program->n_aux;
-    // aux == NULL on a circuit with hints: the values are derived on the GPU (k_hint_aux; late
-    // hints inside the witness kernel)
-    const bool derive = !aux && n_aux && c->C.program->hints;
+    // aux == NULL on a circuit with hints: the values are derived on the GPU
+    const bool derive = circuit::aux_derived(*c->C.program, aux);
     if ((!v || (!aux && n_aux && !derive) || !proofs_out || !V_out) && count) return BPP_ERR_ARG;
     if (!pub && c->C.n_pub && count) return BPP_ERR_ARG;
     // every scalar of the witness is checked before any device work and

@@ -1,6 +1,8 @@
-// Caller-defined circuits -- see circuit.h.  The checker this must agree with
-// is tests/circuit_ref.py (compile_program / eval_program / circuit_digest),
-// with public inputs tests/circuit_pub_ref.py.
+// Caller-defined circuits -- see circuit.h.  The checkers this must agree with
+// are tests/circuit_ref.py (compile_program / eval_program / circuit_digest),
+// with public inputs tests/circuit_pub_ref.py, past the one-workgroup bounds
+// tests/circuit_large_ref.py, the hints tests/circuit_hints_ref.py and the
+// hints over wires and x tests/circuit_wire_hints_ref.py.
 #include "circuit.h"
 
 #include <algorithm>
@@ -30,11 +32,54 @@ void digest(const Desc& d, uint8_t out[32]) {
 
 namespace {
 
-// the flagged variable id of a term for the device images: | kTermOne for the
-// coefficient 1, | kTermNeg for -1 (no multiply)
-uint32_t dev_term(uint32_t var, const Sc& a) {
+// The checks of a caller's term table (nlc combinations: lc_off [nlc + 1], lc_var
+// [T], lc_coef [T][32]), the description's and the hint program's alike, in the
+// order the return codes depend on: lc_off[0] = 0, lc_off monotone, no null
+// table; then per combination head(i) and per term id(i, var), ids strictly
+// increasing, the coefficient below l (ERR_NONCANONICAL; every other refusal
+// ERR_ARG) and nonzero.  head (what combination i hangs on: a side's aux index,
+// a hint's op) and id (the ids it may name) are the caller's and return what is
+// wrong, or "".  coef receives the T coefficients.
+template <class Fail, class Where, class Head, class Id>
+int check_terms(const uint32_t* lc_off, const uint32_t* lc_var, const uint8_t* lc_coef, size_t nlc, std::vector<Sc>& coef,
+                Fail fail, Where where, Head head, Id id) {
+  if (lc_off[0] != 0) return fail(ERR_ARG, "lc_off[0] is not 0");
+  for (size_t i = 0; i < nlc; ++i)
+    if (lc_off[i + 1] < lc_off[i]) return fail(ERR_ARG, "lc_off decreases at " + std::to_string(i + 1));
+  const size_t T = lc_off[nlc];
+  if (T && (!lc_var || !lc_coef)) return fail(ERR_ARG, "null lc_var or lc_coef");
+  coef.resize(T);
+  for (size_t i = 0; i < nlc; ++i) {
+    if (const std::string what = head(i); !what.empty()) return fail(ERR_ARG, where(i) + ": " + what);
+    for (size_t t = lc_off[i]; t < lc_off[i + 1]; ++t) {
+      if (const std::string what = id(i, lc_var[t]); !what.empty()) return fail(ERR_ARG, where(i) + ": " + what);
+      if (t > lc_off[i] && lc_var[t] <= lc_var[t - 1]) return fail(ERR_ARG, where(i) + ": ids not strictly increasing");
+      if (!hsc::from_canonical(coef[t], lc_coef + 32 * t))
+        return fail(ERR_NONCANONICAL, where(i) + ": coefficient not below l");
+      if (hsc::is_zero(coef[t])) return fail(ERR_ARG, where(i) + ": zero coefficient");
+    }
+  }
+  return OK;
+}
+
+// A term table's tail of a device image: the terms' variable ids, flagged |
+// kTermOne for the coefficient 1 and | kTermNeg for -1 (no multiply), zeros to
+// a multiple of 8 words, then the Montgomery coefficients [T][8]; the two word
+// offsets to o_vars and o_coefs.
+void dev_terms(std::vector<uint32_t>& dev, const std::vector<uint32_t>& var, const std::vector<Sc>& coef,
+               uint32_t& o_vars, uint32_t& o_coefs) {
   const Sc one = hsc::one(), neg1 = hsc::neg(hsc::one());
-  return var | (a == one ? kTermOne : a == neg1 ? kTermNeg : 0u);
+  o_vars = (uint32_t)dev.size();
+  for (size_t t = 0; t < var.size(); ++t)
+    dev.push_back(var[t] | (coef[t] == one ? kTermOne : coef[t] == neg1 ? kTermNeg : 0u));
+  dev.resize((dev.size() + 7) & ~(size_t)7, 0);
+  o_coefs = (uint32_t)dev.size();
+  for (const Sc& c : coef) {
+    uint32_t w[8];
+    const Sc cR = hsc::to_mont(c);
+    memcpy(w, cR.v, 32);
+    dev.insert(dev.end(), w, w + 8);
+  }
 }
 
 // Validates the hint program of a circuit with m_in inputs, n_pub public inputs,
@@ -51,39 +96,30 @@ int compile_hints(const HintDesc& h, uint32_t m_in, uint32_t n_pub, uint32_t n, 
     return OK;
   }
   if (!h.op || !h.lc_off) return fail(ERR_ARG, "null op or lc_off");
-  if (h.lc_off[0] != 0) return fail(ERR_ARG, "lc_off[0] is not 0");
-  for (uint32_t t = 0; t < n_aux; ++t)
-    if (h.lc_off[t + 1] < h.lc_off[t]) return fail(ERR_ARG, "lc_off decreases at " + std::to_string(t + 1));
-  const size_t T = h.lc_off[n_aux];
-  if (T && (!h.lc_var || !h.lc_coef)) return fail(ERR_ARG, "null lc_var or lc_coef");
+  const uint32_t x_id = 1 + m_in, wbase = 2 + m_in + n_pub, nvar = wbase + 3 * n;
   auto H = std::make_shared<Hints>();
+  const int rc = check_terms(
+      h.lc_off, h.lc_var, h.lc_coef, n_aux, H->lc_coef, fail, [](size_t t) { return "hint " + std::to_string(t); },
+      [&](size_t t) -> std::string {
+        const uint32_t op = h.op[t] & 0xFFu, arg = h.op[t] >> 8;
+        if (op >= kHintOps) return "unknown op";
+        if (arg && op != kHintBit && op != kHintNotBit) return "an arg on an op that takes none";
+        return arg > kHintMaxBit ? "bit index above 252" : "";
+      },
+      [&](size_t, uint32_t var) -> std::string {
+        if (wire_hints) return var >= nvar ? "variable id beyond the last wire" : "";
+        if (var >= wbase) return "variable id out of range, or a wire";
+        return var == x_id ? "reads x (aux exists before x does)" : "";
+      });
+  if (rc != OK) return rc;
+  const size_t T = h.lc_off[n_aux];
   H->op.assign(h.op, h.op + n_aux);
   H->lc_off.assign(h.lc_off, h.lc_off + n_aux + 1);
   H->lc_var.assign(h.lc_var, h.lc_var + T);
-  H->lc_coef.resize(T);
-  const uint32_t x_id = 1 + m_in, wbase = 2 + m_in + n_pub, nvar = wbase + 3 * n;
-  if (wire_hints) H->late.assign(n_aux, 0);
-  for (uint32_t t = 0; t < n_aux; ++t) {
-    const std::string where = "hint " + std::to_string(t);
-    const uint32_t op = h.op[t] & 0xFFu, arg = h.op[t] >> 8;
-    if (op >= kHintOps) return fail(ERR_ARG, where + ": unknown op");
-    if (arg && op != kHintBit && op != kHintNotBit) return fail(ERR_ARG, where + ": an arg on an op that takes none");
-    if (arg > kHintMaxBit) return fail(ERR_ARG, where + ": bit index above 252");
-    for (size_t e = h.lc_off[t]; e < h.lc_off[t + 1]; ++e) {
-      const uint32_t var = h.lc_var[e];
-      if (wire_hints) {
-        if (var >= nvar) return fail(ERR_ARG, where + ": variable id beyond the last wire");
-        if (var == x_id || var >= wbase) H->late[t] = 1;
-      } else {
-        if (var >= wbase) return fail(ERR_ARG, where + ": variable id out of range, or a wire");
-        if (var == x_id) return fail(ERR_ARG, where + ": reads x (aux exists before x does)");
-      }
-      if (e > h.lc_off[t] && var <= h.lc_var[e - 1]) return fail(ERR_ARG, where + ": ids not strictly increasing");
-      if (!hsc::from_canonical(H->lc_coef[e], h.lc_coef + 32 * e))
-        return fail(ERR_NONCANONICAL, where + ": coefficient not below l");
-      if (hsc::is_zero(H->lc_coef[e])) return fail(ERR_ARG, where + ": zero coefficient");
-    }
-  }
+  H->late.assign(n_aux, 0);  // late: the hint names x or a wire (wire_hints only: refused above without)
+  for (uint32_t t = 0; t < n_aux; ++t)
+    for (size_t e = H->lc_off[t]; e < H->lc_off[t + 1]; ++e)
+      if (H->lc_var[e] == x_id || H->lc_var[e] >= wbase) H->late[t] = 1;
   for (uint8_t l : H->late) H->n_late += l;
   if (!H->n_late) H->late.clear();
   // the lane order: by op, INV first, hints of one op in index order (a late
@@ -96,22 +132,12 @@ int compile_hints(const HintDesc& h, uint32_t m_in, uint32_t n_pub, uint32_t n, 
     return op == kHintInv ? 0u : 1u + op;
   };
   std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rank(a) < rank(b); });
-  std::vector<uint32_t>& dev = H->dev;
   for (uint32_t t : order) {
     const uint32_t rec[4] = {t, is_late(t) ? (uint32_t)kHintValue : H->op[t], is_late(t) ? 0u : H->lc_off[t],
                              is_late(t) ? 0u : H->lc_off[t + 1]};
-    dev.insert(dev.end(), rec, rec + 4);
+    H->dev.insert(H->dev.end(), rec, rec + 4);
   }
-  H->dev_vars = (uint32_t)dev.size();
-  for (size_t e = 0; e < T; ++e) dev.push_back(dev_term(H->lc_var[e], H->lc_coef[e]));
-  dev.resize((dev.size() + 7) & ~(size_t)7, 0);
-  H->dev_coefs = (uint32_t)dev.size();
-  for (size_t e = 0; e < T; ++e) {
-    uint32_t w[8];
-    const Sc cR = hsc::to_mont(H->lc_coef[e]);
-    memcpy(w, cR.v, 32);
-    dev.insert(dev.end(), w, w + 8);
-  }
+  dev_terms(H->dev, H->lc_var, H->lc_coef, H->dev_vars, H->dev_coefs);
   out = H;
   return OK;
 }
@@ -131,70 +157,48 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* h
   if (!d.side_aux || !d.lc_off) return fail(ERR_ARG, "null side_aux or lc_off");
   const uint32_t m_in = d.m_in, n = d.n_gates, A = d.n_asserts;
   const size_t nlc = 2 * (size_t)n + A;
-  if (d.lc_off[0] != 0) return fail(ERR_ARG, "lc_off[0] is not 0");
-  for (size_t i = 0; i < nlc; ++i)
-    if (d.lc_off[i + 1] < d.lc_off[i]) return fail(ERR_ARG, "lc_off decreases at " + std::to_string(i + 1));
-  const size_t T = d.lc_off[nlc];
-  if (T && (!d.lc_var || !d.lc_coef)) return fail(ERR_ARG, "null lc_var or lc_coef");
   const uint32_t wbase = 2 + m_in + d.n_pub, nvar = wbase + 3 * n;  // (the first wire id)
   auto P = std::make_shared<Program>();
   P->m_in = m_in, P->n = n, P->n_aux = d.n_aux, P->A = A, P->n_pub = d.n_pub;
-  P->lc_coef.resize(T);
-  uint32_t defined = 0;
-  std::vector<uint32_t> level(n, 0);
-  for (size_t i = 0; i < nlc; ++i) {
-    const bool side = i < 2 * (size_t)n;
-    const uint32_t g = (uint32_t)(i / 2);
-    const std::string where = side ? "gate " + std::to_string(g) + (i & 1 ? " right" : " left")
-                                   : "assert " + std::to_string(i - 2 * (size_t)n);
-    if (side) {
-      const uint32_t a = d.side_aux[i];
-      if (a != SIDE_LC) {
-        if (a >= d.n_aux) return fail(ERR_ARG, where + ": aux index out of range");
-        if (d.lc_off[i + 1] != d.lc_off[i]) return fail(ERR_ARG, where + ": a free side with a combination");
-      } else {
-        ++defined;
-      }
-    }
-    for (size_t t = d.lc_off[i]; t < d.lc_off[i + 1]; ++t) {
-      const uint32_t var = d.lc_var[t];
-      if (var >= nvar) return fail(ERR_ARG, where + ": variable id out of range");
-      if (t > d.lc_off[i] && var <= d.lc_var[t - 1]) return fail(ERR_ARG, where + ": ids not strictly increasing");
-      if (var >= wbase && side) {
-        const uint32_t h = (var - wbase) / 3;
-        if (h >= g) return fail(ERR_ARG, where + ": reads a wire of gate " + std::to_string(h));
-        level[g] = std::max(level[g], level[h] + 1);
-      }
-      if (!hsc::from_canonical(P->lc_coef[t], d.lc_coef + 32 * t))
-        return fail(ERR_NONCANONICAL, where + ": coefficient not below l");
-      if (hsc::is_zero(P->lc_coef[t])) return fail(ERR_ARG, where + ": zero coefficient");
-    }
-  }
+  const auto is_side = [&](size_t i) { return i < 2 * (size_t)n; };
+  const auto where = [&](size_t i) {
+    return is_side(i) ? "gate " + std::to_string(i / 2) + (i & 1 ? " right" : " left")
+                      : "assert " + std::to_string(i - 2 * (size_t)n);
+  };
+  int rc = check_terms(
+      d.lc_off, d.lc_var, d.lc_coef, nlc, P->lc_coef, fail, where,
+      [&](size_t i) -> std::string {
+        if (!is_side(i) || d.side_aux[i] == SIDE_LC) return "";
+        if (d.side_aux[i] >= d.n_aux) return "aux index out of range";
+        return d.lc_off[i + 1] != d.lc_off[i] ? "a free side with a combination" : "";
+      },
+      [&](size_t i, uint32_t var) -> std::string {  // a side of gate g: the wires of gates h < g only
+        if (var >= nvar) return "variable id out of range";
+        return is_side(i) && var >= wbase + 3 * (uint32_t)(i / 2) ? "reads a wire of gate " + std::to_string((var - wbase) / 3)
+                                                                   : "";
+      });
+  if (rc != OK) return rc;
   if (hints) {
-    const int rc = compile_hints(*hints, m_in, d.n_pub, n, d.n_aux, wire_hints, P->hints, err);
+    rc = compile_hints(*hints, m_in, d.n_pub, n, d.n_aux, wire_hints, P->hints, err);
     if (rc != OK) return rc;
   }
-  if (has_late_hints(*P)) {
-    // a late hint's wires come from gates before every side it feeds, and the
-    // levels count them: again over the gates in order, definitions and late hints
-    const Hints& H = *P->hints;
-    std::fill(level.begin(), level.end(), 0);
-    for (uint32_t g = 0; g < n; ++g)
-      for (uint32_t s = 0; s < 2; ++s) {
-        const size_t i = 2 * (size_t)g + s;
-        const uint32_t a = d.side_aux[i];
-        if (a != SIDE_LC && !H.late[a]) continue;
-        const uint32_t* var = a == SIDE_LC ? d.lc_var : H.lc_var.data();
-        const size_t b = a == SIDE_LC ? d.lc_off[i] : H.lc_off[a], e = a == SIDE_LC ? d.lc_off[i + 1] : H.lc_off[a + 1];
-        for (size_t t = b; t < e; ++t) {
-          if (var[t] < wbase) continue;
-          const uint32_t h = (var[t] - wbase) / 3;
-          if (h >= g)
-            return fail(ERR_ARG, "gate " + std::to_string(g) + (s ? " right" : " left") + ": its late hint " +
-                                     std::to_string(a) + " reads a wire of gate " + std::to_string(h));
-          level[g] = std::max(level[g], level[h] + 1);
-        }
-      }
+  // the gates' levels, the hint program known: a side reads the wires that its
+  // definition names or, fed by a late hint, that the hint names -- of gates
+  // before its own (a definition's ids were held to that above, a hint's are
+  // here, at every side its aux index feeds)
+  const Hints* const late = has_late_hints(*P) ? P->hints.get() : nullptr;
+  std::vector<uint32_t> level(n, 0);
+  for (size_t i = 0; i < 2 * (size_t)n; ++i) {
+    const uint32_t g = (uint32_t)(i / 2), a = d.side_aux[i];
+    const bool def = a == SIDE_LC;
+    if (!def && !(late && late->late[a])) continue;
+    const uint32_t *var = def ? d.lc_var : late->lc_var.data(), *off = def ? d.lc_off + i : late->lc_off.data() + a;
+    for (size_t t = off[0]; t < off[1]; ++t) {
+      if (var[t] < wbase) continue;
+      const uint32_t h = (var[t] - wbase) / 3;
+      if (h >= g) return fail(ERR_ARG, where(i) + ": its late hint reads a wire of gate " + std::to_string(h));
+      level[g] = std::max(level[g], level[h] + 1);
+    }
   }
   C = perm::Circuit();
   C.k = 0;  // (no cards: nothing downstream of the witness reads k)
@@ -202,7 +206,7 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* h
   C.n_p = 4;
   while (C.n_p < n) C.n_p *= 2;
   while ((1u << C.lg) < C.n_p) ++C.lg;
-  C.Q = defined + A + 1;
+  C.Q = (uint32_t)std::count(d.side_aux, d.side_aux + 2 * (size_t)n, SIDE_LC) + A + 1;
   C.m = m_in + 1;
   C.nv = m_in;
   C.n_pub = d.n_pub;
@@ -210,6 +214,7 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* h
   if (!d.flags && !lds_fits(C.Q, C.n_p, n))
     return fail(ERR_LEN, "Q = " + std::to_string(C.Q) + ", n = " + std::to_string(n) +
                              " beyond the one-workgroup kernels' LDS (BPP_CIRCUIT_LARGE lifts this)");
+  const size_t T = d.lc_off[nlc];
   P->side_aux.assign(d.side_aux, d.side_aux + 2 * (size_t)n);
   P->lc_off.assign(d.lc_off, d.lc_off + nlc + 1);
   P->lc_var.assign(d.lc_var, d.lc_var + T);
@@ -269,75 +274,30 @@ int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* h
   dev.insert(dev.end(), P->level_off.begin(), P->level_off.end());
   P->dev_level_gate = (uint32_t)dev.size();
   dev.insert(dev.end(), P->level_gate.begin(), P->level_gate.end());
-  // late hints: a record per side, and their terms behind the description's T
-  std::vector<uint32_t> late_var;
-  std::vector<Sc> late_coef;
-  if (has_late_hints(*P)) {
-    const Hints& H = *P->hints;
+  // the image's term tables: the description's T terms and, with late hints (a
+  // record per side), the hints' terms behind them
+  std::vector<uint32_t> tvar = P->lc_var;
+  std::vector<Sc> tcoef = P->lc_coef;
+  if (late) {
     std::vector<uint32_t> at(d.n_aux, 0xFFFFFFFFu);  // where hint a's terms begin (one copy however many sides it feeds)
     P->dev_late = (uint32_t)dev.size();
     for (size_t i = 0; i < 2 * (size_t)n; ++i) {
       const uint32_t a = P->side_aux[i];
       uint32_t rec[3] = {kNoLateHint, 0, 0};
-      if (a != SIDE_LC && H.late[a]) {
+      if (a != SIDE_LC && late->late[a]) {
         if (at[a] == 0xFFFFFFFFu) {
-          at[a] = (uint32_t)(T + late_var.size());
-          late_var.insert(late_var.end(), H.lc_var.begin() + H.lc_off[a], H.lc_var.begin() + H.lc_off[a + 1]);
-          late_coef.insert(late_coef.end(), H.lc_coef.begin() + H.lc_off[a], H.lc_coef.begin() + H.lc_off[a + 1]);
+          at[a] = (uint32_t)tvar.size();
+          tvar.insert(tvar.end(), late->lc_var.begin() + late->lc_off[a], late->lc_var.begin() + late->lc_off[a + 1]);
+          tcoef.insert(tcoef.end(), late->lc_coef.begin() + late->lc_off[a], late->lc_coef.begin() + late->lc_off[a + 1]);
         }
-        rec[0] = H.op[a], rec[1] = at[a], rec[2] = at[a] + (H.lc_off[a + 1] - H.lc_off[a]);
+        rec[0] = late->op[a], rec[1] = at[a], rec[2] = at[a] + (late->lc_off[a + 1] - late->lc_off[a]);
       }
       dev.insert(dev.end(), rec, rec + 3);
     }
   }
-  P->dev_vars = (uint32_t)dev.size();
-  for (size_t t = 0; t < T; ++t) dev.push_back(dev_term(P->lc_var[t], P->lc_coef[t]));
-  for (size_t t = 0; t < late_var.size(); ++t) dev.push_back(dev_term(late_var[t], late_coef[t]));
-  dev.resize((dev.size() + 7) & ~(size_t)7, 0);
-  P->dev_coefs = (uint32_t)dev.size();
-  for (size_t t = 0; t < T + late_var.size(); ++t) {
-    uint32_t w[8];
-    const Sc cR = hsc::to_mont(t < T ? P->lc_coef[t] : late_coef[t - T]);
-    memcpy(w, cR.v, 32);
-    dev.insert(dev.end(), w, w + 8);
-  }
+  dev_terms(dev, tvar, tcoef, P->dev_vars, P->dev_coefs);
   C.program = P;
   return OK;
-}
-
-void eval(const Program& P, uint32_t n_p, const Sc* v, const Sc* aux, const Sc& x, std::vector<Sc>& aL,
-          std::vector<Sc>& aR, std::vector<Sc>& aO, uint32_t* bad_assert, const Sc* pub) {
-  const uint32_t m_in = P.m_in, n = P.n, wbase = 2 + m_in + P.n_pub;
-  aL.assign(n_p, hsc::zero());
-  aR.assign(n_p, hsc::zero());
-  aO.assign(n_p, hsc::zero());
-  std::vector<Sc>* const Wire[3] = {&aL, &aR, &aO};
-  auto lc = [&](size_t i) {
-    Sc acc = hsc::zero();
-    for (size_t t = P.lc_off[i]; t < P.lc_off[i + 1]; ++t) {
-      const uint32_t var = P.lc_var[t];
-      const Sc val = var == 0           ? hsc::one()
-                     : var <= m_in      ? v[var - 1]
-                     : var == 1 + m_in  ? x
-                     : var < wbase      ? pub[var - 2 - m_in]
-                                        : (*Wire[(var - wbase) % 3])[(var - wbase) / 3];
-      acc = hsc::add(acc, hsc::mul(P.lc_coef[t], val));
-    }
-    return acc;
-  };
-  for (uint32_t g = 0; g < n; ++g) {  // (a definition reads gates h < g only)
-    for (uint32_t s = 0; s < 2; ++s) {
-      const uint32_t a = P.side_aux[2 * g + s];
-      (*Wire[s])[g] = a == SIDE_LC ? lc(2 * (size_t)g + s) : aux[a];
-    }
-    aO[g] = hsc::mul(aL[g], aR[g]);
-  }
-  *bad_assert = 0;
-  for (uint32_t a = 0; a < P.A; ++a)
-    if (!hsc::is_zero(lc(2 * (size_t)n + a))) {
-      *bad_assert = a + 1;
-      break;
-    }
 }
 
 namespace {
@@ -353,28 +313,20 @@ Sc hint_op(uint32_t word, const Sc& w) {
                              : hsc::from_u64(hsc::is_zero(w) ? 1 : 0);
 }
 
-}  // namespace
+// One proof's evaluation, what eval, hint_eval and hint_eval_x are made of: the
+// value of a combination and the walk over the gates.  v [m_in], pub [n_pub]
+// and x are the proof's; wires holds l_h, r_h, o_h at 3h + {0, 1, 2} and is
+// scrubbed when the walk goes.
+struct Walk {
+  const Program& P;
+  const Sc *v, *pub;
+  const Sc& x;
+  std::vector<Sc> wires;
+  ~Walk() { std::fill(wires.begin(), wires.end(), hsc::zero()); }
 
-void hint_eval(const Program& P, const Sc* v, const Sc* pub, Sc* aux) {
-  const Hints& H = *P.hints;
-  for (uint32_t t = 0; t < P.n_aux; ++t) {
-    Sc w = hsc::zero();
-    for (size_t e = H.lc_off[t]; e < H.lc_off[t + 1]; ++e) {
-      const uint32_t var = H.lc_var[e];
-      const Sc val = var == 0 ? hsc::one() : var <= P.m_in ? v[var - 1] : pub[var - 2 - P.m_in];
-      w = hsc::add(w, hsc::mul(H.lc_coef[e], val));
-    }
-    aux[t] = hint_op(H.op[t], w);
-    w = hsc::zero();
-  }
-}
-
-void hint_eval_x(const Program& P, const Sc* v, const Sc* pub, const Sc& x, Sc* aux) {
-  const Hints& H = *P.hints;
-  const uint32_t m_in = P.m_in, n = P.n, wbase = 2 + m_in + P.n_pub;
-  std::vector<Sc> wires(3 * (size_t)n, hsc::zero());  // l_h, r_h, o_h at 3h + {0, 1, 2}
-  auto lc = [&](const std::vector<uint32_t>& off, const std::vector<uint32_t>& vars, const std::vector<Sc>& coef,
-                size_t i) {
+  // combination i of a term table over {1, v_j, x, u_i, wires}
+  Sc lc(const std::vector<uint32_t>& off, const std::vector<uint32_t>& vars, const std::vector<Sc>& coef, size_t i) const {
+    const uint32_t m_in = P.m_in, wbase = 2 + m_in + P.n_pub;
     Sc acc = hsc::zero();
     for (size_t t = off[i]; t < off[i + 1]; ++t) {
       const uint32_t var = vars[t];
@@ -386,20 +338,64 @@ void hint_eval_x(const Program& P, const Sc* v, const Sc* pub, const Sc& x, Sc* 
       acc = hsc::add(acc, hsc::mul(coef[t], val));
     }
     return acc;
-  };
-  auto late = [&](uint32_t t) { return !H.late.empty() && H.late[t]; };
-  for (uint32_t t = 0; t < P.n_aux; ++t)
-    aux[t] = late(t) ? hsc::zero() : hint_op(H.op[t], lc(H.lc_off, H.lc_var, H.lc_coef, t));
-  if (H.n_late)
-    for (uint32_t g = 0; g < n; ++g) {
+  }
+  bool late(uint32_t t) const { return !P.hints->late.empty() && P.hints->late[t]; }
+  Sc hint(uint32_t t) const {
+    const Hints& H = *P.hints;
+    Sc w = lc(H.lc_off, H.lc_var, H.lc_coef, t);
+    const Sc r = hint_op(H.op[t], w);
+    w = hsc::zero();
+    return r;
+  }
+  // the early hints' values; a late hint's slot 0
+  void early(Sc* aux) const {
+    for (uint32_t t = 0; t < P.n_aux; ++t) aux[t] = late(t) ? hsc::zero() : hint(t);
+  }
+  // The gates in order (a definition reads gates h < g only): a defined side
+  // from its combination, a free side from aux.  late_aux (null: aux is
+  // complete): a late hint is evaluated into it first, from the wires so far,
+  // at every side it feeds.
+  void gates(const Sc* aux, Sc* late_aux) {
+    wires.assign(3 * (size_t)P.n, hsc::zero());
+    for (uint32_t g = 0; g < P.n; ++g) {
       for (uint32_t s = 0; s < 2; ++s) {
         const uint32_t a = P.side_aux[2 * g + s];
-        if (a != SIDE_LC && late(a)) aux[a] = hint_op(H.op[a], lc(H.lc_off, H.lc_var, H.lc_coef, a));
+        if (a != SIDE_LC && late_aux && late(a)) late_aux[a] = hint(a);
         wires[3 * (size_t)g + s] = a == SIDE_LC ? lc(P.lc_off, P.lc_var, P.lc_coef, 2 * (size_t)g + s) : aux[a];
       }
       wires[3 * (size_t)g + 2] = hsc::mul(wires[3 * (size_t)g], wires[3 * (size_t)g + 1]);
     }
-  std::fill(wires.begin(), wires.end(), hsc::zero());
+  }
+};
+
+}  // namespace
+
+void eval(const Program& P, uint32_t n_p, const Sc* v, const Sc* aux, const Sc& x, std::vector<Sc>& aL,
+          std::vector<Sc>& aR, std::vector<Sc>& aO, uint32_t* bad_assert, const Sc* pub) {
+  Walk w{P, v, pub, x, {}};
+  w.gates(aux, nullptr);
+  std::vector<Sc>* const Wire[3] = {&aL, &aR, &aO};
+  for (uint32_t s = 0; s < 3; ++s) {
+    Wire[s]->assign(n_p, hsc::zero());
+    for (uint32_t g = 0; g < P.n; ++g) (*Wire[s])[g] = w.wires[3 * (size_t)g + s];
+  }
+  *bad_assert = 0;
+  for (uint32_t a = 0; a < P.A; ++a)
+    if (!hsc::is_zero(w.lc(P.lc_off, P.lc_var, P.lc_coef, 2 * (size_t)P.n + a))) {
+      *bad_assert = a + 1;
+      break;
+    }
+}
+
+void hint_eval(const Program& P, const Sc* v, const Sc* pub, Sc* aux) {
+  const Sc no_x = hsc::zero();  // (an early hint names neither x nor a wire)
+  Walk{P, v, pub, no_x, {}}.early(aux);
+}
+
+void hint_eval_x(const Program& P, const Sc* v, const Sc* pub, const Sc& x, Sc* aux) {
+  Walk w{P, v, pub, x, {}};
+  w.early(aux);
+  if (P.hints->n_late) w.gates(aux, aux);
 }
 
 }  // namespace circuit

@@ -146,6 +146,9 @@ void digest(const Desc& d, uint8_t out[32]);
 int compile(const Desc& d, perm::Circuit& C, std::string& err, const HintDesc* hints = nullptr,
             bool wire_hints = false);
 inline bool has_late_hints(const Program& P) { return P.hints && P.hints->n_late; }
+// A prover given no aux rows (aux == nullptr) on a circuit with hints derives
+// them: k_hint_aux, late hints inside the witness kernel.
+inline bool aux_derived(const Program& P, const void* aux) { return !aux && P.n_aux && P.hints; }
 
 // The hints' host reference: aux [n_aux] from v [m_in] and pub [n_pub]
 // (canonical).  What BPP_CIRCUIT_HOST_WITNESS=1 runs in the prover, and what

@@ -92,7 +92,7 @@ inline void transcript_pub(const Circuit& C, merlin::Transcript& tr, const uint8
 }
 
 // Dynamic LDS of the one-workgroup-per-proof kernels k_poly_coef and
-// k_verify_scalars (poly.hip launches them with exactly these; kPolyLanes =
+// k_verify_scalars (poly.hip and verify_scalars.hip launch them with exactly these; kPolyLanes =
 // POLY_T = POW_LO): z^0..z^Q, two tables of min(n_p, kPolyLanes) powers, and
 // the workgroup-sum scratch of 7 (2) scalars per wave.  kLdsMax: what one
 // workgroup may take.
@@ -115,7 +115,7 @@ constexpr size_t split_tables_lds(uint32_t Q, uint32_t n_p, uint32_t nred) {
          (kPolyLanes / 64) * nred * 32;
 }
 static_assert(split_tables_lds((3u << 16) + 1, 1u << 16, 7) <= kLdsMax, "Q <= 2 kMaxGates + kMaxAsserts + 1 fits");
-// The chain witness kernels (poly.hip chain_prefix_products; k_witness and
+// The chain witness kernels (witness.hip chain_prefix_products; k_witness and
 // k_witness_cards: 2 chains of k, k_witness_deck: 1): the prefix products
 // [chains][k] and two scan buffers [chains][lanes] of 32-byte scalars.  256
 // lanes while that fits; the two-chain kernels then go on at 128, and the
@@ -202,7 +202,7 @@ std::vector<uint32_t> fisher_yates(uint32_t k, Rng& rng);
 // tau[5], scalar j = from_wide(SHAKE256("bpperm-prove-sc" || seed ||
 // le32 j)[0..64]) (draw_scalar; oracle/merlin.py indexed_scalar) -- one
 // sponge block per draw, so the GPU makes every draw in its own thread
-// (poly.h draws_dev).
+// (witness.h draws_dev).
 void draw_prover_randomness(const Circuit& C, const Seed& seed, std::vector<uint32_t>& pi, std::vector<hsc::Sc>& gamma,
                             hsc::Sc& alpha, hsc::Sc& beta, hsc::Sc& rho, std::vector<hsc::Sc>& sL,
                             std::vector<hsc::Sc>& sR, std::vector<hsc::Sc>& taus);
@@ -225,7 +225,7 @@ struct RandomDraws {
 void draw_prover_randomness_x8(const Circuit& C, const Seed seeds[8], RandomDraws* const out[8]);
 // As above, but only the host's share -- pi, alpha, beta, rho and tau: the
 // GPU draws gamma, s_L and s_R (and alpha, beta, rho again, into its scalar
-// arrays; poly.h draws_dev), and out[j]'s vectors for them are left empty.
+// arrays; witness.h draws_dev), and out[j]'s vectors for them are left empty.
 // with_pi = false (a caller-supplied shuffle): no pi stream is read and
 // out[j]->pi is left as it is.
 void draw_prover_host_x8(const Circuit& C, const Seed seeds[8], RandomDraws* const out[8], bool with_pi = true);

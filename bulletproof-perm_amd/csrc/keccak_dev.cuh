@@ -1,6 +1,6 @@
 // Keccak-f[1600] on gfx950, one state per lane in registers (25 x 64-bit
 // lanes): the device Merlin transcript (merlin_dev.hip) and the prover's
-// indexed blinding draws (poly.hip k_draws).  Byte-exact with the host's
+// indexed blinding draws (witness.hip k_draws).  Byte-exact with the host's
 // Keccak (host/keccak.cpp; tests/test_gpu_merlin.py, the prover parity
 // tests).
 #pragma once

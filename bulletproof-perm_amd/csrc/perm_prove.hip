@@ -18,11 +18,13 @@
 #include <thread>
 
 #include "perm_internal.h"
+#include "circuit_witness.h"
 #include "host/circuit.h"
 #include "layout.h"
 #include "merlin_dev.h"
 #include "poly.h"
 #include "verify_dev.h"
+#include "witness.h"
 
 using namespace perm_impl;  // (Proof, ProveInputs, Sc)
 
@@ -299,7 +301,7 @@ struct ProveBatch {
   const uint32_t* d_aux = nullptr;  // a program's auxiliary values [P][n_aux]: uploaded, or derived ("pb_aux_hint")
   // no aux rows on a circuit with hints: derived (k_hint_aux; late hints in the witness kernel), and nothing of
   // them is staged or uploaded
-  const bool derive_aux = C.program && in && !in->aux.p && C.program->n_aux && C.program->hints;
+  const bool derive_aux = C.program && in && circuit::aux_derived(*C.program, in->aux.p);
   const uint32_t* d_pub = nullptr;  // a program's uploaded public inputs [P][n_pub]
   uint32_t *d_l = nullptr, *d_r = nullptr, *d_hf = nullptr;
   MsmPoints pts;

@@ -7,7 +7,6 @@
 
 #include "perm_internal.h"
 #include "layout.h"
-#include "poly.h"
 #include "verify_dev.h"
 
 int decompress_ws(bpp_ctx* ctx, const uint8_t* enc, size_t count, const char* name, uint32_t** d_out);

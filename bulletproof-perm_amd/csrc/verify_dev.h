@@ -1,6 +1,8 @@
-// Batch verification on the device (verify_dev.hip, poly.hip k_verify_scalars).
+// Batch verification on the device (verify_dev.hip, verify_scalars.hip).
 #pragma once
 #include <stdint.h>
+
+#include <vector>
 
 #include "ctx.h"
 #include "host/perm.h"
@@ -87,10 +89,19 @@ int verify_merge_groups_dev(bpp_ctx* ctx, const VerifyGroupTab& tab, uint32_t n_
                             const VerifyGatherTab& gt);
 // k_verify_consts (each proof's weight perm::batch_weight(seed, first + p,
 // r_p) and its constants) + k_verify_scalars + k_verify_merge over device
-// records (poly.hip).  seed: 8 words, may be pinned host memory.  d_pub
+// records (verify_scalars.hip).  seed: 8 words, may be pinned host memory.  d_pub
 // (C.n_pub > 0, k_verify_scalars_pub): [count][n_pub][8] words, canonical.
 int verify_scalars_dev_rec(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const uint32_t* d_rec,
                            const uint32_t* seed, uint64_t first, uint32_t* d_sc, const uint32_t* d_pub = nullptr);
+// The batch verifier's MSM scalars for `count` proofs (k_verify_consts +
+// k_verify_scalars + k_verify_merge): rec = [count][12 + lg] canonical
+// scalars (x_perm, y, z, x, w, r, a, b, t_hat, tau_x, mu, -, u_j..); proof p
+// is weighted by perm::batch_weight(seed, first + p, r_p); d_sc (device)
+// receives the 2 n_p + 2 merged generator scalars then count x (m + 8 + 2 lg)
+// weighted proof-point scalars, every proof's check scaled by
+// (prod u_j)^2 y^(n_p - 1) (above).
+int verify_scalars_dev(bpp_ctx* ctx, const perm::Circuit& C, uint32_t count, const std::vector<uint32_t>& rec,
+                       const uint8_t seed[32], uint64_t first, uint32_t* d_sc);
 // Per-proof verdicts (bpp_perm_verify_batch_each).  Term lists of proofs [p0,
 // p0 + M) for the multi-MSM engine: d_scal / d_idx [M][NG + npt] (generator
 // scalars d_gen[p][NG] on generator slots of a set of gn generators, then the

@@ -219,7 +219,7 @@ __global__ void __launch_bounds__(64) k_verify_reduce(uint32_t count, uint32_t l
 // One lane per proof, after k_verify_reduce: the checks (a zero y or u_j
 // rejects the proof: the verifier's scaling by (prod u_j)^2 y^(n_p - 1) must
 // not vanish) and the record's proof scalars.  No inversions: the checks are
-// scaled instead (poly.hip k_verify_consts).
+// scaled instead (verify_scalars.hip k_verify_consts).
 __global__ void __launch_bounds__(64) k_verify_replay_post(uint32_t count, uint32_t lg,
                                                            const uint32_t* __restrict__ okw,
                                                            const uint32_t* __restrict__ proofs, uint32_t pw,
