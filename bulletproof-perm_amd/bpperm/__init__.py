@@ -24,7 +24,7 @@ from ._lib import BppError, check
 MSM_INFLIGHT = 4  # BPP_MSM_INFLIGHT (include/bpperm.h)
 
 __all__ = ["Context", "PointTable", "BppError", "vartime_multiscalar_mul", "default_context", "VerifyJob",
-           "partials_is_identity", "Circuit", "CircuitProver", "verify_groups"]
+           "partials_is_identity", "Circuit", "CircuitProver", "verify_groups", "Reshuffler"]
 
 
 def _buf(b: bytes):
@@ -804,6 +804,101 @@ class DeckProver:
                                                      _buf(self.label), len(self.label), _buf(pb), _buf(vb), ok)
         if rc != 6:
             check(rc, "bpp_deck_verify_batch_each", self.ctx.h)
+        return [b != 0 for b in ok.raw[:count]]
+
+
+class Reshuffler:
+    """Blind re-shuffle proof (bpp_reshuffle_*): the output cards are a
+    permutation of the input cards, each re-blinded with a multiple of
+    B_blinding, and the prover opens none of them -- the step of a card game in
+    which a second player shuffles a deck that the first one committed.  A card
+    is a 32-byte ristretto255 encoding; 2 <= k <= 342, and gens covers
+    max(4, next_pow2(2k - 2))."""
+
+    def __init__(self, gens: Gens, k: int, label: bytes = b"bp-perm", ctx: "Context | None" = None):
+        self.gens = gens
+        self.ctx = ctx or gens.ctx
+        self.k = k
+        self.label = label
+        self.proof_len = int(self.ctx.lib.bpp_reshuffle_proof_len(k))
+
+    def _cards(self, cards, count: int, what: str) -> bytes:
+        cb = bytes(cards) if isinstance(cards, (bytes, bytearray)) else b"".join(_join(c, 32, what) for c in cards)
+        if len(cb) != 32 * self.k * count:
+            raise ValueError(f"{what}: expected k encodings of 32 bytes per proof")
+        return cb
+
+    def shuffle_batch(self, cards_in, perms, blinds=None, seeds32: bytes | None = None, raw: bool = False):
+        """cards_in[p] = the k input cards of shuffle p; perms[p] = k indices,
+        output slot i holding input perms[p][i]; blinds[p] = the k scalars r_i
+        (None: drawn); seeds32 = 32 bytes per proof (None: the OS CSPRNG).
+        Returns (cards_out, proofs): per shuffle the k output cards joined and
+        the proof (raw=True: the two contiguous buffers).  The batch's secrets
+        are wiped."""
+        count = len(perms)
+        if blinds is not None and len(blinds) != count:
+            raise ValueError("perms and blinds must have one entry per proof")
+        if seeds32 is not None and len(seeds32) != 32 * count:
+            raise ValueError("seeds32 must hold 32 bytes per proof")
+        cb = self._cards(cards_in, count, "cards_in")
+        bb = None
+        if blinds is not None:
+            bb = b"".join(x if isinstance(x, (bytes, bytearray)) else _join(x, 32, "blinds") for x in blinds)
+            if len(bb) != 32 * self.k * count:
+                raise ValueError("blinds: expected k scalars of 32 bytes per proof")
+        flat = [int(i) for p in perms for i in p]
+        if len(flat) != self.k * count:
+            raise ValueError("perms: expected k indices per proof")
+        pm = (C.c_uint32 * max(len(flat), 1))(*flat)
+        out = C.create_string_buffer(max(32 * self.k * count, 1))
+        pf = C.create_string_buffer(max(self.proof_len * count, 1))
+        check(self.ctx.lib.bpp_reshuffle_prove_batch(self.ctx.h, self.gens.h, self.k, count, _buf(cb), pm,
+                                                     _buf(bb) if bb is not None else None,
+                                                     _buf(seeds32) if seeds32 is not None else None,
+                                                     _buf(self.label), len(self.label), out, pf),
+              "bpp_reshuffle_prove_batch", self.ctx.h)
+        oraw, praw = out.raw[:32 * self.k * count], pf.raw[:self.proof_len * count]
+        if raw:
+            return oraw, praw
+        return ([oraw[i * 32 * self.k:(i + 1) * 32 * self.k] for i in range(count)],
+                [praw[i * self.proof_len:(i + 1) * self.proof_len] for i in range(count)])
+
+    def verify(self, cards_in, cards_out, proof: bytes) -> bool:
+        ci, co = self._cards(cards_in, 1, "cards_in"), self._cards(cards_out, 1, "cards_out")
+        rc = self.ctx.lib.bpp_reshuffle_verify(self.ctx.h, self.gens.h, self.k, _buf(self.label), len(self.label),
+                                               _buf(ci), _buf(co), _buf(proof), len(proof))
+        if rc == 6:
+            return False
+        check(rc, "bpp_reshuffle_verify", self.ctx.h)
+        return True
+
+    def _batch(self, cards_in, cards_out, proofs):
+        pb = bytes(proofs) if isinstance(proofs, (bytes, bytearray)) else b"".join(proofs)
+        if self.proof_len == 0 or len(pb) % self.proof_len:
+            raise ValueError("proofs: not a whole number of proofs")
+        count = len(pb) // self.proof_len
+        return self._cards(cards_in, count, "cards_in"), self._cards(cards_out, count, "cards_out"), pb, count
+
+    def verify_batch(self, cards_in, cards_out, proofs) -> bool:
+        """cards_in / cards_out / proofs: sequences with one entry per proof, or
+        the contiguous buffers (shuffle_batch(..., raw=True))."""
+        ci, co, pb, count = self._batch(cards_in, cards_out, proofs)
+        rc = self.ctx.lib.bpp_reshuffle_verify_batch(self.ctx.h, self.gens.h, self.k, count, _buf(self.label),
+                                                     len(self.label), _buf(ci), _buf(co), _buf(pb))
+        if rc == 6:
+            return False
+        check(rc, "bpp_reshuffle_verify_batch", self.ctx.h)
+        return True
+
+    def verify_batch_each(self, cards_in, cards_out, proofs) -> "list[bool]":
+        """One verdict per proof, what verify() returns for it alone
+        (bpp_reshuffle_verify_batch_each).  Inputs as verify_batch."""
+        ci, co, pb, count = self._batch(cards_in, cards_out, proofs)
+        ok = C.create_string_buffer(max(count, 1))
+        rc = self.ctx.lib.bpp_reshuffle_verify_batch_each(self.ctx.h, self.gens.h, self.k, count, _buf(self.label),
+                                                          len(self.label), _buf(ci), _buf(co), _buf(pb), ok)
+        if rc != 6:
+            check(rc, "bpp_reshuffle_verify_batch_each", self.ctx.h)
         return [b != 0 for b in ok.raw[:count]]
 
 

@@ -195,26 +195,31 @@ namespace perm_impl BPP_HIDDEN {
 static const char* const kSecretWs[] = {"pb_rng_in", "pb_gamma", "mt_s",  "pv_v",   "pv_g",    "pv_gx",  "poly_vec",
                                         "poly_hf",   "pf_l",     "pf_r",  "ipa_am", "ipa_bm",  "ipa_am1", "ipa_bm1",
                                         "wp_wires",      // (k_witness_program_wide's wires)
-                                        "pb_aux_hint"};  // (k_hint_aux's derived auxiliary values)
+                                        "pb_aux_hint",   // (k_hint_aux's derived auxiliary values)
+                                        "rs_secret"};    // (the re-shuffle prover's draws, perms, b, d, delta, r Bb)
 static const char* const kSecretHost[] = {"pp_v", "pp_g", "ipa_zc_a", "ipa_zc_b"};  // (ipa_zc_*: bpp_ipa_prove zeroes them itself)
-static_assert(sizeof(kSecretWs) / sizeof(kSecretWs[0]) <= WIPE_MAX, "WipeSpans too small");
 int prove_wipe(bpp_ctx* ctx) {
   WipeSpans w = {};
   uint32_t cnt = 0;
   uint64_t most = 0;
+  // one launch per WIPE_MAX live workspaces (one, unless a context has proved with every prover)
+  auto flush = [&]() -> int {
+    if (!cnt) return BPP_OK;
+    const uint32_t bx = (uint32_t)std::min<uint64_t>(64, (most / 16 + 255) / 256 + 1);
+    hipLaunchKernelGGL(k_wipe_spans, dim3(bx, cnt), dim3(256), 0, ctx->stream, w);
+    cnt = 0;
+    most = 0;
+    return ctx_check_launch(ctx, "k_wipe_spans");
+  };
   for (const char* n : kSecretWs) {
     auto it = ctx->ws.find(n);
     if (it == ctx->ws.end() || !it->second.p || !it->second.bytes) continue;
     w.p[cnt] = (uint8_t*)it->second.p;
     w.n[cnt] = it->second.bytes;
     most = std::max<uint64_t>(most, it->second.bytes);
-    ++cnt;
+    if (++cnt == WIPE_MAX) BPP_TRY(flush());
   }
-  if (cnt) {
-    const uint32_t bx = (uint32_t)std::min<uint64_t>(64, (most / 16 + 255) / 256 + 1);
-    hipLaunchKernelGGL(k_wipe_spans, dim3(bx, cnt), dim3(256), 0, ctx->stream, w);
-    BPP_TRY(ctx_check_launch(ctx, "k_wipe_spans"));
-  }
+  BPP_TRY(flush());
   BPP_TRY(ctx_sync(ctx));
   for (const char* n : kSecretHost) {
     auto it = ctx->host_bufs.find(n);

@@ -448,6 +448,72 @@ int bpp_deck_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size
                                const uint8_t* label, size_t llen, const uint8_t* proofs, const uint8_t* V,
                                uint8_t* ok_out);
 
+/* ------------------------------------------ blind re-shuffle proof (sound) */
+/* The step of a card game in which a player shuffles a deck somebody else
+ * committed: the output cards are a permutation of the input cards, each
+ * re-blinded, and the prover can open none of them.
+ * Statement.  Public: input cards C_0..C_{k-1} and output cards C'_0..C'_{k-1},
+ * any valid ristretto255 encodings.  The prover knows a bijection pi on [0, k)
+ * and scalars r_i with C'_i = C_{pi(i)} + r_i Bb, Bb = B_blinding of g;
+ * perms[i] = pi(i): output slot i holds input perm[i].
+ * Argument (DESIGN.md "Protocol: blind re-shuffle"), T = Transcript(label):
+ *   append_message("dom-sep", "reshuffle v1"), append_u64("k", k), C_j under
+ *   "C", C'_i under "C'";  A_i = pi(i) B + alpha_i Bb under "A", x =
+ *   challenge_scalar("x");  e_j = x^(j+1), b_i = e_pi(i), E_i = b_i B + beta_i Bb
+ *   under "E", y = challenge_scalar("y");  T_i = t_i B + w_i Bb under "Ti", T_S
+ *   = sum_i t_i C'_i - t_R Bb under "T", c = challenge_scalar("c");  z_i = t_i +
+ *   c b_i, om_i = w_i + c beta_i, z_R = t_R + c sum_i b_i r_i;  and a proof of
+ *   the shuffle_of_public(k) circuit (bpp_circuit_*_pub) under the same label
+ *   with v_i = y pi(i) + b_i, blindings y alpha_i + beta_i and public inputs
+ *   u_j = y j + e_j, whose commitments V_0..V_{k-1} are D_i = y A_i + E_i.
+ * The verifier accepts iff z_i B + om_i Bb = T_i + c E_i for every i, sum_i z_i
+ * C'_i - z_R Bb = T_S + c sum_j e_j C_j, and the circuit proof verifies for V =
+ * (D_0..D_{k-1}, V_k) with the D_i it formed itself.
+ * Proof bytes, bpp_reshuffle_proof_len(k) = 32 (5k + 3) + the circuit proof's
+ * (9280 at k = 52; 0 for a k outside [2, 342]):
+ *   A[k] | E[k] | Ti[k] | T_S | z[k] | om[k] | z_R | V_k | circuit proof.
+ *   k           2 <= k <= 342 (the circuit's 2k - 2 gates within the plain bound
+ *               of 682; BPP_ERR_LEN beyond, BPP_ERR_ARG below).  bpp_gens_len(g)
+ *               >= max(4, next_pow2(2k - 2)), BPP_ERR_LEN otherwise.
+ *   cards_in / cards_out   count x k x 32 B.
+ *   perms       count x k u32;  blinds  NULL, or count x k x 32 B: the r_i.
+ * Randomness: seeds32 as bpp_perm_prove_batch_entropy.  Draw j =
+ * from_wide(SHAKE256("bpperm-reshuffle-sc" || seed32 || le32 j)[0..64]) in the
+ * order r[k], alpha[k], beta[k], t[k], w[k], t_R; supplied blinds replace draws
+ * 0..k-1; the circuit prover's seed is SHAKE256("bpperm-reshuffle-inner" ||
+ * seed32)[0..32].
+ * Checks of the prover, before any device work and before any output byte: a
+ * perm that is not a bijection on [0, k) -> BPP_ERR_ARG; a blind >= l ->
+ * BPP_ERR_NONCANONICAL (neither needs ctx or g); then the k / g / null checks.
+ * An input card that does not decode -> BPP_ERR_DECOMPRESS, found on the device
+ * before any secret is staged there and before any output byte.  count == 0: BPP_OK.
+ * The verifiers mirror bpp_perm_verify, _verify_batch and _verify_batch_each
+ * (the ok_out contract and count == 0 included), and refuse a response scalar z,
+ * om or z_R >= l with BPP_ERR_NONCANONICAL before any device work, and a card or
+ * a point A, E, Ti, T_S that does not decode with BPP_ERR_DECOMPRESS, found on
+ * the device before anything else runs; _each instead fails that proof alone
+ * (ok_out[p] = 0, BPP_ERR_VERIFY) and gives every other proof its own verdict.  A batch merges the first two checks
+ * of all proofs into ONE MSM of 4k + 1 points per proof plus B and Bb, under
+ * weights rho_p^1..rho_p^(k+1), rho_p = from_wide(SHAKE256("bpperm-reshuffle-wt"
+ * || seed || le64 p || c_p)[0..64]), seed the verifier's own randomness; the
+ * circuit proofs go through the circuit batch verifier.  _each: when the merged
+ * MSM does not pass, one MSM of 4k + 3 terms per proof; a proof's verdict is
+ * that AND the circuit verifier's.
+ * Secret lifetime: that of bpp_perm_prove_batch_entropy; the perms, every draw,
+ * b, v, the blindings, r_i Bb and t_i C'_i are part of what is zeroed and of what
+ * bpp_debug_secret_residue counts. */
+size_t bpp_reshuffle_proof_len(uint32_t k);
+int bpp_reshuffle_prove_batch(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* cards_in,
+                              const uint32_t* perms, const uint8_t* blinds, const uint8_t* seeds32, const uint8_t* label,
+                              size_t llen, uint8_t* cards_out, uint8_t* proofs_out);
+int bpp_reshuffle_verify(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, const uint8_t* label, size_t llen,
+                         const uint8_t* cards_in, const uint8_t* cards_out, const uint8_t* proof, size_t proof_len);
+int bpp_reshuffle_verify_batch(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* label,
+                               size_t llen, const uint8_t* cards_in, const uint8_t* cards_out, const uint8_t* proofs);
+int bpp_reshuffle_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* label,
+                                    size_t llen, const uint8_t* cards_in, const uint8_t* cards_out,
+                                    const uint8_t* proofs, uint8_t* ok_out);
+
 /* -------------------------------------- caller-defined circuits (sound) */
 /* After the shuffle a game needs predicates over the commitments it produced
  * ("the card I play is one of these 13", "this value is below 2^6", "these two
