@@ -21,7 +21,7 @@ int groups_entry(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_group* groups
     size_t total = 0;
     for (size_t g = 0; g < n; ++g) total += groups[g].count;
     if (each && !ok_out && total) return BPP_ERR_ARG;
-    if (each && total) memset(ok_out, 0, total);
+    ok_clear(ok_out, total);  // (nullptr unless each)
     auto named = [&](size_t g, int rc) {  // (keeps a text the check itself left)
       ctx->err = "group " + std::to_string(g) + (ctx->err.empty() ? "" : ": " + ctx->err);
       return rc;
@@ -73,9 +73,7 @@ int groups_entry(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_group* groups
       vg[g] = {C, a.label, a.label_len, a.count, a.proofs, a.V, a.pub};
     }
     BPP_HIP(hipSetDevice(ctx->device));
-    const int rc = verify_groups(ctx, G, vg, n, each ? ok_out : nullptr);
-    if (each && rc != BPP_OK && rc != BPP_ERR_VERIFY) memset(ok_out, 0, total);
-    return rc;
+    return ok_settle(verify_groups(ctx, G, vg, n, ok_out), ok_out, total);
   });
 }
 

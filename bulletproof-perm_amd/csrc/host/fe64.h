@@ -286,6 +286,15 @@ static inline void encode(uint8_t out[32], const ge& p) {
   fe_to_bytes(out, fe_abs(fe_mul(den_inv, fe_sub(p.Z, y))));
 }
 
+// "the point is the identity": it encodes as 0^32 (what every verifier asks
+// of its MSM's result)
+static inline bool is_identity(const ge& p) {
+  static const uint8_t zero[32] = {0};
+  uint8_t e[32];
+  encode(e, p);
+  return memcmp(e, zero, 32) == 0;
+}
+
 // Encodings of 2*P_i for a batch with ONE field inversion per call
 // (RFC 9496's encode needs an inverse square root per point; for a doubled
 // point it is rational).  With e = 2XY, f = Z^2 + dT^2, g = Y^2 + X^2,

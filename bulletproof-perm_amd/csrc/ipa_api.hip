@@ -411,10 +411,7 @@ static int ipa_verify_api(bpp_ctx* ctx, const bpp_gens* g, IpaTranscript* tr, si
     BPP_TRY(gens_points(ctx, g, &pts));
     BPP_TRY(msm_points_extra(ctx, &pts, d_x, (uint32_t)(2 + 2 * lg), n0, "ipav_x_wt", (double)T));
     BPP_TRY(msm_multi(ctx, d_s, (const uint32_t*)d_i, {0, (uint32_t)T}, pts, res));
-    uint8_t e[32];
-    h25519::encode(e, res[0]);
-    static const uint8_t zero[32] = {0};
-    return memcmp(e, zero, 32) == 0 ? BPP_OK : BPP_ERR_VERIFY;
+    return h25519::is_identity(res[0]) ? BPP_OK : BPP_ERR_VERIFY;
   });
 }
 

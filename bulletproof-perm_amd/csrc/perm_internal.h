@@ -173,6 +173,62 @@ inline int gens_cover(bpp_ctx* ctx, const bpp_gens* G, uint32_t n_p) {
   return BPP_ERR_LEN;
 }
 
+// --- steps every batch verifier takes (perm_verify.hip verify_batch and
+// verify_groups, reshuffle_api.hip), each stated once
+
+using h25519::is_identity;  // "the MSM's result is the identity"
+
+// "the OS gave no randomness" (perm::os_entropy, perm::verify_seed)
+inline int no_entropy(bpp_ctx* ctx) {
+  ctx->err = "getrandom failed";
+  return BPP_ERR_DEVICE;
+}
+// the verifier's own randomness for the batch weights
+inline int verify_seed_or_err(bpp_ctx* ctx, uint8_t seed[32]) {
+  return perm::verify_seed(seed) ? BPP_OK : no_entropy(ctx);
+}
+
+// Proofs per pass of a fallback's per-proof MSMs (TP terms each, c-bit
+// windows): the multi-MSM engine packs T W below 2^32 and keeps M W 2^(c-1)
+// buckets (2^22 terms; 2^24 buckets of P3_BYTES = 2.5 GiB).  May be 0: the
+// caller clamps.
+inline size_t each_pass_proofs(size_t TP, uint32_t c) {
+  const size_t W = (254 + c - 1) / c;
+  return std::min(((size_t)1 << 22) / TP, ((size_t)1 << 24) / (W << (c - 1)));
+}
+
+// "ok_out never keeps a pass of a call that fails": zeroed on entry
+// (ok_clear), and again when the call ends with anything but BPP_OK or
+// BPP_ERR_VERIFY (ok_settle, around the call).  ok_out == nullptr: no verdicts.
+inline void ok_clear(uint8_t* ok_out, size_t n) {
+  if (ok_out && n) memset(ok_out, 0, n);
+}
+inline int ok_settle(int rc, uint8_t* ok_out, size_t n) {
+  if (rc != BPP_OK && rc != BPP_ERR_VERIFY) ok_clear(ok_out, n);
+  return rc;
+}
+
+// The report of a fallback that has filled ok_out [total] after a batch check
+// did not pass: how many proofs failed and the first of them, BPP_ERR_VERIFY.
+// No failing proof (every proof passes alone, yet the weighted sum did not:
+// not reachable for sums of group elements): no pass is reported.
+inline int each_report(bpp_ctx* ctx, uint8_t* ok_out, size_t total) {
+  size_t bad = 0, first = total;
+  for (size_t p = total; p-- > 0;)
+    if (!ok_out[p]) {
+      ++bad;
+      first = p;
+    }
+  if (!bad) {
+    memset(ok_out, 0, total);
+    ctx->err = "the batch check failed but no single proof did";
+    return BPP_ERR_DEVICE;
+  }
+  ctx->err = std::to_string(bad) + " of " + std::to_string(total) + " proofs failed, the first at index " +
+             std::to_string(first);
+  return BPP_ERR_VERIFY;
+}
+
 }  // namespace perm_impl
 
 // A batch verification split into its host replay (begin) and its weighted
@@ -235,13 +291,12 @@ int verify_begin(const perm::Circuit& C, const uint8_t* label, size_t llen, size
 int verify_begin_dev(bpp_ctx* ctx, const perm::Circuit& C, const uint8_t* label, size_t llen, size_t count,
                      const uint8_t* proofs, const uint8_t* V, std::unique_ptr<bpp_verify_job>& job, size_t rfirst = 0,
                      size_t rcount = SIZE_MAX, bool sync = true, bool each = false, const uint8_t* pub = nullptr);
+// ok_out: nullptr (one verdict for the batch), or [count] per-proof verdicts.
 // pub: [count][C.n_pub] canonical scalars (checked by the entry point), the
 // proofs' public inputs; not read when C.n_pub = 0
 int verify_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
-                 size_t count, const uint8_t* proofs, const uint8_t* V, const uint8_t* pub = nullptr);
-int verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
-                      size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out,
-                      const uint8_t* pub = nullptr);
+                 size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out,
+                 const uint8_t* pub = nullptr);
 // One group of a mixed batch (bpp_verify_groups): count proofs of statement C
 // (kept by the caller for the call) under one label, with the arrays
 // verify_batch takes.
@@ -357,9 +412,10 @@ struct VerifyCall {
 // the device; then the verifier on the circuit that build() returns.
 template <class Pre, class Build>
 int verify_entry(const VerifyCall& a, bool stmt_ok, bool len_ok, Pre&& pre, Build&& build) {
-  if (a.each && a.ok_out && a.count) memset(a.ok_out, 0, a.count);
+  uint8_t* const ok_out = a.each ? a.ok_out : nullptr;
+  ok_clear(ok_out, a.count);
   bpp_ctx* const ctx = a.ctx;  // (BPP_HIP names it)
-  return bpp_guard(ctx, [&]() -> int {
+  const int rc = bpp_guard(ctx, [&]() -> int {
     if (!ctx || !a.G || ((!a.proofs || !a.V || (a.each && !a.ok_out)) && a.count) || (!a.label && a.llen) || !stmt_ok)
       return BPP_ERR_ARG;
     BPP_TRY(pre());
@@ -370,11 +426,9 @@ int verify_entry(const VerifyCall& a, bool stmt_ok, bool len_ok, Pre&& pre, Buil
     // before sleeping measured within noise, profiles/r06_sync_spin_ab.txt)
     BPP_HIP(hipSetDevice(ctx->device));
     const perm::Circuit& C = build();
-    if (!a.each) return verify_batch(a.ctx, a.G, C, a.label, a.llen, a.count, a.proofs, a.V, a.pub);
-    const int rc = verify_batch_each(a.ctx, a.G, C, a.label, a.llen, a.count, a.proofs, a.V, a.ok_out, a.pub);
-    if (rc != BPP_OK && rc != BPP_ERR_VERIFY) memset(a.ok_out, 0, a.count);
-    return rc;
+    return verify_batch(a.ctx, a.G, C, a.label, a.llen, a.count, a.proofs, a.V, ok_out, a.pub);
   });
+  return ok_settle(rc, ok_out, a.count);
 }
 inline int no_refusal() { return BPP_OK; }
 

@@ -844,10 +844,7 @@ int prove_batch_entropy(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C,
   std::vector<uint8_t> ent;
   if (!seeds32 && count) {
     ent.resize(32 * count);
-    if (!perm::os_entropy(ent.data(), ent.size())) {
-      ctx->err = "getrandom failed";
-      return BPP_ERR_DEVICE;
-    }
+    if (!perm::os_entropy(ent.data(), ent.size())) return no_entropy(ctx);
     seeds32 = ent.data();
   }
   std::vector<perm::Seed> sd(count);

@@ -1,8 +1,24 @@
-// Permutation proof, verifier: host replay and expansion, device jobs, slices
-// of a sharded batch.  Restates ACProof::ArithmeticCircuitProof::verify
+// Permutation proof, verifier.  Restates ACProof::ArithmeticCircuitProof::verify
 // (bp-perm/src/circuit_lib.rs:478-585) in sound mode as ONE GPU MSM (t-check
 // weighted by a verifier challenge + the IPA check, generator scalars
 // merged).  Transcript order matches oracle/bulletproofs.py ac_verify.
+//
+// In file order:
+//   host jobs      verify_replay, verify_expand, verify_begin,
+//                  verify_terms_weighted, verify_partial
+//   the ONE MSM    verify_msm: the term layout [2 n_p + 2 generators | proof
+//                  points] and its index list, for every path below
+//   device jobs    verify_begin_dev (upload, replay, decompression), the slices
+//                  of a sharded batch (verify_slice_*_dev,
+//                  verify_partial_sharded_dev), job_queue_scalars (a job's
+//                  scalars and its decode word), verify_partial_dev
+//   fallback       verify_each_dev: each proof's own MSM over what a job left
+//   batch drivers  verify_batch (one statement; ok_out names the failing
+//                  proofs) and verify_groups (a mixed batch): seed, job(s),
+//                  the MSM, is_identity, verify_each_dev, each_report
+// The steps the drivers share with reshuffle_api.hip (verify_seed_or_err,
+// is_identity, each_pass_proofs, each_report, ok_clear / ok_settle) are in
+// perm_internal.h.
 #include <string>
 
 #include "perm_internal.h"
@@ -284,14 +300,14 @@ int verify_terms_weighted(const bpp_verify_job& J, const uint8_t seed[32], size_
 
 // The batch's ONE MSM over windows [wb, we) of its c-bit signed digits (c =
 // msm_choose_c(terms)) -> raw partial point: scalars d_sv (2 n_p + 2 merged
-// generator scalars, then count x npt proof-point scalars), proof points d_x.
-static int verify_msm(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, size_t count, const uint32_t* d_sv,
-                      const uint32_t* d_x, uint32_t wb, uint32_t we, h25519::ge* out) {
-  const uint32_t n_p = C.n_p;
-  const size_t NG = 2 * (size_t)n_p + 2, T = NG + count * vpts_n(C);
+// generator scalars, then one per proof point), the npts proof points d_x.
+static int verify_msm(bpp_ctx* ctx, const bpp_gens* G, uint32_t n_p, size_t npts, const uint32_t* d_sv,
+                      const uint32_t* d_x, uint32_t wb, uint32_t we, h25519::ge* out, const char* idx_ws_name) {
+  const size_t NG = 2 * (size_t)n_p + 2, T = NG + npts;
   // term t reads generator t of the resident table (G[0..n_p), H[0..n_p),
-  // B, Bb) or proof point t - NG; the index list is needed only when the
-  // generator set is longer than the padded circuit
+  // B, Bb) or proof point t - NG; the index list (workspace idx_ws_name, its
+  // upload cached by content) is needed only when the generator set is longer
+  // than the padded circuit
   const uint32_t n0 = (uint32_t)(2 * G->n + 2);
   uint32_t* d_idx = nullptr;
   if (G->n != n_p) {
@@ -304,8 +320,8 @@ static int verify_msm(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, s
     idx[2 * n_p + 1] = G->bbidx();
     for (size_t j = NG; j < T; ++j) idx[j] = n0 + (uint32_t)(j - NG);
     void* d = nullptr;
-    BPP_TRY(ctx_ws(ctx, "pv_idx", idx.size() * 4 + 4, &d));
-    BPP_TRY(ctx_h2d_const(ctx, "pv_idx", d, idx.data(), idx.size() * 4));
+    BPP_TRY(ctx_ws(ctx, idx_ws_name, idx.size() * 4 + 4, &d));
+    BPP_TRY(ctx_h2d_const(ctx, idx_ws_name, d, idx.data(), idx.size() * 4));
     d_idx = (uint32_t*)d;
   }
   const uint32_t c = msm_choose_c((double)T);
@@ -354,7 +370,7 @@ int verify_partial(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, con
   int rc = decompress_ws(ctx, enc.data(), enc.size() / 32, "pv_x", &d_x);
   if (rc == BPP_ERR_DECOMPRESS) return BPP_ERR_VERIFY;
   BPP_TRY(rc);
-  return verify_msm(ctx, G, J.C, count, (const uint32_t*)d_sv, d_x, wb, we, out);
+  return verify_msm(ctx, G, n_p, count * npt, (const uint32_t*)d_sv, d_x, wb, we, out, "pv_idx");
 }
 
 // pass 1 on the device (bpp_perm_verify_begin_dev): upload the proofs and V,
@@ -597,23 +613,25 @@ int verify_partial_sharded_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify
   // the slices' proof-point scalars (and, when padded, points) in proof order
   BPP_TRY(gather_blocks_dev(ctx, d_blocks, stride, NG * 32, npt * 32, counts, nslices, (uint8_t*)d_sv + NG * 32));
   if (!tight) BPP_TRY(gather_blocks_dev(ctx, d_pblocks, pstride, 0, npt * prec, counts, nslices, (uint8_t*)d_x));
-  BPP_TRY(verify_msm(ctx, G, J.C, total, (const uint32_t*)d_sv, (const uint32_t*)d_x, wb, we, out));
+  BPP_TRY(verify_msm(ctx, G, J.C.n_p, total * npt, (const uint32_t*)d_sv, (const uint32_t*)d_x, wb, we, out, "pv_idx"));
   return ctx_sync(ctx);
 }
 
-// pass 2 of a device job: each proof's weight perm::batch_weight(seed,
-// first + p, r_p) and constants (k_verify_consts), the weighted scalars
-// (k_verify_scalars) and the MSM over windows [wb, we); BPP_ERR_VERIFY if a
-// proof point did not decode or (an asynchronous begin) the replay rejected a
-// proof.
-int verify_partial_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, const uint8_t seed[32],
-                       size_t first, uint32_t wb, uint32_t we, h25519::ge* out) {
-  BPP_TRY(job_is_current(ctx, J));
-  if (J.rcount != J.count) {
-    ctx->err = "a partially replayed job has no whole-batch partial";
-    return BPP_ERR_ARG;
-  }
-  BPP_TRY(gens_cover(ctx, G, J.C.n_p));
+// What a device job's MSM reads, once job_queue_scalars has queued it: the
+// job's scalars in "pv_s" ([2 n_p + 2 merged | count x npt]; each proof's own
+// generator rows stay in "vs_gen"), its decompressed points in "vj_x", and the
+// decompression's verdict word in pinned memory.
+struct JobTerms {
+  const uint32_t *d_sv, *d_x;
+  const uint64_t* h_dbad;  // valid once ctx's stream has been synchronised
+};
+
+// Queue a device job's scalars on ctx's stream, behind its replay: each
+// proof's weight perm::batch_weight(seed, first + p, r_p) and constants
+// (k_verify_consts) and the weighted scalars (k_verify_scalars); then, behind
+// the decompression (vj_ev_dec), the copy of its verdict word.  No host wait.
+static int job_queue_scalars(bpp_ctx* ctx, const bpp_verify_job& J, const uint8_t seed[32], size_t first,
+                             JobTerms& q) {
   const size_t count = J.count, T = 2 * (size_t)J.C.n_p + 2 + count * J.npt;
   void *d_rec = nullptr, *d_x = nullptr, *d_sv = nullptr, *d_dbad = nullptr;
   BPP_TRY(ctx_ws(ctx, "vj_rec", (count + 1) * vrec_n(J.C) * 32, &d_rec));
@@ -627,35 +645,31 @@ int verify_partial_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J,
     BPP_TRY(verify_scalars_dev_rec(ctx, J.C, (uint32_t)count, (const uint32_t*)d_rec, h_seed, first,
                                    (uint32_t*)d_sv, J.d_pub));
   }
-  uint64_t* h_dbad = nullptr;  // the decompression's verdict, copied behind the MSM
+  uint64_t* h_dbad = nullptr;
   BPP_TRY(ctx_zc_out(ctx, "vj_dbad_h", 8, (uint32_t**)&h_dbad));
   BPP_HIP(hipStreamWaitEvent(ctx->stream, ctx->vj_ev_dec, 0));
   BPP_HIP(hipMemcpyAsync(h_dbad, d_dbad, 8, hipMemcpyDeviceToHost, ctx->stream));
-  BPP_TRY(verify_msm(ctx, G, J.C, count, (const uint32_t*)d_sv, (const uint32_t*)d_x, wb, we, out));
-  BPP_TRY(ctx_sync_latency(ctx));  // (msm_single_dev has synchronised; this keeps h_dbad's contract)
-  BPP_TRY(async_replay_verdict(ctx, J));
-  return decode_verdict(ctx, *h_dbad);
+  q = {(const uint32_t*)d_sv, (const uint32_t*)d_x, h_dbad};
+  return BPP_OK;
 }
 
-// Verify `count` proofs with ONE MSM: generator scalars summed across proofs
-// with per-proof weights derived from every proof's r challenge; the
-// transcripts are replayed on the device.
-int verify_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
-                 size_t count, const uint8_t* proofs, const uint8_t* V, const uint8_t* pub) {
-  uint8_t seed[32];  // the verifier's own randomness for the batch weights
-  if (!perm::verify_seed(seed)) {
-    ctx->err = "getrandom failed";
-    return BPP_ERR_DEVICE;
+// pass 2 of a device job: its scalars (job_queue_scalars) and the MSM over
+// windows [wb, we); BPP_ERR_VERIFY if a proof point did not decode or (an
+// asynchronous begin) the replay rejected a proof.
+int verify_partial_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job& J, const uint8_t seed[32],
+                       size_t first, uint32_t wb, uint32_t we, h25519::ge* out) {
+  BPP_TRY(job_is_current(ctx, J));
+  if (J.rcount != J.count) {
+    ctx->err = "a partially replayed job has no whole-batch partial";
+    return BPP_ERR_ARG;
   }
-  std::unique_ptr<bpp_verify_job> job;
-  BPP_TRY(verify_begin_dev(ctx, C, label, llen, count, proofs, V, job, 0, SIZE_MAX, false, false, pub));
-  const uint32_t c = msm_choose_c((double)verify_terms(*job));
-  h25519::ge res;
-  BPP_TRY(verify_partial_dev(ctx, G, *job, seed, 0, 0, (254 + c - 1) / c, &res));
-  uint8_t e[32];
-  h25519::encode(e, res);
-  static const uint8_t zero[32] = {0};
-  return memcmp(e, zero, 32) == 0 ? BPP_OK : BPP_ERR_VERIFY;
+  BPP_TRY(gens_cover(ctx, G, J.C.n_p));
+  JobTerms q;
+  BPP_TRY(job_queue_scalars(ctx, J, seed, first, q));
+  BPP_TRY(verify_msm(ctx, G, J.C.n_p, J.count * J.npt, q.d_sv, q.d_x, wb, we, out, "pv_idx"));
+  BPP_TRY(ctx_sync_latency(ctx));  // (msm_single_dev has synchronised; this keeps h_dbad's contract)
+  BPP_TRY(async_replay_verdict(ctx, J));
+  return decode_verdict(ctx, *q.h_dbad);
 }
 
 // Per-proof verdicts of a device job whose batch check (verify_partial_dev)
@@ -672,10 +686,8 @@ static int verify_each_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job
   const uint32_t n_p = J.C.n_p, n0 = (uint32_t)(2 * G->n + 2);
   const size_t count = J.count, npt = J.npt, NG = 2 * (size_t)n_p + 2, TP = NG + npt;
   if (n0 + count * npt >= 0x80000000ull) return BPP_ERR_LEN;  // (an engine entry is index | sign << 31)
-  const uint32_t c = msm_choose_c((double)TP), W = (254 + c - 1) / c;
-  // proofs per pass: the engine packs T W below 2^32 and keeps M W 2^(c-1)
-  // buckets (2^22 terms; 2^24 buckets of P3_BYTES = 2.5 GiB)
-  size_t per = std::min(((size_t)1 << 22) / TP, ((size_t)1 << 24) / ((size_t)W << (c - 1)));
+  const uint32_t c = msm_choose_c((double)TP);
+  size_t per = each_pass_proofs(TP, c);
   if (const char* e = getenv("BPP_VERIFY_EACH_PROOFS"))  // (read per call, as BPP_MSM_FB)
     per = std::min<size_t>(strtoull(e, nullptr, 10), ((size_t)1 << 24) / TP);
   per = std::min(std::max<size_t>(per, 1), count);
@@ -711,50 +723,32 @@ static int verify_each_dev(bpp_ctx* ctx, const bpp_gens* G, const bpp_verify_job
   return BPP_OK;
 }
 
-// verify_batch that names the failing proofs: the same job and the same ONE
-// merged MSM; only when that does not pass, each proof's own MSM
-// (verify_each_dev).  ok_out [count]: 1 = proof p verifies alone.
-int verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
-                      size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out, const uint8_t* pub) {
+// Verify `count` proofs with ONE MSM: generator scalars summed across proofs
+// with per-proof weights derived from every proof's r challenge; the
+// transcripts are replayed on the device.  ok_out (nullptr: one verdict for the
+// batch) names the failing proofs, [count], 1 = proof p verifies alone: the same
+// job and the same ONE merged MSM, all ones when it passes; only when it does
+// not, each proof's own MSM (verify_each_dev) and each_report.
+int verify_batch(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, const uint8_t* label, size_t llen,
+                 size_t count, const uint8_t* proofs, const uint8_t* V, uint8_t* ok_out, const uint8_t* pub) {
+  const bool each = ok_out != nullptr;
   uint8_t seed[32];
-  if (!perm::verify_seed(seed)) {
-    ctx->err = "getrandom failed";
-    return BPP_ERR_DEVICE;
-  }
+  BPP_TRY(verify_seed_or_err(ctx, seed));
   std::unique_ptr<bpp_verify_job> job;
-  BPP_TRY(verify_begin_dev(ctx, C, label, llen, count, proofs, V, job, 0, SIZE_MAX, false, true, pub));
+  BPP_TRY(verify_begin_dev(ctx, C, label, llen, count, proofs, V, job, 0, SIZE_MAX, false, each, pub));
   const uint32_t c = msm_choose_c((double)verify_terms(*job));
   h25519::ge res;
   // (BPP_ERR_VERIFY: a replay verdict or an undecodable point, found after
   // the MSM and its synchronisation, with the job's device state complete)
   const int rc = verify_partial_dev(ctx, G, *job, seed, 0, 0, (254 + c - 1) / c, &res);
-  if (rc != BPP_OK && rc != BPP_ERR_VERIFY) return rc;
-  if (rc == BPP_OK) {
-    uint8_t e[32];
-    h25519::encode(e, res);
-    static const uint8_t zero[32] = {0};
-    if (memcmp(e, zero, 32) == 0) {
-      memset(ok_out, 1, count);
-      return BPP_OK;
-    }
+  if (rc != BPP_OK && !(each && rc == BPP_ERR_VERIFY)) return rc;
+  if (rc == BPP_OK && is_identity(res)) {
+    if (each) memset(ok_out, 1, count);
+    return BPP_OK;
   }
+  if (!each) return BPP_ERR_VERIFY;
   BPP_TRY(verify_each_dev(ctx, G, *job, ok_out));
-  size_t bad = 0, first = count;
-  for (size_t p = count; p-- > 0;)
-    if (!ok_out[p]) {
-      ++bad;
-      first = p;
-    }
-  if (!bad) {
-    // every proof passes alone, yet the weighted sum did not: not reachable
-    // for sums of group elements; no pass is reported
-    memset(ok_out, 0, count);
-    ctx->err = "the batch check failed but no single proof did";
-    return BPP_ERR_DEVICE;
-  }
-  ctx->err = std::to_string(bad) + " of " + std::to_string(count) + " proofs failed, the first at index " +
-             std::to_string(first);
-  return BPP_ERR_VERIFY;
+  return each_report(ctx, ok_out, count);
 }
 
 // A mixed batch (bpp_verify_groups, _each with ok_out): n <= VG_MAX groups, each
@@ -768,7 +762,7 @@ int verify_batch_each(bpp_ctx* ctx, const bpp_gens* G, const perm::Circuit& C, c
 // behind it (k_verify_merge_groups, k_verify_gather_groups), and runs the MSM.
 // Nothing waits on the host before the MSM's own synchronisation; the replay
 // and decode verdicts of every group are read after it.  ok_out: as
-// verify_batch_each -- all ones when the batch passes, else each group's
+// verify_batch's -- all ones when the batch passes, else each group's
 // verify_each_dev over what its job left on its context.
 int verify_groups(bpp_ctx* ctx, const bpp_gens* G, const VerifyGroup* groups, size_t n, uint8_t* ok_out) {
   if (n > VG_MAX) return BPP_ERR_LEN;
@@ -789,10 +783,7 @@ int verify_groups(bpp_ctx* ctx, const bpp_gens* G, const VerifyGroup* groups, si
   const size_t NG = 2 * (size_t)n_max + 2, T = NG + pts, prec = (size_t)MSM_NIELS_WORDS * 4;
   if (total > (1u << 26) || n0 + pts >= 0x80000000ull) return BPP_ERR_LEN;  // (an engine entry is index | sign << 31)
   uint8_t seed[32];
-  if (!perm::verify_seed(seed)) {
-    ctx->err = "getrandom failed";
-    return BPP_ERR_DEVICE;
-  }
+  BPP_TRY(verify_seed_or_err(ctx, seed));
   struct Run {
     bpp_ctx* gctx = nullptr;
     std::unique_ptr<bpp_verify_job> job;
@@ -838,32 +829,17 @@ int verify_groups(bpp_ctx* ctx, const bpp_gens* G, const VerifyGroup* groups, si
     if (int rc = verify_begin_dev(gc, C, grp.label, grp.llen, grp.count, grp.proofs, grp.V, R.job, 0, SIZE_MAX, false,
                                   each, grp.pub))
       return fail(gc, rc);
-    // its scalars, the layout verify_partial_dev leaves: "pv_s" = [2 n_p + 2
-    // merged | count x npt], "vs_gen" = each proof's own generator rows
-    const size_t NGg = 2 * (size_t)C.n_p + 2, npt = R.job->npt, gpts = grp.count * npt;
+    // its scalars, as verify_partial_dev queues them; then the group's event
+    // and where the merge finds the group's blocks
+    const size_t NGg = 2 * (size_t)C.n_p + 2, gpts = grp.count * R.job->npt;
     auto queue = [&]() -> int {
       bpp_ctx* ctx = gc;  // (BPP_HIP names it)
-      void *d_rec = nullptr, *g_x = nullptr, *g_sv = nullptr, *d_dbad = nullptr;
-      BPP_TRY(ctx_ws(ctx, "vj_rec", (grp.count + 1) * vrec_n(C) * 32, &d_rec));
-      BPP_TRY(ctx_ws(ctx, "vj_x", gpts * prec, &g_x));
-      BPP_TRY(ctx_ws(ctx, "vj_dbad", 8, &d_dbad));
-      BPP_TRY(ctx_ws(ctx, "pv_s", (NGg + gpts) * 32 + 32, &g_sv));
-      {
-        HostScope hs(ctx, "verify_terms");
-        uint32_t* h_seed = nullptr;
-        BPP_TRY(ctx_zc_in(ctx, "vj_seed", seed, 32, &h_seed));
-        BPP_TRY(verify_scalars_dev_rec(ctx, C, (uint32_t)grp.count, (const uint32_t*)d_rec, h_seed, first,
-                                       (uint32_t*)g_sv, R.job->d_pub));
-      }
-      // behind the decompression: its verdict word, then the group's event
-      uint64_t* h_dbad = nullptr;
-      BPP_TRY(ctx_zc_out(ctx, "vj_dbad_h", 8, (uint32_t**)&h_dbad));
-      R.h_dbad = h_dbad;
-      BPP_HIP(hipStreamWaitEvent(ctx->stream, ctx->vj_ev_dec, 0));
-      BPP_HIP(hipMemcpyAsync(h_dbad, d_dbad, 8, hipMemcpyDeviceToHost, ctx->stream));
+      JobTerms q;
+      BPP_TRY(job_queue_scalars(ctx, *R.job, seed, first, q));
+      R.h_dbad = q.h_dbad;
       if (!ctx->vg_ev) BPP_HIP(hipEventCreateWithFlags(&ctx->vg_ev, hipEventDisableTiming));
       BPP_HIP(hipEventRecord(ctx->vg_ev, ctx->stream));
-      tab.g[tab.n].blk = (const uint32_t*)g_sv;
+      tab.g[tab.n].blk = q.d_sv;
       tab.g[tab.n].n_p = C.n_p;
       ++tab.n;
       auto seg = [&](const void* src, void* dst, size_t bytes) {
@@ -872,8 +848,8 @@ int verify_groups(bpp_ctx* ctx, const bpp_gens* G, const VerifyGroup* groups, si
         gt.pre[gt.n + 1] = gt.pre[gt.n] + bytes / 16;
         ++gt.n;
       };
-      seg((const uint8_t*)g_sv + NGg * 32, (uint8_t*)d_sv + (NG + pt0) * 32, gpts * 32);
-      seg(g_x, (uint8_t*)d_x + pt0 * prec, gpts * prec);
+      seg((const uint8_t*)q.d_sv + NGg * 32, (uint8_t*)d_sv + (NG + pt0) * 32, gpts * 32);
+      seg(q.d_x, (uint8_t*)d_x + pt0 * prec, gpts * prec);
       return BPP_OK;
     };
     if (int rc = queue()) return fail(gc, rc);
@@ -887,26 +863,9 @@ int verify_groups(bpp_ctx* ctx, const bpp_gens* G, const VerifyGroup* groups, si
   h25519::ge res;
   auto merged = [&]() -> int {
     BPP_TRY(verify_merge_groups_dev(ctx, tab, n_max, (uint32_t*)d_sv, gt));
-    // term t reads generator t of the resident set or proof point t - NG (the
-    // rule of verify_msm: no list when the set is exactly as long)
-    uint32_t* d_idx = nullptr;
-    if (G->n != n_max) {
-      std::vector<uint32_t> idx(T);
-      for (uint32_t i = 0; i < n_max; ++i) {
-        idx[i] = G->gidx(i);
-        idx[n_max + i] = G->hidx(i);
-      }
-      idx[2 * n_max] = G->bidx();
-      idx[2 * n_max + 1] = G->bbidx();
-      for (size_t j = NG; j < T; ++j) idx[j] = n0 + (uint32_t)(j - NG);
-      void* d = nullptr;
-      BPP_TRY(ctx_ws(ctx, "vg_idx", idx.size() * 4 + 4, &d));
-      BPP_TRY(ctx_h2d_const(ctx, "vg_idx", d, idx.data(), idx.size() * 4));
-      d_idx = (uint32_t*)d;
-    }
-    const uint32_t c = msm_choose_c((double)T);
-    return msm_single_dev(ctx, (const uint32_t*)d_sv, d_idx, G->d_tbl, T, c, 0, (254 + c - 1) / c, &res,
-                          (const uint32_t*)d_x, n0);
+    const uint32_t c = msm_choose_c((double)T);  // (every window)
+    return verify_msm(ctx, G, n_max, pts, (const uint32_t*)d_sv, (const uint32_t*)d_x, 0, (254 + c - 1) / c, &res,
+                      "vg_idx");
   };
   if (int rc = merged()) return fail(nullptr, rc);
   // ctx's stream waited for every group's event and has been synchronised:
@@ -918,10 +877,7 @@ int verify_groups(bpp_ctx* ctx, const bpp_gens* G, const VerifyGroup* groups, si
       rejected = true;
   }
   if (!rejected) {
-    uint8_t e[32];
-    h25519::encode(e, res);
-    static const uint8_t zero[32] = {0};
-    if (memcmp(e, zero, 32) == 0) {
+    if (is_identity(res)) {
       if (each) memset(ok_out, 1, total);
       return BPP_OK;
     }
@@ -930,20 +886,7 @@ int verify_groups(bpp_ctx* ctx, const bpp_gens* G, const VerifyGroup* groups, si
   if (!each) return BPP_ERR_VERIFY;
   for (size_t s = 0; s < started; ++s)
     if (int rc = verify_each_dev(run[s].gctx, G, *run[s].job, ok_out + run[s].first)) return fail(run[s].gctx, rc);
-  size_t bad = 0, first_bad = total;
-  for (size_t p = total; p-- > 0;)
-    if (!ok_out[p]) {
-      ++bad;
-      first_bad = p;
-    }
-  if (!bad) {
-    memset(ok_out, 0, total);
-    ctx->err = "the batch check failed but no single proof did";
-    return BPP_ERR_DEVICE;
-  }
-  ctx->err = std::to_string(bad) + " of " + std::to_string(total) + " proofs failed, the first at index " +
-             std::to_string(first_bad);
-  return BPP_ERR_VERIFY;
+  return each_report(ctx, ok_out, total);
 }
 
 }  // namespace perm_impl

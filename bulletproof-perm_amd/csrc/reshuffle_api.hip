@@ -365,19 +365,15 @@ int verify_chunk(const VerifyArgs& a, const perm::Circuit& C, const uint8_t seed
     BPP_TRY(msm_single_dev(ctx, (const uint32_t*)d_s, (const uint32_t*)d_idx, G->d_tbl, T1, c, 0, (254 + c - 1) / c,
                            &res, (const uint32_t*)d_tbl, n0));
   }
-  static const uint8_t zero[32] = {0};
-  uint8_t e[32];
-  h25519::encode(e, res);
-  const bool sigma_ok = memcmp(e, zero, 32) == 0;
+  const bool sigma_ok = is_identity(res);
 
   std::vector<uint8_t> h_Du(2 * n * S), ok_s(P, 1);
   BPP_TRY(ctx_d2h(ctx, h_Du.data(), d_D, 2 * n * S));  // (D and u are adjacent; synchronises)
   if (!sigma_ok && ok) {
     // each proof's own checks (i) and (ii): P MSMs of 4k + 3 terms over the same
     // table and weights, in passes as verify_each_dev's
-    const uint32_t c = msm_choose_c((double)TP), Wn = (254 + c - 1) / c;
-    const size_t per = std::min<size_t>(
-        P, std::max<size_t>(1, std::min(((size_t)1 << 22) / TP, ((size_t)1 << 24) / ((size_t)Wn << (c - 1)))));
+    const uint32_t c = msm_choose_c((double)TP);
+    const size_t per = std::min<size_t>(P, std::max<size_t>(1, each_pass_proofs(TP, c)));
     void *d_res = nullptr, *d_renc = nullptr;
     BPP_TRY(ctx_ws(ctx, "rs_v_res", (size_t)P * P3_BYTES, &d_res));
     BPP_TRY(ctx_ws(ctx, "rs_v_renc", (size_t)P * 32, &d_renc));
@@ -392,6 +388,7 @@ int verify_chunk(const VerifyArgs& a, const perm::Circuit& C, const uint8_t seed
     BPP_TRY(points_compress_p3_dev(ctx, (const uint32_t*)d_res, P, (uint8_t*)d_renc));
     std::vector<uint8_t> renc((size_t)P * 32);
     BPP_TRY(ctx_d2h(ctx, renc.data(), d_renc, renc.size()));
+    static const uint8_t zero[32] = {0};  // (the results come back encoded)
     for (uint32_t p = 0; p < P; ++p) ok_s[p] = memcmp(renc.data() + 32 * (size_t)p, zero, 32) == 0;
   }
   if (!sigma_ok && !ok) return BPP_ERR_VERIFY;
@@ -405,9 +402,8 @@ int verify_chunk(const VerifyArgs& a, const perm::Circuit& C, const uint8_t seed
     memcpy(iproofs.data() + p * il, pf + (5 * (size_t)k + 3) * S, il);
   });
   const uint8_t* h_u = h_Du.data() + n * S;
-  if (!ok) return verify_batch(ctx, G, C, a.label, a.llen, P, iproofs.data(), iV.data(), h_u);
-  const int rc = verify_batch_each(ctx, G, C, a.label, a.llen, P, iproofs.data(), iV.data(), ok, h_u);
-  if (rc != BPP_OK && rc != BPP_ERR_VERIFY) return rc;
+  const int rc = verify_batch(ctx, G, C, a.label, a.llen, P, iproofs.data(), iV.data(), ok, h_u);
+  if (!ok || (rc != BPP_OK && rc != BPP_ERR_VERIFY)) return rc;
   bool all = true;
   for (uint32_t p = 0; p < P; ++p) all &= (ok[p] = ok[p] && ok_s[p] && !undec[p]) != 0;
   return all ? BPP_OK : BPP_ERR_VERIFY;
@@ -415,8 +411,9 @@ int verify_chunk(const VerifyArgs& a, const perm::Circuit& C, const uint8_t seed
 
 int verify_call(const VerifyArgs& a, bool each, bool len_ok) {
   bpp_ctx* const ctx = a.ctx;
-  if (each && a.ok_out && a.count) memset(a.ok_out, 0, a.count);
-  return bpp_guard(ctx, [&]() -> int {
+  uint8_t* const ok_out = each ? a.ok_out : nullptr;
+  ok_clear(ok_out, a.count);
+  const int rc = bpp_guard(ctx, [&]() -> int {
     // in the prover's order: the arrays and k, then the proofs' own scalars
     // (neither needs ctx or g), then the null handles
     if (((!a.cards_in || !a.cards_out || !a.proofs || (each && !a.ok_out)) && a.count) || (!a.label && a.llen))
@@ -446,36 +443,22 @@ int verify_call(const VerifyArgs& a, bool each, bool len_ok) {
     BPP_TRY(gens_cover(ctx, a.G, C->n_p));
     BPP_HIP(hipSetDevice(ctx->device));
     uint8_t seed[32];
-    if (!perm::verify_seed(seed)) {
-      ctx->err = "getrandom failed";
-      return BPP_ERR_DEVICE;
-    }
+    BPP_TRY(verify_seed_or_err(ctx, seed));
     const uint32_t per = chunk_of(k, a.count);
-    int verdict = BPP_OK;
+    bool failed = false;  // (each) some chunk's proof
     for (size_t p0 = 0; p0 < a.count; p0 += per) {
       const uint32_t P = (uint32_t)std::min<size_t>(per, a.count - p0);
-      const int rc = verify_chunk(a, *C, seed, p0, P, each ? a.ok_out + p0 : nullptr);
-      if (rc == BPP_ERR_VERIFY && each) {
-        verdict = rc;
-        continue;
-      }
-      if (rc != BPP_OK) {
-        if (each) memset(a.ok_out, 0, a.count);
-        return rc;
-      }
+      const int crc = verify_chunk(a, *C, seed, p0, P, each ? a.ok_out + p0 : nullptr);
+      if (crc == BPP_ERR_VERIFY && each)
+        failed = true;
+      else if (crc != BPP_OK)
+        return crc;
     }
-    if (each && verdict != BPP_OK) {
-      size_t nbad = 0, fb = a.count;
-      for (size_t p = a.count; p-- > 0;)
-        if (!a.ok_out[p]) {
-          ++nbad;
-          fb = p;
-        }
-      ctx->err = std::to_string(nbad) + " of " + std::to_string(a.count) + " proofs failed, the first at index " +
-                 std::to_string(fb);
-    }
-    return verdict;
+    // (a chunk answers BPP_ERR_VERIFY only after clearing one of its ok bytes,
+    // so each_report's "no single proof failed" branch is not reachable here)
+    return failed ? each_report(ctx, a.ok_out, a.count) : BPP_OK;
   });
+  return ok_settle(rc, ok_out, a.count);
 }
 
 }  // namespace
@@ -514,10 +497,7 @@ int bpp_reshuffle_prove_batch(bpp_ctx* ctx, const bpp_gens* G, uint32_t k, size_
     std::vector<uint8_t> ent;
     if (!seeds32) {
       ent.resize(32 * count);
-      if (!perm::os_entropy(ent.data(), ent.size())) {
-        ctx->err = "getrandom failed";
-        return BPP_ERR_DEVICE;
-      }
+      if (!perm::os_entropy(ent.data(), ent.size())) return no_entropy(ctx);
       seeds32 = ent.data();
     }
     // every chunk is proved into the caller's buffers only once it is whole; a

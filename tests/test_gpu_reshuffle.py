@@ -231,6 +231,26 @@ def test_verify_batch_each_names_the_failing_proofs(gens):
         assert (sigma, inner) == ((False, True) if p == 2 else (True, False))
 
 
+def test_verify_batch_each_error_text(gens):
+    """3 proofs at k = 2, the last one's z_R with its lowest bit flipped (still
+    canonical): the text counts the failing proofs and names the first."""
+    import bpperm
+    import ctypes
+    k, rows = 2, reference(2)
+    at = {name: off for name, off, _ in rr.regions(k)}["zR"]
+    proofs = [r[5] for r in rows]
+    proofs[2] = proofs[2][:at] + bytes([proofs[2][at] ^ 1]) + proofs[2][at + 1:]
+    assert int.from_bytes(proofs[2][at:at + 32], "little") < L
+    rs = bpperm.Reshuffler(gens, k)
+    ok = ctypes.create_string_buffer(3)
+    rc = rs.ctx.lib.bpp_reshuffle_verify_batch_each(rs.ctx.h, gens.h, k, 3, b"bp-perm", 7,
+                                                    b"".join(b"".join(r[0]) for r in rows),
+                                                    b"".join(b"".join(r[4]) for r in rows), b"".join(proofs), ok)
+    text = (rs.ctx.lib.bpp_ctx_last_error(rs.ctx.h) or b"").decode()
+    assert rc == VERIFY and list(ok.raw) == [1, 1, 0]
+    assert text.endswith("1 of 3 proofs failed, the first at index 2"), text
+
+
 def test_three_players_reshuffle_one_committed_deck(gens):
     """Player 0 commits 5 cards; players 1..3 re-shuffle in turn without any
     opening, every step verifies, and player 0 opens the final cards as

@@ -80,6 +80,49 @@ def test_every_failure_class(batch):
     assert pr.verify_batch(proofs, Vs)
 
 
+def _each_raw(pr, k, proofs, Vs):
+    """-> (rc, verdict bytes, the context's error text) of one bpp_perm_verify_batch_each call"""
+    import ctypes as C
+    n = len(proofs)
+    ok = C.create_string_buffer(n)
+    rc = pr.ctx.lib.bpp_perm_verify_batch_each(pr.ctx.h, pr.gens.h, k, n, pr.label, len(pr.label), b"".join(proofs),
+                                               b"".join(Vs), ok)
+    return rc, list(ok.raw), (pr.ctx.lib.bpp_ctx_last_error(pr.ctx.h) or b"").decode()
+
+
+@pytest.fixture(scope="module")
+def small(ctx):
+    """5 proofs at k = 2 (8 points, tau_x, mu, t_hat, L_0 ...), left unchanged."""
+    import bpperm
+    g = bpperm.Gens(ctx, 64)
+    pr = bpperm.PermProver(g, 2)
+    proofs, Vs = pr.prove_batch(list(range(82_000, 82_005)))
+    yield pr, proofs, Vs
+    g.close()
+
+
+def test_error_text_names_count_and_first(small):
+    """Proof 2 of 5 with t_hat's lowest bit flipped (still canonical)."""
+    pr, proofs, Vs = small
+    bad = list(proofs)
+    _xor(bad, 2, 10 * 32, 1)
+    assert [pr.verify(bad[i], Vs[i]) for i in range(5)] == [True, True, False, True, True]
+    rc, ok, text = _each_raw(pr, 2, bad, Vs)
+    assert rc == 6 and ok == [1, 1, 0, 1, 1]
+    assert text.endswith("1 of 5 proofs failed, the first at index 2"), text
+
+
+def test_undecodable_point_fails_its_proof_alone(small):
+    """L_0 of proof 1 of 4 with its top bit set: no field element, so no point."""
+    pr, proofs, Vs = small
+    bad = list(proofs[:4])
+    _xor(bad, 1, 11 * 32 + 31, 0x80)
+    assert [pr.verify(bad[i], Vs[i]) for i in range(4)] == [True, False, True, True]
+    rc, ok, text = _each_raw(pr, 2, bad, Vs[:4])
+    assert rc == 6 and ok == [1, 0, 1, 1]
+    assert text.endswith("1 of 4 proofs failed, the first at index 1"), text
+
+
 def test_edges(batch, ctx):
     import bpperm
     g, pr, proofs, Vs, bp, bv, singles = batch

@@ -185,6 +185,24 @@ def test_reject_and_name(grp, gens128, which, how):
         assert verdicts == (want if k == which else [True] * 3), k
 
 
+def test_error_text_names_count_and_first(grp, ctx, gens128):
+    """3 two-half proofs (k = 2) and 2 deck proofs (k = 3), the first deck proof
+    with t_hat's lowest bit flipped (still canonical): proof 3 of the call."""
+    import bpperm
+    a = grp["A"]
+    d = bpperm.DeckProver(gens128, 3)
+    proofs, Vs = d.prove_batch([perm_of(3, b"txt%d" % i) for i in range(2)],
+                               b"".join(seed32(b"txt%d" % i) for i in range(2)))
+    proofs[0] = _xor(proofs[0], 10 * 32, 1)
+    assert [d.verify(proofs[i], Vs[i]) for i in range(2)] == [False, True]
+    call = [a.entry(), (d, proofs, Vs)]
+    last = lambda: (ctx.lib.bpp_ctx_last_error(ctx.h) or b"").decode()
+    assert bpperm.verify_groups(gens128, call, each=True) == [[True] * 3, [False, True]]
+    assert last().endswith("1 of 5 proofs failed, the first at index 3"), last()
+    assert bpperm.verify_groups(gens128, call) is False  # (rc 6: any other code raises)
+    assert last().endswith("the batch check failed"), last()
+
+
 # ---------------------------------------------------------------------------
 # 3. kept apart
 
