@@ -105,6 +105,11 @@ SIGNATURES = {
     "bpp_reshuffle_verify": (i32, [vp, vp, u32, vp, sz, vp, vp, vp, sz]),
     "bpp_reshuffle_verify_batch": (i32, [vp, vp, u32, sz, vp, sz, vp, vp, vp]),
     "bpp_reshuffle_verify_batch_each": (i32, [vp, vp, u32, sz, vp, sz, vp, vp, vp, vp]),
+    "bpp_masked_reshuffle_proof_len": (sz, [u32]),
+    "bpp_masked_reshuffle_prove_batch": (i32, [vp, vp, u32, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+    "bpp_masked_reshuffle_verify": (i32, [vp, vp, u32, vp, vp, sz, vp, vp, vp, sz]),
+    "bpp_masked_reshuffle_verify_batch": (i32, [vp, vp, u32, sz, vp, vp, sz, vp, vp, vp]),
+    "bpp_masked_reshuffle_verify_batch_each": (i32, [vp, vp, u32, sz, vp, vp, sz, vp, vp, vp, vp]),
     "bpp_circuit_create": (i32, [vp, C.POINTER(vp)]),
     "bpp_circuit_destroy": (None, [vp]),
     "bpp_circuit_info": (i32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), vp]),

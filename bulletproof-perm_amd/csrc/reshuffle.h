@@ -12,6 +12,20 @@ inline uint32_t rs_points(uint32_t k) { return 5 * k + 1; }
 // Draws per proof; draw j is r, alpha, beta, t, w (k each), then t_R
 inline uint32_t rs_draws(uint32_t k) { return 5 * k + 1; }
 
+// What the masked re-shuffle (masked_reshuffle_api.hip) takes from
+// reshuffle_api.hip as it is: the inner circuit shuffle_of_public(k), compiled
+// once per k and kept (null: it did not compile), its proof's length, "k is a
+// size this argument takes" (BPP_ERR_ARG below 2, BPP_ERR_LEN past 342), and
+// k_decompress over n encodings with its verdict word reset (bad: 8 bytes, ~0
+// or the first index that does not decode)
+namespace perm {
+struct Circuit;
+}
+const perm::Circuit* rs_circuit(uint32_t k);
+size_t rs_inner_len(uint32_t k);
+int rs_k_check(bpp_ctx* ctx, uint32_t k);
+int rs_decompress_dev(bpp_ctx* ctx, const uint32_t* d_enc, size_t n, uint32_t* d_tbl, void* d_bad);
+
 // One transcript phase: up to three runs of 32-byte messages, run s = n[s]
 // messages under label lab[s] from seg[s] + p * stride[s] words, then one
 // challenge scalar.  A label is its bytes packed little-endian, ln its length.

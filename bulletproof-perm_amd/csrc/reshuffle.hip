@@ -8,6 +8,7 @@
 #include "ge_io.cuh"
 #include "merlin_dev.h"
 #include "merlin_lane.cuh"
+#include "rs_dev.cuh"
 #include "sc25519.cuh"
 
 namespace {
@@ -31,40 +32,6 @@ FE_INLINE sc shake_wide_scalar(uint64_t a[25], int n) {
     w[2 * i + 1] = (uint32_t)(a[i] >> 32);
   }
   return sc_from_wide_w(w);
-}
-
-FE_INLINE sc sc_from_u32(uint32_t v) {
-  sc r = sc_zero();
-  r.v[0] = v;
-  return r;
-}
-// a b for canonical a, b
-FE_INLINE sc sc_mul(const sc& a, const sc& b) { return sc_mont(sc_to_mont(a), b); }
-// x^e in Montgomery form from x in Montgomery form, e >= 1 (e is public: a
-// card's index)
-FE_INLINE sc sc_pow_mont(const sc& xR, uint32_t e) {
-  sc r = xR;
-  for (int i = 30 - __builtin_clz(e); i >= 0; --i) {
-    r = sc_mont(r, r);
-    if ((e >> i) & 1u) r = sc_mont(r, xR);
-  }
-  return r;
-}
-
-// take_b ? b : a, limb by limb under a mask: no branch on the (secret) bit
-FE_INLINE fe fe_select(const fe& a, const fe& b, uint32_t mask) {
-  fe r;
-  _Pragma("unroll") for (int i = 0; i < FE_LIMBS; ++i) r.v[i] = a.v[i] ^ ((a.v[i] ^ b.v[i]) & mask);
-  return r;
-}
-FE_INLINE ge_p3 ge_select(const ge_p3& a, const ge_p3& b, uint32_t take_b) {
-  const uint32_t mask = 0u - take_b;
-  ge_p3 r;
-  r.X = fe_select(a.X, b.X, mask);
-  r.Y = fe_select(a.Y, b.Y, mask);
-  r.Z = fe_select(a.Z, b.Z, mask);
-  r.T = fe_select(a.T, b.T, mask);
-  return r;
 }
 
 // merlin's append_message(label, 32 bytes) and challenge_scalar(label) with the
@@ -191,9 +158,7 @@ __global__ void __launch_bounds__(64) k_rs_exponents(uint32_t P, uint32_t k, con
   sc_store(b + 8 * t, sc_from_mont(sc_pow_mont(xR, perms[t] + 1)));
 }
 
-// Lane (p, i): t_i C'_i for the secret nonce t_i, by double-and-add-always: 253
-// doublings, 253 additions and a select per bit, the same instructions and the
-// same addresses whatever t_i is (as pedersen_dev's walk is for its scalars).
+// Lane (p, i): t_i C'_i for the secret nonce t_i, in constant time (ge_ct_mul).
 __global__ void __launch_bounds__(64) k_rs_tsum_mul(uint32_t P, uint32_t k, const uint32_t* __restrict__ draws,
                                                     const uint32_t* __restrict__ tbl_out, uint32_t* __restrict__ prod) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -202,10 +167,7 @@ __global__ void __launch_bounds__(64) k_rs_tsum_mul(uint32_t P, uint32_t k, cons
   const ge_niels A = load_niels(tbl_out, (uint32_t)t);
   const uint32_t* ts = draws + 8 * (3 * n + t);  // (a word per 32 bits: no register array indexed by the bit)
   ge_p3 acc = ge_identity();
-  _Pragma("nounroll") for (int bit = 252; bit >= 0; --bit) {
-    acc = ge_dbl(acc);
-    acc = ge_select(acc, ge_madd(acc, A), (ts[bit >> 5] >> (bit & 31)) & 1u);
-  }
+  _Pragma("nounroll") for (int bit = 252; bit >= 0; --bit) acc = ge_ct_step(acc, A, (ts[bit >> 5] >> (bit & 31)) & 1u);
   store_p3(prod, t, acc);
 }
 

@@ -514,6 +514,81 @@ int bpp_reshuffle_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, uint32_t k,
                                     size_t llen, const uint8_t* cards_in, const uint8_t* cards_out,
                                     const uint8_t* proofs, uint8_t* ok_out);
 
+/* ----------------------------------------- masked re-shuffle proof (sound) */
+/* The blind re-shuffle over cards that can be dealt: a card is an ElGamal pair
+ * (U, W) = (rho B, M + rho K) under the table's joint key K = sum_j K_j, and a
+ * shuffle permutes and re-masks it.  A blindly re-shuffled commitment stays
+ * closed for good (nobody holds the sum of its blindings); a masked card opens
+ * as M = W - sum_j sk_j U once every player publishes its share sk_j U, with
+ * nobody's permutation disclosed.  The open deck (identity, M_j) -- 32 zero
+ * bytes, then the card's public point -- needs no proof, so every player, the
+ * first included, runs this same step.  The decryption shares and their proofs
+ * are not part of this library yet.
+ * Statement.  Public: a key K, input cards (U_j, W_j) and output cards (U'_i,
+ * W'_i), any valid ristretto255 encodings (the identity included; K = identity
+ * is degenerate and not refused).  The prover knows a bijection pi on [0, k)
+ * and scalars r_i with U'_i = U_{pi(i)} + r_i B and W'_i = W_{pi(i)} + r_i K, B
+ * the Pedersen value base of g; perms[i] = pi(i).  One key per call.
+ * Argument (DESIGN.md "Protocol: masked re-shuffle"), T = Transcript(label);
+ * what is not named here is the blind re-shuffle's:
+ *   append_message("dom-sep", "masked reshuffle v1"), append_u64("k", k), K
+ *   under "K";  every input card as two messages, U_j then W_j, under "C", every
+ *   output card the same way under "C'";  A_i, x, E_i, y as there;  T_i under
+ *   "Ti", T_U = sum_i t_i U'_i - t_R B and T_W = sum_i t_i W'_i - t_R K under "T",
+ *   T_U first, c = challenge_scalar("c");  z_i, om_i, z_R = t_R + c sum_i b_i r_i
+ *   and the circuit proof as there.
+ * The verifier accepts iff z_i B + om_i Bb = T_i + c E_i for every i, sum_i z_i
+ * U'_i - z_R B = T_U + c sum_j e_j U_j, sum_i z_i W'_i - z_R K = T_W + c sum_j e_j
+ * W_j, and the circuit proof verifies.  Both sums share z_i and z_R: one r_i
+ * re-masks both halves of a card.
+ * Proof bytes, bpp_masked_reshuffle_proof_len(k) = 32 (5k + 4) + the circuit
+ * proof's (9312 at k = 52; 0 for a k outside [2, 342]):
+ *   A[k] | E[k] | Ti[k] | T_U | T_W | z[k] | om[k] | z_R | V_k | circuit proof.
+ *   k           as bpp_reshuffle_*, with its error codes.
+ *   key         32 B.
+ *   cards_in / cards_out   count x k x 64 B, U | W per card.
+ *   perms       count x k u32;  blinds  NULL, or count x k x 32 B: the r_i.
+ * Randomness: the draws (their indices, their order r, alpha, beta, t, w, t_R,
+ * the blinds in place of draws 0..k-1), the circuit prover's seed and the batch
+ * weights rho_p are bpp_reshuffle_prove_batch's and _verify_batch's, domain
+ * strings included.  Seeds are single-use: a seed used for a plain re-shuffle
+ * must not be used again for a masked one, nor the other way round.
+ * Checks of the prover, before any device work and before any output byte: a
+ * perm that is not a bijection on [0, k) -> BPP_ERR_ARG; a blind >= l ->
+ * BPP_ERR_NONCANONICAL (neither needs ctx or g); then the k / g / null checks.
+ * A key or a component of an input card that does not decode ->
+ * BPP_ERR_DECOMPRESS, found on the device before any secret is staged there and
+ * before any output byte.  count == 0: BPP_OK.
+ * The verifiers mirror bpp_reshuffle_verify, _verify_batch and
+ * _verify_batch_each: a response scalar >= l -> BPP_ERR_NONCANONICAL before any
+ * device work; a card component or a point A, E, Ti, T_U, T_W that does not
+ * decode -> BPP_ERR_DECOMPRESS, found on the device before anything else runs
+ * (_each instead fails that proof alone); a key that does not decode refuses
+ * the whole call, in _each too.  A batch merges the first three checks of all
+ * proofs into ONE MSM of 6k + 2 points per proof plus B, Bb and K, under weights
+ * rho_p^1..rho_p^k, rho_p^(k+1) for the U sum and rho_p^(k+2) for the W sum.
+ * _each: when the merged MSM does not pass, one MSM of 6k + 5 terms per proof; a
+ * proof's verdict is that AND the circuit verifier's.
+ * Secret lifetime: that of bpp_reshuffle_prove_batch; r_i B, r_i K, t_i U'_i,
+ * t_i W'_i, t_R B and t_R K are part of what is zeroed and of what
+ * bpp_debug_secret_residue counts.  No secret goes through the bucket engine.
+ * bpp_verify_groups and the multi-GPU job API do not take these proofs. */
+size_t bpp_masked_reshuffle_proof_len(uint32_t k);
+int bpp_masked_reshuffle_prove_batch(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* key,
+                                     const uint8_t* cards_in, const uint32_t* perms, const uint8_t* blinds,
+                                     const uint8_t* seeds32, const uint8_t* label, size_t llen, uint8_t* cards_out,
+                                     uint8_t* proofs_out);
+int bpp_masked_reshuffle_verify(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, const uint8_t* key, const uint8_t* label,
+                                size_t llen, const uint8_t* cards_in, const uint8_t* cards_out, const uint8_t* proof,
+                                size_t proof_len);
+int bpp_masked_reshuffle_verify_batch(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count, const uint8_t* key,
+                                      const uint8_t* label, size_t llen, const uint8_t* cards_in,
+                                      const uint8_t* cards_out, const uint8_t* proofs);
+int bpp_masked_reshuffle_verify_batch_each(bpp_ctx* ctx, const bpp_gens* g, uint32_t k, size_t count,
+                                           const uint8_t* key, const uint8_t* label, size_t llen,
+                                           const uint8_t* cards_in, const uint8_t* cards_out, const uint8_t* proofs,
+                                           uint8_t* ok_out);
+
 /* -------------------------------------- caller-defined circuits (sound) */
 /* After the shuffle a game needs predicates over the commitments it produced
  * ("the card I play is one of these 13", "this value is below 2^6", "these two
