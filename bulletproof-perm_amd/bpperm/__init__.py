@@ -808,34 +808,46 @@ class DeckProver:
         return [b != 0 for b in ok.raw[:count]]
 
 
-class Reshuffler:
-    """Blind re-shuffle proof (bpp_reshuffle_*): the output cards are a
-    permutation of the input cards, each re-blinded with a multiple of
-    B_blinding, and the prover opens none of them -- the step of a card game in
-    which a second player shuffles a deck that the first one committed.  A card
-    is a 32-byte ristretto255 encoding; 2 <= k <= 342, and gens covers
-    max(4, next_pow2(2k - 2))."""
+class _Reshuffle:
+    """What the two kinds of re-shuffle proof share: every call, over the
+    kind's export-name stem, the bytes of one card, the text that refuses cards
+    of another size, and the leading key argument (none, or the key)."""
+    _stem = ""       # bpp_<..>_prove_batch, .._verify, ..
+    _card = 0        # bytes per card
+    _card_what = ""  # "expected ..": what _cards refuses with
+    _key = ()        # the exports' key argument: none, or (key,)
 
     def __init__(self, gens: Gens, k: int, label: bytes = b"bp-perm", ctx: "Context | None" = None):
         self.gens = gens
         self.ctx = ctx or gens.ctx
         self.k = k
         self.label = label
-        self.proof_len = int(self.ctx.lib.bpp_reshuffle_proof_len(k))
+        self.proof_len = int(getattr(self.ctx.lib, self._stem + "_proof_len")(k))
+
+    def _call(self, name: str, *args) -> "tuple[int, str]":
+        """bpp_<stem>_<name>(ctx, gens, k, ..): its return code, and the export's name"""
+        name = f"{self._stem}_{name}"
+        return getattr(self.ctx.lib, name)(self.ctx.h, self.gens.h, self.k, *args), name
+
+    def _verdict(self, rc: int, name: str) -> bool:
+        if rc == 6:
+            return False
+        check(rc, name, self.ctx.h)
+        return True
 
     def _cards(self, cards, count: int, what: str) -> bytes:
         cb = bytes(cards) if isinstance(cards, (bytes, bytearray)) else b"".join(_join(c, 32, what) for c in cards)
-        if len(cb) != 32 * self.k * count:
-            raise ValueError(f"{what}: expected k encodings of 32 bytes per proof")
+        if len(cb) != self._card * self.k * count:
+            raise ValueError(f"{what}: {self._card_what}")
         return cb
 
     def shuffle_batch(self, cards_in, perms, blinds=None, seeds32: bytes | None = None, raw: bool = False):
-        """cards_in[p] = the k input cards of shuffle p; perms[p] = k indices,
-        output slot i holding input perms[p][i]; blinds[p] = the k scalars r_i
-        (None: drawn); seeds32 = 32 bytes per proof (None: the OS CSPRNG).
-        Returns (cards_out, proofs): per shuffle the k output cards joined and
-        the proof (raw=True: the two contiguous buffers).  The batch's secrets
-        are wiped."""
+        """cards_in[p] = the k input cards of shuffle p (joined, or their
+        32-byte encodings in order); perms[p] = k indices, output slot i holding
+        input perms[p][i]; blinds[p] = the k scalars r_i (None: drawn); seeds32
+        = 32 bytes per proof (None: the OS CSPRNG).  Returns (cards_out,
+        proofs): per shuffle the k output cards joined and the proof (raw=True:
+        the two contiguous buffers).  The batch's secrets are wiped."""
         count = len(perms)
         if blinds is not None and len(blinds) != count:
             raise ValueError("perms and blinds must have one entry per proof")
@@ -851,27 +863,22 @@ class Reshuffler:
         if len(flat) != self.k * count:
             raise ValueError("perms: expected k indices per proof")
         pm = (C.c_uint32 * max(len(flat), 1))(*flat)
-        out = C.create_string_buffer(max(32 * self.k * count, 1))
+        deck = self._card * self.k
+        out = C.create_string_buffer(max(deck * count, 1))
         pf = C.create_string_buffer(max(self.proof_len * count, 1))
-        check(self.ctx.lib.bpp_reshuffle_prove_batch(self.ctx.h, self.gens.h, self.k, count, _buf(cb), pm,
-                                                     _buf(bb) if bb is not None else None,
-                                                     _buf(seeds32) if seeds32 is not None else None,
-                                                     _buf(self.label), len(self.label), out, pf),
-              "bpp_reshuffle_prove_batch", self.ctx.h)
-        oraw, praw = out.raw[:32 * self.k * count], pf.raw[:self.proof_len * count]
+        rc, name = self._call("prove_batch", count, *self._key, _buf(cb), pm, _buf(bb) if bb is not None else None,
+                              _buf(seeds32) if seeds32 is not None else None, _buf(self.label), len(self.label), out, pf)
+        check(rc, name, self.ctx.h)
+        oraw, praw = out.raw[:deck * count], pf.raw[:self.proof_len * count]
         if raw:
             return oraw, praw
-        return ([oraw[i * 32 * self.k:(i + 1) * 32 * self.k] for i in range(count)],
+        return ([oraw[i * deck:(i + 1) * deck] for i in range(count)],
                 [praw[i * self.proof_len:(i + 1) * self.proof_len] for i in range(count)])
 
     def verify(self, cards_in, cards_out, proof: bytes) -> bool:
         ci, co = self._cards(cards_in, 1, "cards_in"), self._cards(cards_out, 1, "cards_out")
-        rc = self.ctx.lib.bpp_reshuffle_verify(self.ctx.h, self.gens.h, self.k, _buf(self.label), len(self.label),
-                                               _buf(ci), _buf(co), _buf(proof), len(proof))
-        if rc == 6:
-            return False
-        check(rc, "bpp_reshuffle_verify", self.ctx.h)
-        return True
+        return self._verdict(*self._call("verify", *self._key, _buf(self.label), len(self.label), _buf(ci), _buf(co),
+                                         _buf(proof), len(proof)))
 
     def _batch(self, cards_in, cards_out, proofs):
         pb = bytes(proofs) if isinstance(proofs, (bytes, bytearray)) else b"".join(proofs)
@@ -884,123 +891,49 @@ class Reshuffler:
         """cards_in / cards_out / proofs: sequences with one entry per proof, or
         the contiguous buffers (shuffle_batch(..., raw=True))."""
         ci, co, pb, count = self._batch(cards_in, cards_out, proofs)
-        rc = self.ctx.lib.bpp_reshuffle_verify_batch(self.ctx.h, self.gens.h, self.k, count, _buf(self.label),
-                                                     len(self.label), _buf(ci), _buf(co), _buf(pb))
-        if rc == 6:
-            return False
-        check(rc, "bpp_reshuffle_verify_batch", self.ctx.h)
-        return True
+        return self._verdict(*self._call("verify_batch", count, *self._key, _buf(self.label), len(self.label), _buf(ci),
+                                         _buf(co), _buf(pb)))
 
     def verify_batch_each(self, cards_in, cards_out, proofs) -> "list[bool]":
-        """One verdict per proof, what verify() returns for it alone
-        (bpp_reshuffle_verify_batch_each).  Inputs as verify_batch."""
+        """One verdict per proof, what verify() returns for it alone (the
+        kind's .._verify_batch_each).  Inputs as verify_batch."""
         ci, co, pb, count = self._batch(cards_in, cards_out, proofs)
         ok = C.create_string_buffer(max(count, 1))
-        rc = self.ctx.lib.bpp_reshuffle_verify_batch_each(self.ctx.h, self.gens.h, self.k, count, _buf(self.label),
-                                                          len(self.label), _buf(ci), _buf(co), _buf(pb), ok)
+        rc, name = self._call("verify_batch_each", count, *self._key, _buf(self.label), len(self.label), _buf(ci),
+                              _buf(co), _buf(pb), ok)
         if rc != 6:
-            check(rc, "bpp_reshuffle_verify_batch_each", self.ctx.h)
+            check(rc, name, self.ctx.h)
         return [b != 0 for b in ok.raw[:count]]
 
 
-class MaskedReshuffler:
+class Reshuffler(_Reshuffle):
+    """Blind re-shuffle proof (bpp_reshuffle_*): the output cards are a
+    permutation of the input cards, each re-blinded with a multiple of
+    B_blinding, and the prover opens none of them -- the step of a card game in
+    which a second player shuffles a deck that the first one committed.  A card
+    is a 32-byte ristretto255 encoding; 2 <= k <= 342, and gens covers
+    max(4, next_pow2(2k - 2))."""
+    _stem, _card, _card_what = "bpp_reshuffle", 32, "expected k encodings of 32 bytes per proof"
+
+
+class MaskedReshuffler(_Reshuffle):
     """Masked re-shuffle proof (bpp_masked_reshuffle_*): the blind re-shuffle
     over ElGamal pairs under a table's joint key, the shuffle a game can deal
     cards from.  A card is 64 bytes, U | W = (rho B, M + rho K); the output
     cards are a permutation of the input cards, each re-masked with (r B, r K)
     under one r.  The open deck is 32 zero bytes and the card's public point per
     card and needs no proof.  key: K, 32 bytes; 2 <= k <= 342, and gens covers
-    max(4, next_pow2(2k - 2))."""
+    max(4, next_pow2(2k - 2)).  A shuffle's input cards are 64 bytes each, or
+    the 2k encodings U_0, W_0, U_1, ..; its output cards come joined, 64 k
+    bytes."""
+    _stem, _card, _card_what = "bpp_masked_reshuffle", 64, "expected k cards of 64 bytes (U | W) per proof"
 
     def __init__(self, gens: Gens, k: int, key: bytes, label: bytes = b"bp-perm", ctx: "Context | None" = None):
         if len(key) != 32:
             raise ValueError("key: expected one 32-byte encoding")
-        self.gens = gens
-        self.ctx = ctx or gens.ctx
-        self.k = k
+        super().__init__(gens, k, label, ctx)
         self.key = bytes(key)
-        self.label = label
-        self.proof_len = int(self.ctx.lib.bpp_masked_reshuffle_proof_len(k))
-
-    def _cards(self, cards, count: int, what: str) -> bytes:
-        cb = bytes(cards) if isinstance(cards, (bytes, bytearray)) else b"".join(_join(c, 32, what) for c in cards)
-        if len(cb) != 64 * self.k * count:
-            raise ValueError(f"{what}: expected k cards of 64 bytes (U | W) per proof")
-        return cb
-
-    def shuffle_batch(self, cards_in, perms, blinds=None, seeds32: bytes | None = None, raw: bool = False):
-        """cards_in[p] = the k input cards of shuffle p (64 bytes each, or the
-        2k encodings U_0, W_0, U_1, ..); perms, blinds, seeds32 and raw as
-        Reshuffler.shuffle_batch.  Returns (cards_out, proofs): per shuffle the
-        k output cards joined (64 k bytes) and the proof.  The batch's secrets
-        are wiped."""
-        count = len(perms)
-        if blinds is not None and len(blinds) != count:
-            raise ValueError("perms and blinds must have one entry per proof")
-        if seeds32 is not None and len(seeds32) != 32 * count:
-            raise ValueError("seeds32 must hold 32 bytes per proof")
-        cb = self._cards(cards_in, count, "cards_in")
-        bb = None
-        if blinds is not None:
-            bb = b"".join(x if isinstance(x, (bytes, bytearray)) else _join(x, 32, "blinds") for x in blinds)
-            if len(bb) != 32 * self.k * count:
-                raise ValueError("blinds: expected k scalars of 32 bytes per proof")
-        flat = [int(i) for p in perms for i in p]
-        if len(flat) != self.k * count:
-            raise ValueError("perms: expected k indices per proof")
-        pm = (C.c_uint32 * max(len(flat), 1))(*flat)
-        out = C.create_string_buffer(max(64 * self.k * count, 1))
-        pf = C.create_string_buffer(max(self.proof_len * count, 1))
-        check(self.ctx.lib.bpp_masked_reshuffle_prove_batch(self.ctx.h, self.gens.h, self.k, count, _buf(self.key),
-                                                            _buf(cb), pm, _buf(bb) if bb is not None else None,
-                                                            _buf(seeds32) if seeds32 is not None else None,
-                                                            _buf(self.label), len(self.label), out, pf),
-              "bpp_masked_reshuffle_prove_batch", self.ctx.h)
-        oraw, praw = out.raw[:64 * self.k * count], pf.raw[:self.proof_len * count]
-        if raw:
-            return oraw, praw
-        return ([oraw[i * 64 * self.k:(i + 1) * 64 * self.k] for i in range(count)],
-                [praw[i * self.proof_len:(i + 1) * self.proof_len] for i in range(count)])
-
-    def verify(self, cards_in, cards_out, proof: bytes) -> bool:
-        ci, co = self._cards(cards_in, 1, "cards_in"), self._cards(cards_out, 1, "cards_out")
-        rc = self.ctx.lib.bpp_masked_reshuffle_verify(self.ctx.h, self.gens.h, self.k, _buf(self.key), _buf(self.label),
-                                                      len(self.label), _buf(ci), _buf(co), _buf(proof), len(proof))
-        if rc == 6:
-            return False
-        check(rc, "bpp_masked_reshuffle_verify", self.ctx.h)
-        return True
-
-    def _batch(self, cards_in, cards_out, proofs):
-        pb = bytes(proofs) if isinstance(proofs, (bytes, bytearray)) else b"".join(proofs)
-        if self.proof_len == 0 or len(pb) % self.proof_len:
-            raise ValueError("proofs: not a whole number of proofs")
-        count = len(pb) // self.proof_len
-        return self._cards(cards_in, count, "cards_in"), self._cards(cards_out, count, "cards_out"), pb, count
-
-    def verify_batch(self, cards_in, cards_out, proofs) -> bool:
-        """cards_in / cards_out / proofs: sequences with one entry per proof, or
-        the contiguous buffers (shuffle_batch(..., raw=True))."""
-        ci, co, pb, count = self._batch(cards_in, cards_out, proofs)
-        rc = self.ctx.lib.bpp_masked_reshuffle_verify_batch(self.ctx.h, self.gens.h, self.k, count, _buf(self.key),
-                                                            _buf(self.label), len(self.label), _buf(ci), _buf(co),
-                                                            _buf(pb))
-        if rc == 6:
-            return False
-        check(rc, "bpp_masked_reshuffle_verify_batch", self.ctx.h)
-        return True
-
-    def verify_batch_each(self, cards_in, cards_out, proofs) -> "list[bool]":
-        """One verdict per proof, what verify() returns for it alone
-        (bpp_masked_reshuffle_verify_batch_each).  Inputs as verify_batch."""
-        ci, co, pb, count = self._batch(cards_in, cards_out, proofs)
-        ok = C.create_string_buffer(max(count, 1))
-        rc = self.ctx.lib.bpp_masked_reshuffle_verify_batch_each(self.ctx.h, self.gens.h, self.k, count,
-                                                                 _buf(self.key), _buf(self.label), len(self.label),
-                                                                 _buf(ci), _buf(co), _buf(pb), ok)
-        if rc != 6:
-            check(rc, "bpp_masked_reshuffle_verify_batch_each", self.ctx.h)
-        return [b != 0 for b in ok.raw[:count]]
+        self._key = (_buf(self.key),)
 
 
 class _CircuitDescC(C.Structure):

@@ -1,6 +1,6 @@
-// Device helpers the re-shuffle kernels share (reshuffle.hip, the blind
-// re-shuffle; masked_reshuffle.hip, the masked one): small scalar steps, the
-// masked select, and the constant-time scalar-times-point walk.
+// Device helpers the re-shuffle kernels share (reshuffle.hip: k_rs_*, the blind
+// re-shuffle's, and k_mrs_*, the masked one's): small scalar steps, the masked
+// select, and the constant-time scalar-times-point walk.
 #pragma once
 #include "ge_io.cuh"
 #include "sc25519.cuh"

@@ -4,9 +4,11 @@ batches across a wave boundary, the edge inputs, every region bound, every
 refusal by name, per-proof verdicts (a card whose halves were re-masked under
 two different scalars among them), a three-player chain from the open deck that
 the key's discrete log unmasks, and the batch's secrets wiped with the plain
-re-shuffle still exact in the same process."""
+re-shuffle still exact in the same process, every refusal's text, and a batch
+one proof longer than a launch sequence takes."""
 import ctypes
 import json
+import random
 import sys
 from pathlib import Path
 
@@ -23,6 +25,8 @@ L = mr.L
 GOLDEN = json.loads((HERE / "golden" / "masked_reshuffle.json").read_text())["cases"]
 ARG, LEN, DECOMPRESS, NONCANONICAL, VERIFY = 1, 2, 3, 4, 6
 UNDECODABLE = b"\xff" * 32
+K_TEXT = "reshuffle: k > 342 (the inner circuit's 2k - 2 gates pass the plain bound of 682)"
+KEY_TEXT = "masked reshuffle: the key does not decode"
 
 
 @pytest.fixture(scope="module")
@@ -325,3 +329,115 @@ def test_secrets_are_wiped_and_the_plain_reshuffle_is_unmoved(gens, ctx):
     assert ms.shuffle_batch(cards, perms, blinds=blinds, seeds32=seeds) == first
     assert ms.verify_batch(cards, first[0], first[1])
     assert ctx.secret_residue() == 0
+
+
+def test_refusal_texts(gens, one):
+    """k = 3, at most 3 proofs a call: what bpp_ctx_last_error ends with after
+    each refusal, the proof's index (never 0 alone), the card's or point's and
+    the card's half among them; the key's from the prover and the three
+    verifiers."""
+    import bpperm
+    ms, cards, out, pf, o = one
+    perm, seed = reference(3)[1][0][1], reference(3)[1][0][2]
+    lib, bad = ms.ctx.lib, UNDECODABLE
+    nokey = bpperm.MaskedReshuffler(gens, 3, UNDECODABLE)
+
+    def text_of(code, f, *a, **kw):
+        with pytest.raises(bpperm.BppError) as e:
+            f(*a, **kw)
+        assert e.value.code == code
+        return (lib.bpp_ctx_last_error(ms.ctx.h) or b"").decode()
+
+    def at(region, i=0):
+        return pf[:o[region] + 32 * i] + bad + pf[o[region] + 32 * i + 32:]
+
+    def verifier(code, q, ci=cards, co=out, proof=pf):  # three proofs, proof q as given
+        cis, cos, pfs = [cards] * 3, [out] * 3, [pf] * 3
+        cis[q], cos[q], pfs[q] = ci, co, proof
+        return text_of(code, ms.verify_batch, cis, cos, pfs)
+
+    bad_u, bad_w = bad + cards[1][32:], cards[2][:32] + bad
+    # the key: the prover and the three verifiers
+    assert text_of(DECOMPRESS, nokey.shuffle_batch, [cards], [perm], seeds32=seed).endswith(KEY_TEXT)
+    assert text_of(DECOMPRESS, nokey.verify, cards, out, pf).endswith(KEY_TEXT)
+    assert text_of(DECOMPRESS, nokey.verify_batch, [cards] * 2, [out] * 2, [pf] * 2).endswith(KEY_TEXT)
+    assert text_of(DECOMPRESS, nokey.verify_batch_each, [cards] * 2, [out] * 2, [pf] * 2).endswith(KEY_TEXT)
+    # the prover
+    t = text_of(DECOMPRESS, ms.shuffle_batch, [cards, [cards[0], bad_u, cards[2]]], [perm, perm], seeds32=seed * 2)
+    assert t.endswith("masked reshuffle 1: U of input card 1 does not decode"), t
+    t = text_of(DECOMPRESS, ms.shuffle_batch, [cards, cards, cards[:2] + [bad_w]], [perm] * 3, seeds32=seed * 3)
+    assert t.endswith("masked reshuffle 2: W of input card 2 does not decode"), t
+    t = text_of(ARG, ms.shuffle_batch, [cards] * 3, [perm, perm, [0, 0, 1]], seeds32=seed * 3)
+    assert t.endswith("masked reshuffle 2: perm is not a bijection on [0, k)"), t
+    t = text_of(NONCANONICAL, ms.shuffle_batch, [cards] * 2, [perm] * 2, seeds32=seed * 2,
+                blinds=[[mr.sb(1)] * 3, [mr.sb(1), L.to_bytes(32, "little"), mr.sb(2)]])
+    assert t.endswith("masked reshuffle 1: non-canonical blind"), t
+    # the verifier, one case per class of point
+    t = verifier(DECOMPRESS, 1, ci=[cards[0], bad_u, cards[2]])
+    assert t.endswith("masked reshuffle 1: U of input card 1 does not decode"), t
+    t = verifier(DECOMPRESS, 2, ci=cards[:2] + [bad_w])
+    assert t.endswith("masked reshuffle 2: W of input card 2 does not decode"), t
+    t = verifier(DECOMPRESS, 2, co=[bad + out[0][32:]] + out[1:])
+    assert t.endswith("masked reshuffle 2: U of output card 0 does not decode"), t
+    t = verifier(DECOMPRESS, 1, co=[out[0], out[1][:32] + bad, out[2]])
+    assert t.endswith("masked reshuffle 1: W of output card 1 does not decode"), t
+    t = verifier(DECOMPRESS, 0, proof=at("A", 1))
+    assert t.endswith("masked reshuffle 0: A 1 does not decode"), t
+    t = verifier(DECOMPRESS, 2, proof=at("E", 0))
+    assert t.endswith("masked reshuffle 2: E 0 does not decode"), t
+    t = verifier(DECOMPRESS, 1, proof=at("Ti", 2))
+    assert t.endswith("masked reshuffle 1: T 2 does not decode"), t
+    t = verifier(DECOMPRESS, 2, proof=at("TU"))
+    assert t.endswith("masked reshuffle 2: T_U does not decode"), t
+    t = verifier(DECOMPRESS, 1, proof=at("TW"))
+    assert t.endswith("masked reshuffle 1: T_W does not decode"), t
+    t = verifier(NONCANONICAL, 2, proof=pf[:o["om"]] + L.to_bytes(32, "little") + pf[o["om"] + 32:])
+    assert t.endswith("masked reshuffle 2: a response scalar is not canonical"), t
+    # k = 343, on both sides: the blind re-shuffle's text
+    buf, sink = bytes(343 * 64), ctypes.create_string_buffer(343 * 64)
+    ident = (ctypes.c_uint32 * 343)(*range(343))
+    assert lib.bpp_masked_reshuffle_prove_batch(ms.ctx.h, gens.h, 343, 1, ms.key, buf, ident, None, seed, b"bp-perm", 7,
+                                                sink, sink) == LEN
+    assert (lib.bpp_ctx_last_error(ms.ctx.h) or b"").decode().endswith(K_TEXT)
+    assert lib.bpp_masked_reshuffle_verify(ms.ctx.h, gens.h, 343, ms.key, b"bp-perm", 7, buf, buf, buf, 32) == LEN
+    assert (lib.bpp_ctx_last_error(ms.ctx.h) or b"").decode().endswith(K_TEXT)
+
+
+def test_a_batch_across_a_chunk_boundary(ctx):
+    """k = 342: a launch sequence takes 2^22 / (7k + 2) = 1750 proofs, so 1751
+    shuffles of one open deck run as two.  The batch verifies; with z_0 + 1 in
+    proofs 0, 1749 and 1750 exactly those three fail; an undecodable A_0 in
+    proof 1750 alone refuses the batch and names that proof."""
+    import bpperm
+    k, chunk = 342, 1750
+    count = chunk + 1
+    assert chunk == (1 << 22) // (7 * k + 2)
+    rnd = random.Random(343)
+    g = bpperm.Gens(ctx, 1024)
+    try:
+        pts = g.pedersen_commit([mr.sb(10 + i) for i in range(k + 1)], [mr.sb(rnd.randrange(L)) for _ in range(k + 1)])
+        ms = bpperm.MaskedReshuffler(g, k, pts[k])
+        cin = b"".join(bytes(32) + m for m in pts[:k]) * count  # the open deck
+        cout, proofs = ms.shuffle_batch(cin, [rnd.sample(range(k), k) for _ in range(count)],
+                                        seeds32=rnd.randbytes(32 * count), raw=True)
+        assert ms.verify_batch(cin, cout, proofs)
+        pl, z0 = ms.proof_len, 32 * (3 * k + 2)
+        bad = bytearray(proofs)
+        for p in (0, chunk - 1, chunk):
+            at = p * pl + z0
+            bad[at:at + 32] = mr.sb(int.from_bytes(bad[at:at + 32], "little") + 1)
+        ok = ctypes.create_string_buffer(count)
+        rc = ctx.lib.bpp_masked_reshuffle_verify_batch_each(ctx.h, g.h, k, count, ms.key, b"bp-perm", 7, cin, cout,
+                                                            bytes(bad), ok)
+        text = (ctx.lib.bpp_ctx_last_error(ctx.h) or b"").decode()
+        assert rc == VERIFY
+        assert [p for p in range(count) if not ok.raw[p]] == [0, chunk - 1, chunk]
+        assert text.endswith("3 of %d proofs failed, the first at index 0" % count), text
+        bad = bytearray(proofs)
+        bad[chunk * pl:chunk * pl + 32] = b"\xff" * 32
+        with pytest.raises(bpperm.BppError) as e:
+            ms.verify_batch(cin, cout, bytes(bad))
+        assert e.value.code == DECOMPRESS
+        assert str(e.value).endswith("masked reshuffle %d: A 0 does not decode" % chunk), str(e.value)
+    finally:
+        g.close()

@@ -1,9 +1,11 @@
 """bpp_reshuffle_* on the GPU: output cards and proofs byte-exact against the
 reference helper (tests/reshuffle_ref.py) and the committed fixtures, batches
 across a wave boundary, the edge inputs, every refusal by name, per-proof
-verdicts, a three-player chain over one committed deck, and the batch's secrets
-wiped."""
+verdicts, a three-player chain over one committed deck, the batch's secrets wiped, every
+refusal's text, and a batch one proof longer than a launch sequence takes."""
+import ctypes
 import json
+import random
 import sys
 from pathlib import Path
 
@@ -19,7 +21,8 @@ from oracle.merlin import pedersen_gens_default  # noqa: E402
 pytestmark = pytest.mark.gpu
 L = rr.L
 GOLDEN = json.loads((HERE / "golden" / "reshuffle.json").read_text())["cases"]
-VERIFY, DECOMPRESS, NONCANONICAL = 6, 3, 4
+ARG, LEN, VERIFY, DECOMPRESS, NONCANONICAL = 1, 2, 6, 3, 4
+K_TEXT = "reshuffle: k > 342 (the inner circuit's 2k - 2 gates pass the plain bound of 682)"
 
 
 @pytest.fixture(scope="module")
@@ -285,3 +288,99 @@ def test_secrets_are_wiped(gens, ctx):
     rs.shuffle_batch(cards, [rr.rand_perm(k, b"wipe-%d" % p) for p in range(3)],
                      blinds=[[rr.sb(rr.rand_scalar(b"wipe-r%d-%d" % (p, i))) for i in range(k)] for p in range(3)])
     assert ctx.secret_residue() == 0
+
+
+def test_refusal_texts(gens, one):
+    """k = 3, at most 3 proofs a call: what bpp_ctx_last_error ends with after
+    each refusal that names a proof, the proof's index (never 0 alone) and the
+    point's among them."""
+    import bpperm
+    rs, cards, out, pf, o = one
+    perm, seed = reference(3)[0][1], reference(3)[0][2]
+    lib, bad = rs.ctx.lib, b"\xff" * 32
+
+    def text_of(code, f, *a, **kw):
+        with pytest.raises(bpperm.BppError) as e:
+            f(*a, **kw)
+        assert e.value.code == code
+        return (lib.bpp_ctx_last_error(rs.ctx.h) or b"").decode()
+
+    def at(region, i):
+        return pf[:o[region] + 32 * i] + bad + pf[o[region] + 32 * i + 32:]
+
+    def verifier(code, q, ci=cards, co=out, proof=pf):  # three proofs, proof q as given
+        cis, cos, pfs = [cards] * 3, [out] * 3, [pf] * 3
+        cis[q], cos[q], pfs[q] = ci, co, proof
+        return text_of(code, rs.verify_batch, cis, cos, pfs)
+
+    # the prover
+    t = text_of(DECOMPRESS, rs.shuffle_batch, [cards, cards[:2] + [bad]], [perm, perm], seeds32=seed * 2)
+    assert t.endswith("reshuffle 1: input card 2 does not decode"), t
+    t = text_of(ARG, rs.shuffle_batch, [cards] * 3, [perm, perm, [0, 0, 1]], seeds32=seed * 3)
+    assert t.endswith("reshuffle 2: perm is not a bijection on [0, k)"), t
+    t = text_of(NONCANONICAL, rs.shuffle_batch, [cards] * 2, [perm] * 2, seeds32=seed * 2,
+                blinds=[[rr.sb(1)] * 3, [rr.sb(1), L.to_bytes(32, "little"), rr.sb(2)]])
+    assert t.endswith("reshuffle 1: non-canonical blind"), t
+    # the verifier, one case per class of point
+    t = verifier(DECOMPRESS, 1, ci=[cards[0], bad, cards[2]])
+    assert t.endswith("reshuffle 1: input card 1 does not decode"), t
+    t = verifier(DECOMPRESS, 2, co=out[:2] + [bad])
+    assert t.endswith("reshuffle 2: output card 2 does not decode"), t
+    t = verifier(DECOMPRESS, 0, proof=at("A", 1))
+    assert t.endswith("reshuffle 0: A 1 does not decode"), t
+    t = verifier(DECOMPRESS, 2, proof=at("E", 0))
+    assert t.endswith("reshuffle 2: E 0 does not decode"), t
+    t = verifier(DECOMPRESS, 1, proof=at("Ti", 2))
+    assert t.endswith("reshuffle 1: T 2 does not decode"), t
+    t = verifier(DECOMPRESS, 2, proof=at("T", 0))
+    assert t.endswith("reshuffle 2: T_S 0 does not decode"), t
+    t = verifier(NONCANONICAL, 2, proof=pf[:o["om"]] + L.to_bytes(32, "little") + pf[o["om"] + 32:])
+    assert t.endswith("reshuffle 2: a response scalar is not canonical"), t
+    # k = 343, on both sides
+    buf, sink = bytes(343 * 32), ctypes.create_string_buffer(343 * 32)
+    ident = (ctypes.c_uint32 * 343)(*range(343))
+    assert lib.bpp_reshuffle_prove_batch(rs.ctx.h, gens.h, 343, 1, buf, ident, None, seed, b"bp-perm", 7, sink,
+                                         sink) == LEN
+    assert (lib.bpp_ctx_last_error(rs.ctx.h) or b"").decode().endswith(K_TEXT)
+    assert lib.bpp_reshuffle_verify(rs.ctx.h, gens.h, 343, b"bp-perm", 7, buf, buf, buf, 32) == LEN
+    assert (lib.bpp_ctx_last_error(rs.ctx.h) or b"").decode().endswith(K_TEXT)
+
+
+def test_a_batch_across_a_chunk_boundary(ctx):
+    """k = 342: a launch sequence takes 2^22 / (5k + 1) = 2451 proofs, so 2452
+    shuffles of one committed deck run as two.  The batch verifies; with z_0 + 1
+    in proofs 0, 2450 and 2451 exactly those three fail; an undecodable A_0 in
+    proof 2451 alone refuses the batch and names that proof."""
+    import bpperm
+    k, chunk = 342, 2451
+    count = chunk + 1
+    assert chunk == (1 << 22) // (5 * k + 1)
+    rnd = random.Random(342)
+    g = bpperm.Gens(ctx, 1024)
+    try:
+        rs = bpperm.Reshuffler(g, k)
+        deck = b"".join(g.pedersen_commit([rr.sb(10 + i) for i in range(k)],
+                                          [rr.sb(rnd.randrange(L)) for _ in range(k)]))
+        cin = deck * count
+        cout, proofs = rs.shuffle_batch(cin, [rnd.sample(range(k), k) for _ in range(count)],
+                                        seeds32=rnd.randbytes(32 * count), raw=True)
+        assert rs.verify_batch(cin, cout, proofs)
+        pl, z0 = rs.proof_len, 32 * (3 * k + 1)
+        bad = bytearray(proofs)
+        for p in (0, chunk - 1, chunk):
+            at = p * pl + z0
+            bad[at:at + 32] = rr.sb(int.from_bytes(bad[at:at + 32], "little") + 1)
+        ok = ctypes.create_string_buffer(count)
+        rc = ctx.lib.bpp_reshuffle_verify_batch_each(ctx.h, g.h, k, count, b"bp-perm", 7, cin, cout, bytes(bad), ok)
+        text = (ctx.lib.bpp_ctx_last_error(ctx.h) or b"").decode()
+        assert rc == VERIFY
+        assert [p for p in range(count) if not ok.raw[p]] == [0, chunk - 1, chunk]
+        assert text.endswith("3 of %d proofs failed, the first at index 0" % count), text
+        bad = bytearray(proofs)
+        bad[chunk * pl:chunk * pl + 32] = b"\xff" * 32
+        with pytest.raises(bpperm.BppError) as e:
+            rs.verify_batch(cin, cout, bytes(bad))
+        assert e.value.code == DECOMPRESS
+        assert str(e.value).endswith("reshuffle %d: A 0 does not decode" % chunk), str(e.value)
+    finally:
+        g.close()

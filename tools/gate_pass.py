@@ -9,6 +9,12 @@ launches per profiled stage (Context.profile).  The entries:
     verify_groups           bpp_verify_groups, four kinds x 1024 (tools/groups_cost.py's wide mix)
     reshuffle_verify        bpp_reshuffle_verify_batch, 52 cards x 4096
     verify_each_one_bad     bpp_perm_verify_batch_each, 52 cards x 4096, one tampered proof (the fallback)
+    reshuffle_prove         bpp_reshuffle_prove_batch, 52 cards x 384
+    masked_reshuffle_prove  bpp_masked_reshuffle_prove_batch, 52 cards x 384
+    masked_reshuffle_verify bpp_masked_reshuffle_verify_batch, 52 cards x 4096
+    reshuffle_verify_each_one_bad, masked_reshuffle_verify_each_one_bad
+                            the two kinds' _verify_batch_each, 52 cards x 4096, one proof's z_0 with its
+                            lowest bit flipped (the sigma fallback)
 
     python tools/gate_pass.py TREE
 
@@ -78,6 +84,30 @@ rdeck = b"".join(gens.pedersen_commit([sb(10 + i) for i in range(K)], [sb(rnd.ra
 rin = rdeck * NV
 rout, rpf = rs.shuffle_batch(rin, [rnd.sample(range(K), K) for _ in range(NV)], seeds32=rnd.randbytes(32 * NV), raw=True)
 def reshuffle_verify(): check(lib.bpp_reshuffle_verify_batch(ctx.h, gens.h, K, NV, label, len(label), rin, rout, rpf), "rverify", ctx.h)
+# .. the same batch, proof 1000 with z_0's lowest bit flipped: every proof's own sigma MSM
+def one_bad(pf, pl, z0): return pf[:1000 * pl + z0] + bytes([pf[1000 * pl + z0] ^ 1]) + pf[1000 * pl + z0 + 1:]
+def each_bad(fn, *args):
+    def f():
+        rc = fn(ctx.h, gens.h, K, NV, *args, ok)
+        assert rc == 6 and ok.raw.count(b"\0") == 1 and ok.raw[1000] == 0, rc
+    return f
+rbad = one_bad(rpf, rs.proof_len, 32 * (3 * K + 1))
+reshuffle_each_bad = each_bad(lib.bpp_reshuffle_verify_batch_each, label, len(label), rin, rout, rbad)
+# .. and its prover: 384 shuffles of the deck, the scalars r_i drawn from fixed seeds
+rperms = (C.c_uint32 * (K * B))(*[i for _ in range(B) for i in rnd.sample(range(K), K)])
+rseeds = rnd.randbytes(32 * B)
+rout_b, rpf_b = C.create_string_buffer(32 * K * B), C.create_string_buffer(rs.proof_len * B)
+def reshuffle_prove(): check(lib.bpp_reshuffle_prove_batch(ctx.h, gens.h, K, B, rin, rperms, None, rseeds, label, len(label), rout_b, rpf_b), "rprove", ctx.h)
+# masked re-shuffle: the open deck over the same points under a committed point as the key, 4096 shuffles of it
+ms = bpperm.MaskedReshuffler(gens, K, gens.pedersen_commit([sb(9)], [sb(rnd.randrange(L))])[0])
+mkey, mlen = ms.key, ms.proof_len
+min_ = b"".join(bytes(32) + rdeck[32 * i:32 * i + 32] for i in range(K)) * NV
+mout, mpf = ms.shuffle_batch(min_, [rnd.sample(range(K), K) for _ in range(NV)], seeds32=rnd.randbytes(32 * NV), raw=True)
+def masked_reshuffle_verify(): check(lib.bpp_masked_reshuffle_verify_batch(ctx.h, gens.h, K, NV, mkey, label, len(label), min_, mout, mpf), "mverify", ctx.h)
+masked_each_bad = each_bad(lib.bpp_masked_reshuffle_verify_batch_each, mkey, label, len(label), min_, mout,
+                           one_bad(mpf, mlen, 32 * (3 * K + 2)))
+mout_b, mpf_b = C.create_string_buffer(64 * K * B), C.create_string_buffer(mlen * B)
+def masked_reshuffle_prove(): check(lib.bpp_masked_reshuffle_prove_batch(ctx.h, gens.h, K, B, mkey, min_, rperms, None, rseeds, label, len(label), mout_b, mpf_b), "mprove", ctx.h)
 def one_call(f):
     """the work counters' delta and the launches per stage of one call"""
     w0 = ctx.work(); f(); w1 = ctx.work()
@@ -97,5 +127,8 @@ def med(f, per):
     return {"value": sorted(out)[W // 2], "calls_per_window": reps, **one_call(f)}
 ENTRIES = (("verify", verify, NV), ("prove_circuit_two_half", prove_c, B), ("verify_pub", verify_pub, NV),
            ("verify_groups", verify_groups, NV), ("reshuffle_verify", reshuffle_verify, NV),
-           ("verify_each_one_bad", verify_each_bad, NV))
+           ("verify_each_one_bad", verify_each_bad, NV), ("reshuffle_prove", reshuffle_prove, B),
+           ("masked_reshuffle_prove", masked_reshuffle_prove, B), ("masked_reshuffle_verify", masked_reshuffle_verify, NV),
+           ("reshuffle_verify_each_one_bad", reshuffle_each_bad, NV),
+           ("masked_reshuffle_verify_each_one_bad", masked_each_bad, NV))
 print(json.dumps({name: med(f, per) for name, f, per in ENTRIES}))
